@@ -2,6 +2,7 @@
 """bench.py -- BASELINE.json metric: D-D edges aggregated / s over encoder forward + backward.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload biosnap|biosnap963|synthetic|synthetic-small]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over the full graph: `z = FMEncoder.forward(...)` (P-P GCN x2,
 P->D mean, two R-GCN layers) followed by its backward with a fixed upstream gradient g ~ N(0,1)
@@ -39,6 +40,7 @@ Objects on the JSON line besides the contract's fields:
                 config 5 on one GPU) and the whole graphed training epoch (tip.py:24-30), each timed by
                 this process after the headline measurement (fewer steps; --no-extras skips them).
   cpu_baseline  the oracle's CPU port on the host cores (rank 0, N = 1 only), bounded sample.
+  dumped_outputs  with --dump-outputs DIR: what was written there (z.npy, grad.<parameter>.npy of the last timed step).
   preprocess_s / init_s  the first step on the real graph (all gather plans are built there) / before it, one step
                 on a 6 000-edge toy graph: what a fresh process spends loading torch's and libtipk's device code.
 """
@@ -80,7 +82,13 @@ def parse():
     ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 --pmc child passes (HBM traffic of this run)')
     ap.add_argument('--step-only', action='store_true',
                     help='run nothing but the warm-up and timed steps (PMC passes: bytes / (steps + warmup) = bytes per step)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed (z and every parameter gradient) as '
+                         'DIR/<name>.npy in float32, at most 64 MB in all (rank 0; inputs are seeded: runs compare output for output)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -824,6 +832,33 @@ def timed(run, steps, warmup, fence):
     return time.perf_counter() - t0
 
 
+DUMP_BYTES = 64 << 20            # --dump-outputs: budget of all arrays together
+
+
+def dump_outputs(dirname, z, grads):
+    """Write z and the parameter gradients of one step as DIR/z.npy and DIR/grad.<parameter>.npy (float32).  If they hold
+    more than DUMP_BYTES together, every array keeps the same fraction of its elements: a sorted sample of its flat indices
+    drawn from a generator seeded by the array's name (the same elements on every run), stored 1-D.  -> summary dict"""
+    import zlib
+    import numpy as np
+    arrays = [('z', z)] + [('grad.' + k, g) for k, g in sorted(grads.items()) if g is not None]
+    arrays = [(name, np.ascontiguousarray(t.detach().float().cpu().numpy())) for name, t in arrays]
+    total = sum(a.size * 4 for _, a in arrays)
+    frac = min(1.0, DUMP_BYTES / float(max(total, 1)))
+    os.makedirs(dirname, exist_ok=True)
+    written, sampled = 0, []
+    for name, a in arrays:
+        if frac < 1.0:
+            keep = int(a.size * frac)
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        written += a.nbytes
+    return {'dir': os.path.abspath(dirname), 'arrays': len(arrays), 'bytes': written, 'sampled': sampled,
+            'what': 'z and the parameter gradients of the last timed step (float32)'}
+
+
 def replay_event_stats(run, n, fence):
     """Per-replay GPU durations of the timed object (hipEvent timing, median of >= 20): one HIP event pair around
     EACH of n replays on the launch stream -> {n, median_us, p10_us, p90_us, min_us, max_us}.  Reported next to the contract's
@@ -1009,11 +1044,12 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    import fcntl
-    with open(os.path.join(ROOT, 'tip_amd', '.build.lock'), 'w') as lk:    # ranks started by a launcher: ONE `make` at a time
-        fcntl.flock(lk, fcntl.LOCK_EX)                                     # (the first builds, the others find it fresh)
-        _lib.ensure_built()                        # child `make` if the .so is missing / stale (before GPU use)
-        fcntl.flock(lk, fcntl.LOCK_UN)
+    if _lib._stale_reason(_lib.LIB_PATH) is not None:   # a build is due (a fresh library needs no lock: the tree may be read-only)
+        import fcntl
+        with open(os.path.join(ROOT, 'tip_amd', '.build.lock'), 'w') as lk:    # ranks started by a launcher: ONE `make` at a time
+            fcntl.flock(lk, fcntl.LOCK_EX)                                     # (the first builds, the others find it fresh)
+            _lib.ensure_built()                    # child `make` if the .so is missing / stale (before GPU use)
+            fcntl.flock(lk, fcntl.LOCK_UN)
     args.gpus = world
     assert torch.cuda.is_available(), 'bench.py needs a GPU (the product path has no CPU fallback)'
     n_dev = torch.cuda.device_count()
@@ -1135,6 +1171,13 @@ def main():
             run()
         fence()
     elapsed = timed(run, args.steps, args.warmup, fence)
+    dumped = None
+    if args.dump_outputs and rank == 0:                       # before anything else runs the step again
+        if launch == 'graph':
+            z_last, grads_last = b.outputs()
+        else:                                                  # (also when a capture succeeded here but not on every rank)
+            z_last, grads_last = b.z, {k: prm.grad for k, prm in enc.named_parameters()}
+        dumped = dump_outputs(args.dump_outputs, z_last, grads_last)
     replay_stats = None
     if world == 1 and not args.step_only:
         replay_stats = replay_event_stats(run, max(100, args.steps), fence)
@@ -1198,6 +1241,8 @@ def main():
         }
         if replay_stats is not None:
             out['replay_events'] = replay_stats
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         if multi is not None:
             out['multi_step_graph'] = multi
         if per_rank_ms is not None:

@@ -1,5 +1,5 @@
 """-m gpu: the one-shot all-reduce over peer-mapped mailboxes (include/tipk.h section 8, tip_amd/csrc/tipk_peer.hip) with
-2 and 4 ranks SHARING the one GPU of the test box (hipIpc mappings of the other processes' mailboxes on the same
+2, 4 and 5 ranks SHARING the one GPU of the test box (hipIpc mappings of the other processes' mailboxes on the same
 device; on an 8-GPU node the same code writes over xGMI): sums against a float64 reference, identical bits on every
 rank, repeated calls (both mailbox halves, growing sequence numbers), sizes from one element to several chunks, inside
 a captured hipGraph replayed with changing inputs, and the relation-sharded encoder layer on top of it."""
@@ -88,7 +88,7 @@ def _worker(rank, world, port, ret):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize('world', [2, 4, 8])
+@pytest.mark.parametrize('world', [2, 4, 5])          # at most 6 processes may hold the GPU: this one and 5 ranks
 def test_direct_exchange_ranks_sharing_one_gpu(world):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')

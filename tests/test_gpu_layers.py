@@ -664,7 +664,7 @@ def _shard_worker(rank, world, port, ret, max_relations=12):
         st = Setting()
         from tip_amd import neg_sampling as NS
         stamp('data dict')
-        # the UNSHARDED model runs on rank 0 only (8 ranks share one GPU: eight full-size references cost 9 minutes);
+        # the UNSHARDED model runs on rank 0 only (5 ranks share one GPU: a full-size reference on each costs minutes);
         # what the other ranks compare against travels through the process group
         ref_pack = [None]
         if rank == 0:
@@ -802,12 +802,13 @@ def test_config4_biosnap_sharded_over_four_ranks():
 
 
 @pytest.mark.timeout(1500)
-def test_config4_full_biosnap_sharded_over_eight_ranks():
-    """BASELINE config 4 at the rank count it names and at FULL size: all 1 097 relations over EIGHT ranks (sharing the one
-    GPU of the test box over gloo; 8 x MI355X over RCCL is the driver's to run).  With 8 shards the partition, the per-rank
-    plan sizes and the forward route (>= 4 ranks: Y route) differ from the 4-rank case; same assertions: loss, embeddings,
-    gradients, two Adam steps, the gathered test() record."""
-    _run_shard_workers(8, None)
+def test_config4_full_biosnap_sharded_over_five_ranks():
+    """BASELINE config 4 at FULL size over the most ranks one shared test box takes (at most 6 processes may hold the GPU:
+    this one and 5 ranks, sharing it over gloo; 8 x MI355X over RCCL is the driver's to run): all 1 097 relations over FIVE
+    ranks.  With an odd shard count the partition and the per-rank plan sizes differ from the 4-rank case, the forward
+    route is the same (>= 4 ranks: Y route); same assertions: loss, embeddings, gradients, two Adam steps, the gathered
+    test() record."""
+    _run_shard_workers(5, None)
 
 
 def test_graphed_train_step_matches_eager():

@@ -238,20 +238,20 @@ def test_bench_two_ranks_direct_exchange_and_timed_routes():
 
 
 @pytest.mark.timeout(1500)
-def test_bench_eight_ranks_oversubscribed_auto_collective():
-    """`bench.py --gpus 8 --oversubscribe` on BioSNAP (BASELINE config 4's rank count; the ranks share the one GPU, gloo):
-    the exchange is set up behind its self-test, both collectives are timed per message size and the faster kept, and the
-    line carries what the first real 8-GPU run will be read by: per-rank step times, the collective's timings, the
-    replicated stage and the Amdahl ceiling it implies."""
+def test_bench_four_ranks_oversubscribed_auto_collective():
+    """`bench.py --gpus 4 --oversubscribe` on BioSNAP (the ranks share the one GPU, gloo; at most 6 processes may hold it:
+    this one, bench.py's launcher and 4 ranks): the exchange is set up behind its self-test, both collectives are timed per
+    message size and the faster kept, and the line carries what the first real 8-GPU run will be read by: per-rank step
+    times, the collective's timings, the replicated stage and the Amdahl ceiling it implies."""
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     env.pop('TIPK_COLLECTIVE', None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--oversubscribe', '--steps', '3',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--oversubscribe', '--steps', '3',
                           '--warmup', '1', '--no-cpu-baseline', '--no-kernel-table'], env=env, capture_output=True, text=True, timeout=1400)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
-    assert rec['n_gpus'] == 8 and rec['value'] > 0 and 'relation-sharded x8' in rec['config']['parallelism']
-    assert len(rec['per_rank_ms_per_step']) == 8 and all(v > 0 for v in rec['per_rank_ms_per_step'])
+    assert rec['n_gpus'] == 4 and rec['value'] > 0 and 'relation-sharded x4' in rec['config']['parallelism']
+    assert len(rec['per_rank_ms_per_step']) == 4 and all(v > 0 for v in rec['per_rank_ms_per_step'])
     assert abs(max(rec['per_rank_ms_per_step']) - rec['ms_per_step']) < 1e-3
     ct = rec['config']['collective_timing']
     assert ct and (('per_size' in ct and len(ct['per_size']) >= 3 and

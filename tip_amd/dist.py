@@ -236,7 +236,7 @@ class DirectExchange(object):
     once -- posts flags, waits for the others' flags and adds the slots in rank order.  One kernel per rank and call
     instead of the 2 (w - 1) dependent steps of a ring; results are identical on every rank and from run to run.
     The mailboxes are exchanged as hipIpc handles through the process group (any backend) once, at construction.
-    It is validated with ranks SHARING one GPU (tests/test_gpu_direct_exchange.py: 2, 4 and 8 ranks, a peer that skips a
+    It is validated with ranks SHARING one GPU (tests/test_gpu_direct_exchange.py: 2, 4 and 5 ranks, a peer that skips a
     call); over xGMI it has never run.  `RelationShard.try_direct_exchange` therefore sets it up only if every rank can map
     every mailbox and a timed self-test gives the right sums, `choose_collective` then times it against the process
     group per message size and keeps the faster (bench.py does both for N > 1); the flag wait is bounded, and a wait that
