@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 23
+#define TIPK_ABI_VERSION 24
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -965,6 +965,78 @@ int tipk_plan_link_words(const int64_t* src, const int64_t* dst, int64_t n_edges
 int tipk_host_plan_array(const tipk_host_plan* plan, const char* name, const void** data, int64_t* count, int* elem_bytes);
 int64_t tipk_host_plan_scalar(const tipk_host_plan* plan, const char* name);
 void tipk_host_plan_free(tipk_host_plan* plan);
+
+/* 10d. The whole encoder behind one handle: FMEncoder.forward (src/layers.py:520-550, identity protein and drug features) and its
+ *     autograd as the fused schedule of tip_amd/encoder.py `_EncoderStep` -- 8 + 8 launches, the same kernels with the same
+ *     arguments in the same order (bit-identical results).  tip_amd/csrc/tipk_encoder.hip.
+ *     tipk_encoder_build (allocates and synchronises, like tipk_graph_build): the graphs as the reference holds them, idx_bytes 4 | 8
+ *         for all of them, on the device or on the host -- pp_index [2][n_pp_edges] (pp_train_indices), dp_index [2][n_dp_edges]
+ *         (dp_edge_index: proteins 0 .. n_prot - 1, drugs n_prot .. n_prot + n_drug - 1), dd_index [2][n_dd_edges] (dd_train_idx)
+ *         with dd_range [n_rel][2] (dd_train_range: consecutive blocks covering the edge list).  The P-P encoder is the reference's
+ *         PPEncoder(n_prot): GCNConv(n_prot, 32) -> GCNConv(32, 16).  Every plan is built here, once.  TIPK_EINVAL for NULL,
+ *         negative or inconsistent arguments (ids out of range, ranges that do not tile the edge list, add with n_embed !=
+ *         prot_drug_dim); TIPK_EUNSUPPORTED where the fused kernels do not take the shape (the conditions of encoder.py
+ *         `usable`: more than 1 024 drugs, n_hid1 != 32, widths or base counts a `*_supported` query refuses, a P -> D edge that
+ *         starts at a drug, every protein a P -> D source) -- there is no other route behind the handle.
+ *     tipk_encoder_workspace_bytes: size of the caller-owned workspace (16-byte aligned).  It holds what the backward pass reads
+ *         (conv outputs, x0, x1, the P -> D mean, both layers' pair cells and node-major XB, one pair-gradient table per layer) and
+ *         the scratch of both passes.  tipk_encoder_workspace_init (one hipMemsetAsync on `stream`, capturable) prepares a workspace
+ *         before its first use: the passes read parts of it as zeros (unlinked cells, XB padding, unused gradient rows) and keep them
+ *         at zero.  One workspace per handle in flight; two handles with their own workspaces on two streams share nothing mutable.
+ *     tipk_encoder_fwd: z_out [n_drug x n_hid2] (ldz = n_hid2) = the encoder output.  Parameters (tipk_encoder_params) in the
+ *         reference's state_dict shapes, contiguous; the two GCN weights [out, in] as row-major storage (lin_layout 0: two launches
+ *         more forward, two more backward -- transposes) or stored transposed, [in, out] in memory (lin_layout 1: how this
+ *         package's modules keep them; the 16-launch schedule).  d_norm [n_drug] (nullable = 1).  x_drug must be NULL (identity drug
+ *         features: x_drug @ embed = embed); dense features: TIPK_EUNSUPPORTED.
+ *     tipk_encoder_bwd: from grad_z [n_drug x n_hid2] (ld_g = n_hid2) every parameter gradient in the parameter's own shape and
+ *         lin_layout (overwritten; grads->embed is also the gradient of the identity drug features, g_x_drug must be NULL).
+ *         flags TIPK_ENCODER_FROM_FWD: the workspace still holds what tipk_encoder_fwd with THESE parameters left in it (the
+ *         semantics of TIPK_RGCN_WORKSPACE_FROM_FWD); flags 0 recomputes XB and the pair cells first (always safe, 3 launches more).
+ *     fwd / bwd never allocate, never synchronise and return a status for every failure (no C++ exception crosses the ABI):
+ *     both can be captured into a hipGraph. */
+#define TIPK_ENCODER_FROM_FWD 1
+typedef struct tipk_encoder tipk_encoder;
+typedef struct tipk_encoder_dims {
+    int n_embed, prot_drug_dim, n_hid1, n_hid2, num_base;
+    int cat;                                   /* 1: mod 'cat', 0: mod 'add' */
+} tipk_encoder_dims;
+typedef struct tipk_encoder_params {
+    const float* embed;                        /* embed                      [n_drug x n_embed] */
+    const float* pp_w1; const float* pp_b1;    /* pp_encoder.conv1.lin.weight [32 x n_prot], .bias [32] */
+    const float* pp_w2; const float* pp_b2;    /* pp_encoder.conv2.lin.weight [16 x 32], .bias [16] */
+    const float* hgcn_w;                       /* hgcn.weight                [16 x prot_drug_dim] */
+    const float* basis1; const float* att1; const float* root1;   /* rgcn1: [num_base x d_in x n_hid1], [n_rel x num_base], [d_in x n_hid1] */
+    const float* basis2; const float* att2; const float* root2;   /* rgcn2: [num_base x n_hid1 x n_hid2], [n_rel x num_base], [n_hid1 x n_hid2] */
+    int lin_layout;                            /* 0: the GCN weights row-major [out, in]; 1: stored [in, out] */
+} tipk_encoder_params;
+typedef struct tipk_encoder_grads {            /* the same tensors, written (GCN weights in the params' lin_layout) */
+    float* embed; float* pp_w1; float* pp_b1; float* pp_w2; float* pp_b2; float* hgcn_w;
+    float* basis1; float* att1; float* root1; float* basis2; float* att2; float* root2;
+} tipk_encoder_grads;
+int tipk_encoder_build(const void* pp_index, int64_t n_pp_edges, const void* dp_index, int64_t n_dp_edges, const void* dd_index,
+                       int64_t n_dd_edges, const void* dd_range, int64_t n_rel, int idx_bytes, int64_t n_prot, int64_t n_drug,
+                       const tipk_encoder_dims* dims, tipk_encoder** enc_out);
+int64_t tipk_encoder_workspace_bytes(const tipk_encoder* enc);
+int tipk_encoder_workspace_init(const tipk_encoder* enc, void* workspace, int64_t workspace_bytes, tipk_stream_t stream);
+int tipk_encoder_fwd(const tipk_encoder* enc, const tipk_encoder_params* params, const float* x_drug /* must be NULL */, int64_t ld_x,
+                     const float* d_norm /* nullable */, float* z_out, int64_t ldz, void* workspace, int64_t workspace_bytes,
+                     tipk_stream_t stream);
+int tipk_encoder_bwd(const tipk_encoder* enc, const tipk_encoder_params* params, const float* x_drug /* must be NULL */, int64_t ld_x,
+                     const float* d_norm /* nullable */, const float* grad_z, int64_t ld_g, tipk_encoder_grads* grads,
+                     float* g_x_drug /* must be NULL */, int64_t ld_gx, int flags, void* workspace, int64_t workspace_bytes,
+                     tipk_stream_t stream);
+int tipk_encoder_destroy(tipk_encoder* enc);
+/* The encoder's plans that were built only in Python before, as host plans (section 10c; tests/test_host_encoder_plans.py):
+ *   tipk_plan_hier_csr   layers.py `hier_graph` pd_csr -- arrays "fwd_ptr", "fwd_src", "scale" (float), "fwd_wg" ([n][2] =
+ *                        `drug_workgroups`), "fwd_order", "t_ptr", "t_dst", "t_w" (float), "t_wg" (`deal_rows_by_edges` with the
+ *                        given limits: tipk_pd_stage_bwd_limits); scalar "n_src".  dst in the concatenated node space.
+ *   tipk_plan_gcn_norm   layers.py `gcn_norm_graph(edge_index, n_nodes, d=d, rows=rows)` (rows ascending, nullable = all) as the module
+ *                        builds it on the DEVICE: deg^-1/2 correctly rounded (torch's device pow(-0.5); its CPU pow rounds twice).  The
+ *                        grouped gather plans under "fwd." and "bwd." ("row_id", "edge_w", "items", "perm"; "n_items", "group_slots"). */
+int tipk_plan_hier_csr(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n_all, int64_t n_source, int64_t n_table,
+                       int max_rows, int max_edges, tipk_host_plan** plan_out);
+int tipk_plan_gcn_norm(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n_nodes, const int64_t* rows /* nullable */,
+                       int64_t n_rows, int d, tipk_host_plan** plan_out);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libtipk.so')
 CSRC = os.path.join(_HERE, 'csrc')
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class TipkError(RuntimeError):
@@ -51,6 +51,26 @@ class WgGemmDesc(C.Structure):
                 ('b2', C.c_void_p), ('b2_sk', C.c_int64), ('b2_sn', C.c_int64),
                 ('k2', C.c_int64),
                 ('gate', C.c_void_p), ('gate_sm', C.c_int64), ('gate_sz', C.c_int64)]
+
+
+ENCODER_PARAMS = ('embed', 'pp_w1', 'pp_b1', 'pp_w2', 'pp_b2', 'hgcn_w', 'basis1', 'att1', 'root1', 'basis2', 'att2', 'root2')
+ENCODER_FROM_FWD = 1                           # TIPK_ENCODER_FROM_FWD
+
+
+class EncoderDims(C.Structure):
+    """struct tipk_encoder_dims (include/tipk.h section 10d)."""
+    _fields_ = [('n_embed', C.c_int), ('prot_drug_dim', C.c_int), ('n_hid1', C.c_int), ('n_hid2', C.c_int), ('num_base', C.c_int),
+                ('cat', C.c_int)]
+
+
+class EncoderParams(C.Structure):
+    """struct tipk_encoder_params."""
+    _fields_ = [(k, C.c_void_p) for k in ENCODER_PARAMS] + [('lin_layout', C.c_int)]
+
+
+class EncoderGrads(C.Structure):
+    """struct tipk_encoder_grads."""
+    _fields_ = [(k, C.c_void_p) for k in ENCODER_PARAMS]
 
 
 GROUP_MAX = 6                                  # TIPK_GROUP_MAX
@@ -169,6 +189,14 @@ SIGNATURES = {
     'tipk_host_plan_array': (_I, [_P, C.c_char_p, _P, _P, _P]),
     'tipk_host_plan_scalar': (_L, [_P, C.c_char_p]),
     'tipk_host_plan_free': (None, [_P]),
+    'tipk_plan_hier_csr': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P]),
+    'tipk_plan_gcn_norm': (_I, [_P, _P, _L, _L, _P, _L, _I, _P]),
+    'tipk_encoder_build': (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _I, _L, _L, _P, C.POINTER(C.c_void_p)]),
+    'tipk_encoder_workspace_bytes': (_L, [_P]),
+    'tipk_encoder_workspace_init': (_I, [_P, _P, _L, _P]),
+    'tipk_encoder_fwd': (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _L, _P]),
+    'tipk_encoder_bwd': (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _I, _P, _L, _P]),
+    'tipk_encoder_destroy': (_I, [_P]),
     'tipk_split_flags': (_I, [_P, _L, _L, C.c_double, C.c_uint64, _P, _P, _P]),
     'tipk_split_scatter': (_I, [_P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }

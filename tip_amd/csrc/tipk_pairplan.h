@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include <vector>
+#include "../../include/tipk.h"
 
 namespace tipk_plan {
 
@@ -65,3 +66,8 @@ void pair_link_words(const int64_t* src, const int64_t* dst, int64_t n_edges, in
 bool relations_symmetric(const int64_t* src, const int64_t* dst, const int64_t* rel, int64_t n_edges, int64_t n_nodes);
 
 }  // namespace tipk_plan
+
+// host plans of include/tipk.h section 10c filled by other files of the library (tipk_encoder.hip); nullptr / -1 on failure
+tipk_host_plan* tipk_host_plan_new();
+int tipk_host_plan_put(tipk_host_plan* h, const char* name, const void* data, int64_t count, int elem_bytes);
+int64_t* tipk_host_plan_scalar_ref(tipk_host_plan* h, const char* name);

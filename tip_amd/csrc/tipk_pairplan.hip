@@ -683,3 +683,15 @@ extern "C" int64_t tipk_host_plan_scalar(const tipk_host_plan* h, const char* na
 }
 
 extern "C" void tipk_host_plan_free(tipk_host_plan* h) { delete h; }
+
+tipk_host_plan* tipk_host_plan_new() { return new (std::nothrow) tipk_host_plan; }
+
+int tipk_host_plan_put(tipk_host_plan* h, const char* name, const void* data, int64_t count, int elem_bytes) {
+    std::vector<char>& a = h->arrays[name];
+    a.resize((size_t)count * (size_t)elem_bytes);
+    if (!a.empty()) memcpy(a.data(), data, a.size());
+    h->elem[name] = elem_bytes;
+    return TIPK_OK;
+}
+
+int64_t* tipk_host_plan_scalar_ref(tipk_host_plan* h, const char* name) { return &h->scalars[name]; }
