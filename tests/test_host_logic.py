@@ -885,3 +885,113 @@ def test_pd_stage_row_deal_and_forward_workgroup_descs():
             c = int(cnt[r])
             assert (w == 16) == (c > 512) and (w == 4) == (64 < c <= 512)
     assert sorted(seen) == list(range(cnt.numel()))
+
+
+def _sampler_rel_ptrs():
+    dd = build_data_dict()
+    rg = dd['dd_train_range']
+    return {
+        'biosnap': np.r_[0, rg[:, 1].numpy()].astype(np.int64),
+        'one_huge_relation': np.array([0, 4_000_000], dtype=np.int64),
+        'empty_first_middle_last': np.r_[0, np.cumsum([0, 0, 5000, 0, 30000, 17, 0, 0])].astype(np.int64),
+    }
+
+
+@pytest.mark.parametrize('case', ['biosnap', 'one_huge_relation', 'empty_first_middle_last'])
+@pytest.mark.parametrize('n_wg', [1, 512])
+def test_sampler_units_give_every_position_to_exactly_one_unit(case, n_wg):
+    """The bitmap sampler's deal (tip_amd.neg_sampling.sampler_units): every position belongs to exactly one unit, the
+    units of a relation tile it in order without gaps, a workgroup walks the units of one relation in increasing
+    position order, and the deal is the same on every call."""
+    from tip_amd.neg_sampling import sampler_units
+    rel_ptr = _sampler_rel_ptrs()[case]
+    ptr, units = sampler_units(torch.from_numpy(rel_ptr), n_wg)
+    ptr, units = ptr.numpy(), units.numpy().astype(np.int64)
+    assert ptr.shape == (n_wg + 1,) and ptr[0] == 0 and ptr[-1] == units.shape[0] and (np.diff(ptr) >= 0).all()
+    hits = np.zeros(int(rel_ptr[-1]), dtype=np.int32)
+    for r, a, b in units:
+        assert rel_ptr[r] <= a < b <= rel_ptr[r + 1]
+        hits[a:b] += 1
+    assert (hits == 1).all()
+    for r in range(rel_ptr.size - 1):
+        mine = units[units[:, 0] == r]
+        if rel_ptr[r] == rel_ptr[r + 1]:
+            assert mine.shape[0] == 0                                   # an empty relation has no unit
+            continue
+        mine = mine[np.argsort(mine[:, 1])]
+        assert mine[0, 1] == rel_ptr[r] and mine[-1, 2] == rel_ptr[r + 1] and (mine[1:, 1] == mine[:-1, 2]).all()
+    for w in range(n_wg):
+        mine = units[ptr[w]:ptr[w + 1]]
+        for r in np.unique(mine[:, 0]):
+            starts = mine[mine[:, 0] == r, 1]
+            assert (np.diff(starts) > 0).all()
+    p2, u2 = sampler_units(torch.from_numpy(rel_ptr), n_wg)
+    assert np.array_equal(p2.numpy(), ptr) and np.array_equal(u2.numpy(), units)
+
+
+def test_sampler_units_deal_consecutive_units_of_one_relation():
+    """The deals the GPU suite uses to reach the bitmap sampler's `rel == have` path (a workgroup's next unit belongs to
+    the relation whose bitmap it already holds: no rebuild, no barrier in front of the draws) do contain such pairs."""
+    from tip_amd.neg_sampling import sampler_units
+
+    def consecutive(rel_ptr, n_wg):
+        ptr, units = sampler_units(torch.tensor(rel_ptr), n_wg)
+        return sum(int(units[i, 0] == units[i + 1, 0]) for w in range(n_wg) for i in range(int(ptr[w]), int(ptr[w + 1]) - 1))
+
+    assert consecutive([0, 20000], 1) == 1                              # two units of 10 000 on one workgroup
+    assert consecutive([0, 4_000_000], 512) > 100
+    assert consecutive(_sampler_rel_ptrs()['biosnap'].tolist(), 512) == 0     # (the training deal never takes that path)
+
+
+def test_sampler_spec_keeps_the_64th_draw_on_a_saturated_relation():
+    """Every cell of the relation is a positive: every attempt is rejected, and the spec keeps what attempt 63 drew."""
+    from oracle.philox_sampler import philox4x32_10, typed_negative_sampling_spec, MAX_ATTEMPTS
+    seed = 0x0123456789ABCDEF
+    for n in (4, 1):
+        cells = np.array([(u, v) for u in range(n) for v in range(n)], dtype=np.int64).T
+        pos = np.tile(cells, (1, 40))[:, :37 + 3 * n]
+        E = pos.shape[1]
+        got = typed_negative_sampling_spec(pos, n, [0, E], seed)
+        c = np.arange(E, dtype=np.uint64)
+        q = c >> np.uint64(2)
+        xs = philox4x32_10(q & np.uint64(0xFFFFFFFF), q >> np.uint64(32), np.full(E, MAX_ATTEMPTS - 1), 0,
+                           seed & 0xFFFFFFFF, seed >> 32)
+        x = np.choose((c & np.uint64(3)).astype(np.int64), xs)
+        cand = ((x * np.uint64(n * n)) >> np.uint64(32)).astype(np.int64)
+        assert np.array_equal(got, np.stack([cand // n, cand % n]))
+
+
+def test_sampler_spec_wide_branch_matches_python_integers():
+    """n^2 >= 2^32: one 64-bit candidate per Philox call, mulhi64(x1:x0, n^2).  The spec's vectorised mulhi64 against
+    Python integers, with the rejection loop restated per position."""
+    from oracle.philox_sampler import philox4x32_10, typed_negative_sampling_spec
+    rng = np.random.RandomState(12)
+    seed = 0xFEDCBA9876543210
+    for n in (65536, 70001, 4_000_000):
+        E = 300
+        pos = rng.randint(0, n, (2, E)).astype(np.int64)
+        pos[:, 150:] = pos[:, :150]                                     # repeated positives
+        offs = [0, 3]
+        nn = n * n
+
+        def first_draw(ctr):
+            x0, x1, _, _ = philox4x32_10(np.uint64(ctr & 0xFFFFFFFF), np.uint64(ctr >> 32), 0, 0, seed & 0xFFFFFFFF, seed >> 32)
+            return ((int(x0) | int(x1) << 32) * nn) >> 64
+
+        for e in range(100, 180):                                       # their first draw is a positive: drawn again
+            c0 = first_draw(e + offs[1])
+            pos[:, e + 120] = (c0 // n, c0 % n)
+        got = typed_negative_sampling_spec(pos, n, [0, 100, E], seed, pos_offset=offs)
+        for r, (a, b) in enumerate(((0, 100), (100, E))):
+            keys = set((pos[0, a:b] * n + pos[1, a:b]).tolist())
+            if r == 1:
+                assert all(first_draw(e + offs[1]) in keys for e in range(100, 180))
+            for e in range(a, b):
+                ctr = e + offs[r]
+                for attempt in range(64):
+                    x0, x1, _, _ = philox4x32_10(np.uint64(ctr & 0xFFFFFFFF), np.uint64(ctr >> 32), attempt, 0,
+                                                 seed & 0xFFFFFFFF, seed >> 32)
+                    cand = ((int(x0) | int(x1) << 32) * nn) >> 64
+                    if cand not in keys:
+                        break
+                assert (got[0, e], got[1, e]) == (cand // n, cand % n), (n, e)

@@ -186,6 +186,14 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red, int t) {
     return m;
 }
 
+// |v| for the magnitude bounds zmax / wmax that choose the fixed-point scales, +inf for a NaN or an infinity (fmaxf would
+// drop a NaN): a non-finite z or w cannot pass through the integer sums as a finite number.  Where the bound comes out
+// infinite the scales are NaN (`nonfinite_scale`) and the conversion back makes the loss and the gradients NaN.
+__device__ __forceinline__ float fx_mag(float v) { return fabsf(v) <= 3.402823466e38f ? fabsf(v) : __builtin_inff(); }
+__device__ __forceinline__ double nonfinite_scale(double scale, float zmax, float wmax) {
+    return zmax <= 3.402823466e38f && wmax <= 3.402823466e38f ? scale : __builtin_nan("");
+}
+
 __device__ __forceinline__ void fx_add(unsigned long long* p, float c, double scale) {
     atomicAdd(p, (unsigned long long)(long long)((double)c * scale));      // ds_add_u64
 }
@@ -227,20 +235,21 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
     float* red = zl + (((int64_t)n_nodes * ld + 3) & ~3LL);   // [16 waves][k] + [16]
     uint16_t* ixl = reinterpret_cast<uint16_t*>(red + 16 * k + 16);   // [4][TASK_MAX] ids of the current task
     const bool want_grad = g_z != nullptr;
-    float zmax = 0.f;
+    float zmax = 0.f, wmax = 0.f;
     for (int i = t; i < n_nodes * k; i += 1024) {
         const int r = i / k, c = i - r * k;
         const float v = z[i];
         zl[r * ld + c] = v;
-        zmax = fmaxf(zmax, fabsf(v));
+        zmax = fmaxf(zmax, fx_mag(v));
     }
     for (int i = t; i < n_nodes * lg; i += 1024) gzl[i] = 0ull;
-    double scale = 1.0;
-    if (want_grad) {
-        float wmax = 0.f;
-        for (int i = t; i < n_rel * k; i += 1024) wmax = fmaxf(wmax, fabsf(w[i]));
+    if (want_grad || MODE == 1) {                             // (the objective without gradients: they flag non-finite inputs)
+        for (int i = t; i < n_rel * k; i += 1024) wmax = fmaxf(wmax, fx_mag(w[i]));
         zmax = block_max_1024(zmax, red, t);
         wmax = block_max_1024(wmax, red, t);
+    }
+    double scale = 1.0;
+    if (want_grad) {
         // bound on sum |contribution| into any element: every position adds <= 4 |q| zmax wmax with
         // sum |q| <= 1 (fused objective: |q| <= 1/n each) or <= sum |g| over this workgroup's positions
         float bound = 4.f * zmax * wmax;
@@ -271,9 +280,9 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
         scale_w = ldexp(1.0, ex > 180 ? 180 : ex);
         if (blockIdx.x == 0 && t == 0) {                      // the finalize kernel divides by them
             const int64_t base = (int64_t)n_nodes * k + (int64_t)n_rel * k + 1;
-            reinterpret_cast<double*>(ws)[base] = scale;
-            reinterpret_cast<double*>(ws)[base + 1] = scale_w;
-            reinterpret_cast<double*>(ws)[base + 2] = scale_l;
+            reinterpret_cast<double*>(ws)[base] = nonfinite_scale(scale, zmax, wmax);
+            reinterpret_cast<double*>(ws)[base + 1] = nonfinite_scale(scale_w, zmax, wmax);
+            reinterpret_cast<double*>(ws)[base + 2] = nonfinite_scale(scale_l, zmax, wmax);
         }
     }
     __syncthreads();
@@ -430,12 +439,12 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
             float tot = 0.f;
             for (int wv = 0; wv < 16; ++wv) tot += red[16 * k + wv];
             if (ws) atomicAdd(ws + (int64_t)n_nodes * k + (int64_t)n_rel * k, (unsigned long long)(long long)((double)(tot * inv_n) * scale_l));
-            else atomicAdd(loss_out, tot * inv_n);
+            else atomicAdd(loss_out, (float)nonfinite_scale(tot * inv_n, zmax, wmax));
         }
     }
     if (want_grad) {
         __syncthreads();
-        const double inv_scale = 1.0 / scale;
+        const double inv_scale = 1.0 / nonfinite_scale(scale, zmax, wmax);
         for (int i = t; i < n_nodes * k; i += 1024) {
             const int r = i / k, c = i - r * k;
             const long long a = (long long)gzl[r * lg + c];
@@ -518,10 +527,10 @@ __global__ __launch_bounds__(1024) void distmult_objective_kernel(
         const int r = i / K, c = i - r * K;
         const float v = z[i];
         zl[r * ld + c] = v;
-        zmax = fmaxf(zmax, fabsf(v));
+        zmax = fmaxf(zmax, fx_mag(v));
     }
     for (int i = t; i < n_nodes * lg; i += 1024) gzl[i] = 0ull;
-    for (int i = t; i < n_rel * K; i += 1024) wmax = fmaxf(wmax, fabsf(w[i]));
+    for (int i = t; i < n_rel * K; i += 1024) wmax = fmaxf(wmax, fx_mag(w[i]));
     zmax = block_max_1024(zmax, red, t);
     wmax = block_max_1024(wmax, red, t);
     // scales: identical in every workgroup (they depend on z and w only); per-TERM scale for d z (fx_add_term)
@@ -539,9 +548,9 @@ __global__ __launch_bounds__(1024) void distmult_objective_kernel(
     const double scale_l = 1125899906842624.0;                            // 2^50: the objective is < 2^7
     if (blockIdx.x == 0 && t == 0) {                                      // the finalize kernel divides by them
         const int64_t base = (int64_t)n_nodes * K + (int64_t)n_rel * K + 1;
-        reinterpret_cast<double*>(ws)[base] = scale;
-        reinterpret_cast<double*>(ws)[base + 1] = scale_w;
-        reinterpret_cast<double*>(ws)[base + 2] = scale_l;
+        reinterpret_cast<double*>(ws)[base] = nonfinite_scale(scale, zmax, wmax);
+        reinterpret_cast<double*>(ws)[base + 1] = nonfinite_scale(scale_w, zmax, wmax);
+        reinterpret_cast<double*>(ws)[base + 2] = nonfinite_scale(scale_l, zmax, wmax);
     }
     __syncthreads();
     const float scale_f = (float)scale;
@@ -733,10 +742,11 @@ __global__ __launch_bounds__(256) void det_finalize_kernel(unsigned long long* w
                                                            float* loss_out, float* g_z, float* g_w, int store) {
     const double* sc = reinterpret_cast<const double*>(ws + n_z + n_w + 1);
     const double inv_z = 1.0 / sc[0], inv_w = 1.0 / sc[1], inv_l = 1.0 / sc[2];
+    const bool nonfinite = sc[2] != sc[2];                     // NaN scales: z or w held a NaN or an infinity
     const int64_t total = n_z + n_w + 1;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const long long a = (long long)ws[i];
-        if (a == 0 && !store) continue;
+        if (a == 0 && !store && !nonfinite) continue;
         if (a != 0) ws[i] = 0ull;
         if (i < n_z) { if (g_z) g_z[i] = (store ? 0.0f : g_z[i]) + (float)((double)a * inv_z); }
         else if (i < n_z + n_w) { if (g_w) g_w[i - n_z] = (store ? 0.0f : g_w[i - n_z]) + (float)((double)a * inv_w); }

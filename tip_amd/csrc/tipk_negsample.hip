@@ -308,8 +308,12 @@ __global__ __launch_bounds__(1024) void neg_sample_bitmap_kernel(
             }
             store_pair(e, cand);
         }
-        __syncthreads();                                   // (the queue has been read)
+        __syncthreads();                                   // (the queue and its length have been read)
         if (t == 0) *qlen = 0u;
+        // the zero lands before any wave parks a position of the next unit: without this barrier a next unit of the SAME
+        // relation (no bitmap build, no barrier in front of its draws) could count a parked position and then lose it to
+        // this store -- the position was never drawn again and its output slot kept whatever was there
+        __syncthreads();
         }
         cur = nxt;
     }

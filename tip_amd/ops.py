@@ -1150,28 +1150,38 @@ def distmult_loss(z, weight, pos_index, neg_index, edge_type, need_grad=True):
 
 
 def typed_negative_sampling_device(pos_key_sorted, rel_ptr, n_rel, n_nodes, seed, n_positions, dtype=torch.int64,
-                                   call_counter=None, wg=None, pos_offset=None, packed=False, keys32=None):
+                                   call_counter=None, wg=None, pos_offset=None, packed=False, keys32=None, out=None):
     """pos_offset: optional int64 device tensor [n_rel]: Philox counter of position e of relation r = e + pos_offset[r]
     (relation-sharded runs: the position's number in the whole triple list).
     call_counter: optional int64 device tensor [2] = {position, seed} (the stream's state): the
     Philox key is derived on the device from it, `seed` is ignored, and the position is advanced by
-    one afterwards."""
-    require_device(pos_key_sorted, rel_ptr, call_counter)
+    one afterwards.
+    out: optional preallocated result on the device -- int32 [n_positions] (packed), or `dtype` [2, n_positions] whose two
+    rows are contiguous; every position is written."""
+    require_device(pos_key_sorted, rel_ptr, call_counter, out)
     dev = pos_key_sorted.device
+    if out is not None:
+        shape = (n_positions,) if packed else (2, n_positions)
+        if (tuple(out.shape) != shape or out.dtype != (torch.int32 if packed else dtype) or out.device != dev
+                or out.stride()[-1] != 1):
+            raise ValueError('out must be a %s %s tensor on %s with unit stride along positions'
+                             % (torch.int32 if packed else dtype, shape, dev))
     st = stream_ptr(dev)
     wg_ptr, wg_units = wg if (wg is not None and not switches.on('TIPK_NO_BITMAP')) else (None, None)
     # a stream state with a ticket word {position, seed, ticket}: the sampling launch moves the position on itself
     adv = 1 if (call_counter is not None and call_counter.numel() >= 3 and n_positions > 0 and n_rel > 0) else 0
     if packed:                                     # one 32-bit word u | v << 16 per position (same draws, same pairs)
         assert n_nodes <= 65535
-        out = torch.empty((n_positions,), dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty((n_positions,), dtype=torch.int32, device=dev)
         check(lib().tipk_typed_negative_sampling(ptr(pos_key_sorted), ptr(rel_ptr), n_rel, n_nodes, seed, ptr(call_counter), adv,
                                                  ptr(wg_ptr), ptr(wg_units), 0 if wg_ptr is None else wg_ptr.numel() - 1,
                                                  ptr(pos_offset), ptr(keys32), ptr(out), None, 2, n_positions, st),
               'tipk_typed_negative_sampling')
         out._tipk_packed_pairs = True
     else:
-        out = torch.empty((2, n_positions), dtype=dtype, device=dev)
+        if out is None:
+            out = torch.empty((2, n_positions), dtype=dtype, device=dev)
         check(lib().tipk_typed_negative_sampling(ptr(pos_key_sorted), ptr(rel_ptr), n_rel, n_nodes, seed,
                                                  ptr(call_counter), adv, ptr(wg_ptr), ptr(wg_units),
                                                  0 if wg_ptr is None else wg_ptr.numel() - 1, ptr(pos_offset), ptr(keys32), ptr(out[0]), ptr(out[1]),
