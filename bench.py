@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json metric: D-D edges aggregated / s over encoder forward + backward.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload biosnap|biosnap963|synthetic|synthetic-small]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over the full graph: `z = FMEncoder.forward(...)` (P-P GCN x2,
 P->D mean, two R-GCN layers) followed by its backward with a fixed upstream gradient g ~ N(0,1)
@@ -19,7 +19,14 @@ bench.py ...` as a child, relays rank 0's JSON line and exits with the child's r
 `--oversubscribe` lets N ranks share fewer GPUs (gloo collectives; a functional check of the N-rank
 path on a 1-GPU box, not a measurement).
 
-Objects on the JSON line besides the contract's fields:
+A plain run does only what the headline needs: build the workload, the first step (`preprocess_s`), capture, the untimed
+settle replays, the W warm-up and K timed steps, --dump-outputs, the result line.  On that line besides the contract's
+fields: settle_replays, config, build_id, per_rank_ms_per_step (N > 1) and
+  preprocess_s  the first step on the real graph (all gather plans are built there).
+  dumped_outputs  with --dump-outputs DIR: what was written there (z.npy, grad.<parameter>.npy of the last timed step).
+
+--full adds everything else the benchmark measures or checks, each in runs of its own (--no-pmc, --no-cpu-baseline,
+--no-kernel-table and --no-extras drop single legs of it):
   roofline      the dominant kernel: algorithmic bytes per launch ((4 + 4 d) B per edge)
                 / its launch duration, measured live with HIP events on the launch stream around a
                 hipGraph of 20 back-to-back launches of that kernel on the step's own plans (an event
@@ -40,9 +47,10 @@ Objects on the JSON line besides the contract's fields:
                 config 5 on one GPU) and the whole graphed training epoch (tip.py:24-30), each timed by
                 this process after the headline measurement (fewer steps; --no-extras skips them).
   cpu_baseline  the oracle's CPU port on the host cores (rank 0, N = 1 only), bounded sample.
-  dumped_outputs  with --dump-outputs DIR: what was written there (z.npy, grad.<parameter>.npy of the last timed step).
-  preprocess_s / init_s  the first step on the real graph (all gather plans are built there) / before it, one step
-                on a 6 000-edge toy graph: what a fresh process spends loading torch's and libtipk's device code.
+  replay_events / multi_step_graph / kernels_eager_ms / step_floor / step_hbm / whole_step / replicated  per-replay HIP
+                events, k steps per graph, the eager per-kernel table and the figures derived from the kernel timings.
+  init_s        before the first step on the real graph, one step on a 6 000-edge toy graph: what a fresh process spends
+                loading torch's and libtipk's device code (a plain run skips it: its `preprocess_s` includes that cost).
 """
 import argparse
 import json
@@ -67,19 +75,22 @@ def parse():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--workload', default='biosnap', choices=['biosnap', 'biosnap963', 'synthetic', 'synthetic-small'])
     ap.add_argument('--mod', default='cat', choices=['cat', 'add'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, everything else the benchmark measures or checks: roofline and per-kernel '
+                         'figures, PMC passes, CPU baseline and parity, other configurations, training epoch, op-level C ABI')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and parity leg')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the CPU baseline leg')
     ap.add_argument('--launch', default=None, choices=['graph', 'eager'],
                     help='graph: the step is captured once into a hipGraph and replayed (default); '
                          'eager: one ctypes launch per kernel')
     ap.add_argument('--oversubscribe', action='store_true',
                     help='allow more ranks than GPUs (ranks share devices, gloo collectives): functional check only')
-    ap.add_argument('--no-kernel-table', action='store_true', help='skip the eager per-kernel event pass')
-    ap.add_argument('--no-extras', action='store_true', help='skip other_configs / train_step')
+    ap.add_argument('--no-kernel-table', action='store_true', help='--full without the eager per-kernel event pass')
+    ap.add_argument('--no-extras', action='store_true', help='--full without other_configs / train_step / op_level_c_abi')
     ap.add_argument('--settle', type=int, default=100,
                     help='untimed replays of the captured step BEFORE the W warm-up steps (a fresh process / a fresh box launches its '
                          'first graphs from cold host caches; reported as settle_replays)')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 --pmc child passes (HBM traffic of this run)')
+    ap.add_argument('--no-pmc', action='store_true', help='--full without the rocprofv3 --pmc child passes (HBM traffic of this run)')
     ap.add_argument('--step-only', action='store_true',
                     help='run nothing but the warm-up and timed steps (PMC passes: bytes / (steps + warmup) = bytes per step)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -424,7 +435,9 @@ def time_launch_us(fn, reps=20, replays=5):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
+        # thread_local: with a process group alive (a sharded run) the RCCL watchdog queries the events of finished eager
+        # collectives from its own thread; in the default global mode such a query during this capture aborts the process
+        with torch.cuda.graph(g, stream=side, capture_error_mode='thread_local'):
             for _ in range(reps):
                 fn()
         g.replay()                                         # warm
@@ -1035,8 +1048,9 @@ def main():
     if 'RANK' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))               # children first: this process never touches the GPU
 
+    full = args.full and not args.step_only        # the legs next to the headline (a plain run: setup, W + K steps, the line)
     global _LIVE_PMC
-    if (int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.step_only and not args.no_pmc and not os.environ.get('TIPK_BENCH_CHILD')
+    if (int(os.environ.get('WORLD_SIZE', '1')) == 1 and full and not args.no_pmc and not os.environ.get('TIPK_BENCH_CHILD')
             and not os.environ.get('TIPK_FORCE_SHARD') and args.workload.startswith('biosnap')):
         _LIVE_PMC = measure_pmc_in_run(args)       # child processes: before this one touches the GPU
     import torch
@@ -1127,9 +1141,9 @@ def main():
 
     # one-off initialisation that is not graph preprocessing (first use of torch's device kernels -- sort, bincount,
     # cumsum ... -- and of libtipk's code objects: ~0.4 s of lazy loading on a fresh process), timed on a toy graph and
-    # reported as `init_s`; `preprocess_s` is then the plan build of the REAL graph (the first step)
+    # reported as `init_s` (--full); `preprocess_s` is then the plan build of the REAL graph (the first step)
     init_s = None
-    if not sharded and not args.step_only:                     # (a --step-only child is a PMC pass: full-size steps only)
+    if not sharded and full:                                   # (a --step-only child is a PMC pass: full-size steps only)
         from tip_amd.data import synthetic_data_dict
         t0 = time.perf_counter()
         toy = synthetic_data_dict(n_drug=96, n_rel=6, n_edges=6000, seed=1, with_protein_graph=True, n_prot=128, pp_edges=2048, dp_edges=256)
@@ -1154,10 +1168,10 @@ def main():
             dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         if float(ok.item()) <= 0:
             run, launch = b.step, 'eager'
-    # the large D-D launches alone (roofline objects: HIP events around graphs of 20 back-to-back launches).  They run BEFORE
-    # the headline region: a fresh process times its first milliseconds of GPU work at ramping clocks (20 steps = 7 ms;
+    # --full: the large D-D launches alone (roofline objects: HIP events around graphs of 20 back-to-back launches).  They run
+    # BEFORE the headline region: a fresh process times its first milliseconds of GPU work at ramping clocks (20 steps = 7 ms;
     # measured 0.377 ms/step with the order reversed against 0.36 here and for --steps 100 either way)
-    launches = [] if args.step_only else dd_launches(enc, dev)
+    launches = dd_launches(enc, dev) if full else []
     launch_us = {l['label']: time_launch_us(l['fn']) for l in launches if l['work'] is not None}
     settle = 0
     if launch == 'graph' and args.settle > 0 and world == 1:   # (untimed; the contract's W warm-up steps and K timed steps follow.
@@ -1179,10 +1193,10 @@ def main():
             z_last, grads_last = b.z, {k: prm.grad for k, prm in enc.named_parameters()}
         dumped = dump_outputs(args.dump_outputs, z_last, grads_last)
     replay_stats = None
-    if world == 1 and not args.step_only:
+    if world == 1 and full:
         replay_stats = replay_event_stats(run, max(100, args.steps), fence)
     multi = None
-    if launch == 'graph' and world == 1 and not args.step_only and not sharded:
+    if launch == 'graph' and world == 1 and full and not sharded:
         try:                                                   # (after the headline region; its own graph)
             k_multi = 4
             gm = b.capture_many(k_multi)
@@ -1197,7 +1211,7 @@ def main():
 
     # an eager per-kernel table of the whole step
     kern = {}
-    if not args.no_kernel_table and not args.step_only:
+    if not args.no_kernel_table and full:
         ops.timing_start()
         for _ in range(max(3, min(args.steps, 10))):
             b.step()
@@ -1212,7 +1226,7 @@ def main():
         elapsed = max(float(t.item()) for t in every)
         if shard is not None and shard.direct is not None:
             shard.direct.check()                                           # a wait that ran out -> PeerTimeout: non-zero exit
-    if sharded and args.workload.startswith('biosnap'):
+    if sharded and args.workload.startswith('biosnap') and full:
         replicated = b.replicated_stage_us()                               # what every rank computes redundantly
 
     rc = 0
@@ -1265,7 +1279,7 @@ def main():
                 out['roofline_aggregation'] = roofline_of(by[dom_a], aggs[dom_a], bid)
             out['dd_launches_us'] = {k: round(v, 2) for k, v in launch_us.items()}
         per_edge = sum(2 * (8 + 4 * dims[k]) for k in ('n_hid1', 'n_hid2'))     # 416 / 2080 B per edge
-        if args.workload.startswith('synthetic'):
+        if full and args.workload.startswith('synthetic'):
             # the HBM yardstick of SURVEY 8(d) against the roofline of ALL the GPUs of the job (N x 8 TB/s)
             out['whole_step'] = {'alg_bytes': E * per_edge, 'bytes_per_edge': per_edge, 'GBps': E * per_edge / (ms * 1e-3) / 1e9,
                                  'n_gpus': world, 'peak_GBps': world * HBM_PEAK_GBS,
@@ -1315,7 +1329,7 @@ def main():
                         'kernel-only times: profiles/*_kernel_by_grid.csv',
                 'table': {k: {'launches': v[0], 'mean_ms': round(v[1], 5)}
                           for k, v in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])}}
-        if world == 1 and not args.no_cpu_baseline and not args.step_only:
+        if world == 1 and full and not args.no_cpu_baseline:
             if launch == 'graph':
                 b.graph.replay()                                   # the timed object itself: one more replay of the captured step
                 torch.cuda.synchronize()
@@ -1325,7 +1339,7 @@ def main():
             out['parity_in_bench']['what'] = 'outputs of %s' % ('a replay of the timed hipGraph' if launch == 'graph' else 'an eager step')
             if not out['parity_in_bench']['ok']:
                 rc = 1
-        extras = (world == 1 and not args.no_extras and not args.step_only and not args.no_cpu_baseline
+        extras = (world == 1 and full and not args.no_extras and not args.no_cpu_baseline
                   and args.workload == 'biosnap' and args.mod == 'cat')
         if extras:
             del launches, run

@@ -239,7 +239,7 @@ def test_bench_two_ranks_direct_exchange_and_timed_routes():
 
 @pytest.mark.timeout(1500)
 def test_bench_four_ranks_oversubscribed_auto_collective():
-    """`bench.py --gpus 4 --oversubscribe` on BioSNAP (the ranks share the one GPU, gloo; at most 6 processes may hold it:
+    """`bench.py --gpus 4 --oversubscribe --full` on BioSNAP (the ranks share the one GPU, gloo; at most 6 processes may hold it:
     this one, bench.py's launcher and 4 ranks): the exchange is set up behind its self-test, both collectives are timed per
     message size and the faster kept, and the line carries what the first real 8-GPU run will be read by: per-rank step
     times, the collective's timings, the replicated stage and the Amdahl ceiling it implies."""
@@ -247,7 +247,8 @@ def test_bench_four_ranks_oversubscribed_auto_collective():
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     env.pop('TIPK_COLLECTIVE', None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--oversubscribe', '--steps', '3',
-                          '--warmup', '1', '--no-cpu-baseline', '--no-kernel-table'], env=env, capture_output=True, text=True, timeout=1400)
+                          '--warmup', '1', '--full', '--no-cpu-baseline', '--no-kernel-table'], env=env, capture_output=True, text=True,
+                         timeout=1400)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
     assert rec['n_gpus'] == 4 and rec['value'] > 0 and 'relation-sharded x4' in rec['config']['parallelism']
@@ -263,7 +264,7 @@ def test_bench_four_ranks_oversubscribed_auto_collective():
 
 @pytest.mark.timeout(900)
 def test_bench_one_rank_rccl_in_the_captured_step():
-    """RCCL under the driver: `TIPK_FORCE_SHARD=1 python bench.py --gpus 1` runs the relation-SHARDED
+    """RCCL under the driver: `TIPK_FORCE_SHARD=1 python bench.py --gpus 1 --full` runs the relation-SHARDED
     step on one rank -- `init_process_group('nccl', device_id=...)`, every all-reduce of the step issued through RCCL and
     captured into the step's hipGraph (no silent eager fallback), fd 1 kept clean of RCCL's banner -- and the replayed
     graph's outputs equal the oracle's (`parity_in_bench`)."""
@@ -272,7 +273,7 @@ def test_bench_one_rank_rccl_in_the_captured_step():
     env['TIPK_FORCE_SHARD'] = '1'
     env.pop('TIPK_COLLECTIVE', None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2',
-                          '--no-extras', '--no-pmc', '--cpu-seconds', '2'], env=env, capture_output=True, text=True, timeout=850)
+                          '--full', '--no-extras', '--no-pmc', '--cpu-seconds', '2'], env=env, capture_output=True, text=True, timeout=850)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith('{'), out.stdout[-2000:]         # ONE JSON line, no banner on stdout

@@ -4,7 +4,7 @@
 TAG=${1:-q}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python3 bench.py --steps 100 --warmup 20 --no-extras --no-pmc --no-cpu-baseline > $OUT/b100.json 2> $OUT/b100.err
+python3 bench.py --steps 100 --warmup 20 --full --no-extras --no-pmc --no-cpu-baseline > $OUT/b100.json 2> $OUT/b100.err
 if [ "${2:-}" = "trace" ]; then
   cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_trace.json 2> $OUT/bench_trace.err

@@ -49,7 +49,7 @@ stats = find('trace/**/*kernel_stats.csv')
 if stats:
     rows = list(csv.DictReader(open(stats)))
     with open('profiles/%s_kernel_stats.csv' % tag, 'w') as f:
-        f.write('# rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline`\n')
+        f.write('# rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline`\n')
         f.write('kernel,calls,total_ns,avg_ns,pct,min_ns,max_ns\n')
         for r in rows[:45]:
             f.write('"%s",%s,%s,%.0f,%s,%s,%s\n' % (short(r['Name']), r['Calls'], r['TotalDurationNs'],
