@@ -884,6 +884,10 @@ int tipk_adam_step(int n_tensors, float* const* params, const float* const* grad
  *     layer left in it (pair cells and XB: the caller ran nothing else on that workspace in between) -- the backward pass then
  *     skips recomputing them; tipk_rgcn_bwd = flags 0 (always safe).  On a prepared route the handle's gradient table is
  *     scratch of the backward call: one backward pass per handle at a time (calls on one stream are ordered anyway).
+ *     The rule of every entry in this section: TIPK_OK implies correct numbers, for every stride the call accepts; otherwise a
+ *     non-OK status (shape and argument checks fail before anything is written).  tipk_rgcn_fwd takes the same route for every ld_out (a padded `out` of the pair
+ *     form is written densely into the workspace and copied with its stride), so a FROM_FWD backward pass always finds the
+ *     cells and XB of its own route.
  */
 #define TIPK_RGCN_WORKSPACE_FROM_FWD 1
 typedef struct tipk_graph tipk_graph;

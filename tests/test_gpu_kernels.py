@@ -534,6 +534,253 @@ def test_row_products_s_both_passes(ops, R, N, ch, nb, E):
     close(t, wt, rtol=2e-5, atol=2e-5 * float(wt.abs().max()))
 
 
+# ------------------------------------------------------------------ row / dest products at their boundaries
+# The large-graph routes of an R-GCN layer (`_row_plan` / `rgcn_graph`): the kernels above at the edges of their plans --
+# node counts around the workgroup's 8 nodes, relation counts around the 32-relation tile, (node, tile) lists around the
+# 16-entry batch, non-finite data, and the packing limits of the entry words.  Every case is the fp64 definition on the edge
+# list; exact where the inputs are small integers.
+def _bits_equal(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _rows_ref(key, other, rel, table, att, xb=None, nodes=None):
+    """fp64 definition from the edge list: T[b, v, :] = sum_{e: key_e = v} att[rel_e, b] table[other_e, :] for v in `nodes`
+    (all when None; T is [nb, len(nodes), ch]) and d att[r, b] = sum_{e: rel_e = r} <table[other_e, :], xb[b, key_e, :]>.
+    table / xb may live on the GPU: only the gathered rows are moved."""
+    key, other, rel = (t.cpu().long() for t in (key, other, rel))
+    n, ch = table.shape
+    a = att.double().cpu()
+    nodes = torch.arange(n) if nodes is None else torch.as_tensor(nodes, dtype=torch.long)
+    pos = torch.full((n,), -1, dtype=torch.long)
+    pos[nodes] = torch.arange(len(nodes))
+    sel = pos[key] >= 0
+    rows = table[other[sel].to(table.device)].double().cpu()
+    t = torch.zeros(len(nodes), a.shape[1], ch, dtype=torch.float64)
+    t.index_add_(0, pos[key[sel]], a[rel[sel]].unsqueeze(2) * rows.unsqueeze(1))
+    t = t.permute(1, 0, 2)
+    if xb is None:
+        return t, None
+    tr = table[other.to(table.device)].double().cpu()
+    xk = xb[:, key.to(xb.device)].double().cpu()
+    datt = torch.zeros(a.shape, dtype=torch.float64).index_add_(0, rel, torch.einsum('ec,bec->eb', tr, xk))
+    return t, datt
+
+
+def _rows_plan(form, key, other, rel, n, r):
+    from tip_amd.plan import build_row_stream_plan, build_row_stream_plan_s
+    return (build_row_stream_plan_s if form == 's' else build_row_stream_plan)(key, other, rel, n, r).to(DEV)
+
+
+def _rows_run(ops, plan, table, att, xb=None):
+    """T (forward form) and, with xb [nb, N, ch], d att (transposed form) -- whose T must be the same bits."""
+    n, ch = table.shape
+    t = ops.row_products(plan, table, att)
+    if xb is None:
+        return t, None
+    job, t2 = ops.row_products(plan, table, att, xb.reshape(att.shape[1], n * ch))
+    ops.gemm_group([], [job])
+    assert _bits_equal(t, t2)
+    return t, job.out
+
+
+def _close_nonfinite(got, want, rtol=2e-5, atol=2e-5):
+    """isfinite(got) == isfinite(want) element for element; the finite elements within tolerance."""
+    got = got.detach().to('cpu', torch.float64)
+    fg, fw = torch.isfinite(got), torch.isfinite(want)
+    assert torch.equal(fg, fw), 'non-finite pattern differs at %d of %d elements (%d non-finite in the reference)' % (
+        int((fg != fw).sum()), fg.numel(), int((~fw).sum()))
+    w = want[fw]
+    torch.testing.assert_close(got[fw], w, rtol=rtol, atol=atol * max(1.0, float(w.abs().max())) if w.numel() else atol)
+
+
+_ROW_FORMS = [('v', 32), ('v', 96), ('s', 64)]
+
+
+@pytest.mark.parametrize('form,ch', _ROW_FORMS)
+@pytest.mark.parametrize('R,N', [(1, 1), (31, 7), (32, 8), (33, 9), (65, 17)])
+def test_row_products_tile_and_group_edges(ops, form, ch, R, N):
+    """Relation counts around the 32-relation tile, node counts around the workgroup's 8 nodes; relations 0 and R - 1 without
+    edges (R >= 3: a whole last tile empty at R = 33, 65), a tile with all 32 rows used, a node whose only row is row 31, a
+    node whose rows all sit in one tile, a row of 5 000 entries; table row 0 is NaN and no edge gathers it.  Exact."""
+    g = torch.Generator().manual_seed(R * 100 + N + ch)
+    used = list(range(1, R - 1)) if R >= 3 else list(range(R))
+    lo = 1 if N > 1 else 0                                          # no edge gathers node 0 (its table row is NaN)
+    keys, others, rels = [], [], []
+
+    def add(k, r, m):
+        keys.append(torch.full((m,), k)); rels.append(torch.as_tensor(r).expand(m).clone())
+        others.append(torch.randint(lo, N, (m,), generator=g))
+    add(N - 1, used[len(used) // 2], 5000)                          # one row of 5 000 entries
+    if R >= 64:
+        add(0, torch.arange(32, 64), 32)                            # tile 1: all 32 rows
+        add(min(1, N - 1), 31, 3)                                   # only row 31 of tile 0
+        add(min(2, N - 1), torch.tensor([33, 40, 40, 62]), 4)       # rows in tile 1 only
+    else:
+        add(0, torch.tensor(used), len(used))
+    e = 40 * N
+    own = 3 if R >= 64 else 1                                       # nodes 0 .. own - 1 hold only the rows built above
+    keys.append(torch.randint(own if N > own else 0, N, (e,), generator=g))
+    rels.append(torch.as_tensor(used)[torch.randint(0, len(used), (e,), generator=g)])
+    others.append(torch.randint(lo, N, (e,), generator=g))
+    key, rel, other = torch.cat(keys), torch.cat(rels).long(), torch.cat(others)
+    self_loops = torch.arange(own if N > own else 0, N, 3)
+    key, other = torch.cat([key, self_loops]), torch.cat([other, self_loops.clamp(min=lo)])
+    rel = torch.cat([rel, torch.full((self_loops.numel(),), used[0])])
+    assert (ops.row_products_s_supported if form == 's' else ops.row_products_supported)(N, R, 8, ch)
+    plan = _rows_plan(form, key.to(DEV), other.to(DEV), rel.to(DEV), N, R)
+    table = torch.randint(-3, 4, (N, ch), generator=g).float()
+    if N > 1:
+        table[0] = float('nan')
+    att, xb = torch.randint(-3, 4, (R, 8), generator=g).float(), torch.randint(-2, 3, (8, N, ch), generator=g).float()
+    t, datt = _rows_run(ops, plan, table.to(DEV), att.to(DEV), xb.to(DEV))
+    wt, wa = _rows_ref(key, other, rel, table, att, xb)
+    assert bool(torch.isfinite(wt).all()) and bool(torch.isfinite(wa).all())
+    assert torch.equal(t.cpu().double(), wt) and torch.equal(datt.cpu().double(), wa)
+    if R >= 3:
+        assert bool((datt[0] == 0).all()) and bool((datt[R - 1] == 0).all())
+    t2, datt2 = _rows_run(ops, plan, table.to(DEV), att.to(DEV), xb.to(DEV))
+    assert _bits_equal(t, t2) and _bits_equal(datt, datt2)
+
+
+@pytest.mark.parametrize('form,ch', _ROW_FORMS)
+def test_row_products_list_lengths_and_empty(ops, form, ch):
+    """(node, tile) lists of exactly 15, 16, 17, 31, 32 and 33 entries, on one row (the per-lane form: one half holds them
+    all) and on two rows of either parity (each half holds one); E = 0 gives zeros.  Exact."""
+    R, N = 40, 40
+    g = torch.Generator().manual_seed(ch)
+    keys, rels = [], []
+    for i, L in enumerate((15, 16, 17, 31, 32, 33)):
+        keys.append(torch.full((L,), 2 * i)); rels.append(torch.full((L,), 5 + i))
+        keys.append(torch.full((2 * L,), 2 * i + 1)); rels.append(torch.cat([torch.full((L,), 6 + i), torch.full((L,), 7 + i)]))
+        keys.append(torch.full((L,), 20 + i)); rels.append(torch.full((L,), 32 + i % 8))    # tile 1 alone
+    key, rel = torch.cat(keys), torch.cat(rels)
+    other = torch.randint(1, N, (key.numel(),), generator=g)
+    table = torch.randint(-3, 4, (N, ch), generator=g).float()
+    table[0] = float('nan')
+    att, xb = torch.randint(-3, 4, (R, 8), generator=g).float(), torch.randint(-2, 3, (8, N, ch), generator=g).float()
+    plan = _rows_plan(form, key.to(DEV), other.to(DEV), rel.to(DEV), N, R)
+    t, datt = _rows_run(ops, plan, table.to(DEV), att.to(DEV), xb.to(DEV))
+    wt, wa = _rows_ref(key, other, rel, table, att, xb)
+    assert torch.equal(t.cpu().double(), wt) and torch.equal(datt.cpu().double(), wa)
+    empty = torch.zeros(0, dtype=torch.long)
+    plan0 = _rows_plan(form, empty.to(DEV), empty.to(DEV), empty.to(DEV), N, R)
+    t, datt = _rows_run(ops, plan0, table.to(DEV), att.to(DEV), xb.to(DEV))
+    assert bool((t == 0).all()) and bool((datt == 0).all())
+
+
+@pytest.mark.parametrize('sign', [1.0, -1.0])
+@pytest.mark.parametrize('form,ch', _ROW_FORMS + [('dest', 48)])
+def test_row_and_dest_products_nonfinite_rows(ops, form, ch, sign):
+    """One table row is +-Inf (one sign: no Inf - Inf inside a row sum): exactly the outputs whose fp64 value is non-finite
+    are non-finite, and the rest match.  A running row sum that resets as `acc * 0 + piece` turns the next row of the same
+    node into NaN (0 * Inf); its d att is finite in fp64."""
+    from tip_amd.plan import build_dest_plan
+    R, N, E = 70, 50, 4000
+    g = torch.Generator().manual_seed(int(ch + sign))
+    rel = torch.randint(0, R, (E,), generator=g)
+    key = torch.randint(0, N, (E,), generator=g)
+    other = torch.randint(0, N, (E,), generator=g)
+    bad = 7
+    other[other == bad] = bad + 1
+    # the Inf row is gathered into rows (10, 3), (10, 3) again and (40, 3) only: node 3's later rows, (11 .. 69, 3), stay finite
+    key, other, rel = torch.cat([key, torch.tensor([3, 3, 3])]), torch.cat([other, torch.full((3,), bad)]), torch.cat([rel, torch.tensor([10, 10, 40])])
+    table = torch.randn(N, ch, generator=g)
+    table[bad] = sign * float('inf')
+    att = torch.randn(R, 8, generator=g)
+    xb = torch.randn(8, N, ch, generator=g)
+    if form == 'dest':
+        bits = ops.dest_products_bits(N, R, 8, ch)
+        dp = build_dest_plan(other.to(DEV), key.to(DEV), rel.to(DEV), N, R, bits).to(DEV)
+        t = ops.dest_products(dp, table.to(DEV), att.to(DEV))
+        assert _bits_equal(t, ops.dest_products(dp, table.to(DEV), att.to(DEV)))
+        wt, _ = _rows_ref(key, other, rel, table, att)
+        _close_nonfinite(t, wt)
+        return
+    plan = _rows_plan(form, key.to(DEV), other.to(DEV), rel.to(DEV), N, R)
+    t, datt = _rows_run(ops, plan, table.to(DEV), att.to(DEV), xb.to(DEV))
+    wt, wa = _rows_ref(key, other, rel, table, att, xb)
+    assert int((~torch.isfinite(wa)).any(1).sum()) == 2                # d att of relations 10 and 40 only
+    _close_nonfinite(t, wt)
+    _close_nonfinite(datt, wa)
+
+
+@pytest.mark.timeout(300)
+def test_row_products_per_lane_at_65536_nodes(ops):
+    """The per-lane form packs `other` into 16 bits: N = 65 536 with key and other = 65 535 (and 0) is taken and exact;
+    N = 65 537 is refused (the layer falls through to the CSR / dest routes)."""
+    N, R, ch, nb = 65536, 40, 32, 8
+    assert ops.row_products_supported(N, R, nb, ch) and not ops.row_products_supported(N + 1, R, nb, ch)
+    g = torch.Generator().manual_seed(65536)
+    E = 40000
+    key, other, rel = torch.randint(0, N, (E,), generator=g), torch.randint(0, N, (E,), generator=g), torch.randint(0, R, (E,), generator=g)
+    edge = torch.tensor([[N - 1, N - 1, R - 1], [N - 1, 0, 0], [0, N - 1, 31], [N - 1, N - 1, 32], [N - 2, N - 1, R - 1]])
+    key, other, rel = torch.cat([key, edge[:, 0]]), torch.cat([other, edge[:, 1]]), torch.cat([rel, edge[:, 2]])
+    plan = _rows_plan('v', key.to(DEV), other.to(DEV), rel.to(DEV), N, R)
+    table = torch.randint(-3, 4, (N, ch), generator=g).float().to(DEV)
+    att = torch.randint(-3, 4, (R, nb), generator=g).float().to(DEV)
+    xb = torch.randint(-2, 3, (nb, N, ch), generator=g).float().to(DEV)
+    t, datt = _rows_run(ops, plan, table, att, xb)
+    nodes = sorted(set([0, 1, N - 2, N - 1] + torch.randint(0, N, (60,), generator=g).tolist()))
+    wt, wa = _rows_ref(key, other, rel, table, att, xb, nodes)
+    assert torch.equal(t[:, nodes].cpu().double(), wt) and torch.equal(datt.cpu().double(), wa)
+
+
+@pytest.mark.timeout(300)
+def test_row_products_s_two_gigabyte_table(ops):
+    """`row_products_s` reads the table through a buffer resource of n_nodes * row bytes (a load past it returns 0, no
+    error): at the largest N with N * 64 * 4 < 2^31 the last table rows are gathered and summed, not read as zeros."""
+    ch, R, nb = 64, 3, 1
+    N = (2 ** 31) // (ch * 4) - 1
+    assert ops.row_products_s_supported(N, R, nb, ch) and N * ch * 4 < 2 ** 31
+    g = torch.Generator().manual_seed(31)
+    last = torch.arange(N - 40, N)
+    key = torch.cat([last, torch.tensor([0, 1, 2, N - 1, N - 1]), torch.randint(0, N, (2000,), generator=g)])
+    other = torch.cat([last.flip(0), torch.tensor([N - 1, N - 2, N - 1, N - 1, 3]), torch.randint(0, N, (2000,), generator=g)])
+    rel = torch.randint(0, R, (key.numel(),), generator=g)
+    plan = _rows_plan('s', key.to(DEV), other.to(DEV), rel.to(DEV), N, R)
+    table = torch.empty(N, ch, device=DEV)
+    table.copy_(torch.arange(N, device=DEV, dtype=torch.float32).remainder_(97).sub_(48).unsqueeze(1))
+    table[:, 1::2] += 0.5
+    att = torch.randint(-3, 4, (R, nb), generator=g).float().to(DEV)
+    xb = torch.empty(nb, N, ch, device=DEV).fill_(1.0)
+    xb[:, -64:] = torch.randint(-2, 3, (nb, 64, ch), generator=g).float().to(DEV)
+    t, datt = _rows_run(ops, plan, table, att, xb)
+    del plan
+    nodes = sorted(set(last.tolist() + [0, 1, 2, 3, 7] + torch.randint(0, N, (32,), generator=g).tolist()))
+    wt, wa = _rows_ref(key, other, rel, table, att, xb, nodes)
+    assert bool(wt[:, -1].abs().max() > 0)
+    assert torch.equal(t[:, nodes].cpu().double(), wt) and torch.equal(datt.cpu().double(), wa)
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('R', [256, 257])
+def test_dest_products_words_with_bit_31(ops, R):
+    """`dest_products` edge words are rel | src << bits wrapped to int32 and decoded unsigned: N just above 2^(31 - bits)
+    with sources past that bound (bit 31 set), relation R - 1 and relation 0, R = 256 / 257 (8 / 9 bits)."""
+    from tip_amd.plan import build_dest_plan
+    d_in, nb = 32, 2
+    bits = 8 if R == 256 else 9
+    N = (1 << (31 - bits)) + 5
+    assert ops.dest_products_bits(N, R, nb, d_in) == bits
+    g = torch.Generator().manual_seed(R)
+    hi = torch.arange(N - 8, N)
+    src = torch.cat([hi, hi, torch.tensor([0, N - 1, 1 << (31 - bits)]), torch.randint(0, N, (3000,), generator=g)])
+    dst = torch.cat([hi.flip(0), torch.full((8,), 5), torch.tensor([N - 1, 0, N - 1]), torch.randint(0, N, (3000,), generator=g)])
+    rel = torch.cat([torch.full((8,), R - 1), torch.zeros(8, dtype=torch.long), torch.tensor([R - 1, R - 1, 0]),
+                     torch.randint(0, R, (3000,), generator=g)])
+    order = torch.sort(rel, stable=True).indices
+    src, dst, rel = src[order], dst[order], rel[order]
+    dp = build_dest_plan(src.to(DEV), dst.to(DEV), rel.to(DEV), N, R, bits).to(DEV)
+    assert bool((dp.edges < 0).any())                               # words with bit 31 set
+    x = torch.arange(N, device=DEV, dtype=torch.float32).remainder_(89).sub_(44).unsqueeze(1).repeat(1, d_in)
+    x[:, ::3] += 0.25
+    att = torch.randint(-3, 4, (R, nb), generator=g).float().to(DEV)
+    t = ops.dest_products(dp, x, att)
+    nodes = sorted(set(hi.tolist() + [0, 1, 5] + torch.randint(0, N, (32,), generator=g).tolist()))
+    wt, _ = _rows_ref(dst, src, rel, x, att, None, nodes)
+    assert torch.equal(t[:, nodes].cpu().double(), wt)
+
+
 @pytest.mark.parametrize('R,N,d', [(70, 645, 32), (33, 100, 16), (1097, 37, 8)])
 def test_unwritten_rows_masked_end_to_end(ops, R, N, d):
     """Rows (relation, node) without edges: the wave-stream gather with write_zeros=False leaves them untouched

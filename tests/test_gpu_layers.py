@@ -179,6 +179,70 @@ def test_graph_handle_pair_form_is_the_modules_pair_form_bit_for_bit(name):
         assert L.tipk_graph_destroy(h) == 0
 
 
+@pytest.mark.parametrize('relu', [0, 1])
+@pytest.mark.parametrize('flags', [0, 1])
+@pytest.mark.parametrize('prepared', [False, True])
+def test_graph_handle_padded_strides_vs_fp64(prepared, flags, relu):
+    """tipk_rgcn_fwd / tipk_rgcn_bwd_ex with every leading dimension larger than its width (ld_x, ld_out, ld_g, ld_gx, ld_relu),
+    on the generic route (handle not prepared) and the pair form (prepared), with and without TIPK_RGCN_WORKSPACE_FROM_FWD,
+    against fp64 (include/tipk.h section 10: TIPK_OK implies correct numbers).  A forward pass with ld_out != d_out once took
+    the generic route while a FROM_FWD backward pass took the pair form and read cells / XB that were never written."""
+    import ctypes as C
+    from tip_amd import _lib
+    L = _lib.lib()
+    g = load_golden('rgcn_fast_sym')
+    r, nb, d_in, d_out = g['l1.att'].shape[0], 32, 64, 32
+    ei, rg = g['dd_idx'].to(DEV), g['dd_range'].to(DEV)
+    n = g['x'].shape[0]
+    gen = torch.Generator().manual_seed(3)
+    basis, att, root = (g['l1.' + k].to(DEV).contiguous() for k in ('basis', 'att', 'root'))
+    ld_x, ld_out, ld_g, ld_gx, ld_relu = d_in + 8, d_out + 12, d_out + 4, d_in + 20, d_out + 8
+    sentinel = 7.25
+
+    def padded(rows, cols, ld, data=None):
+        buf = torch.full((rows, ld), sentinel, device=DEV)
+        if data is not None:
+            buf[:, :cols] = data
+        return buf
+    x_c = g['x'].float()
+    up_c = torch.randn(n, d_out, generator=gen)
+    xp, upp = padded(n, d_in, ld_x, x_c.to(DEV)), padded(n, d_out, ld_g, up_c.to(DEV))
+    h = C.c_void_p()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    assert L.tipk_graph_build(ptr(ei), None, ptr(rg), 8, ei.shape[1], n, r, None, C.byref(h)) == 0
+    try:
+        if prepared:
+            assert L.tipk_graph_prepare_rgcn(h, nb, d_out) == 0 and L.tipk_graph_rgcn_route(h, nb, d_out) == 2
+        else:
+            assert L.tipk_graph_rgcn_route(h, nb, d_out) == 0
+        ws = torch.full((L.tipk_rgcn_workspace_bytes(h, d_in, d_out, nb),), 255, dtype=torch.uint8, device=DEV)   # NaN patterns
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        outp = padded(n, d_out, ld_out)
+        assert L.tipk_rgcn_fwd(h, ptr(xp), ld_x, d_in, ptr(basis), ptr(att), ptr(root), nb, d_out, relu, ptr(outp), ld_out,
+                               ptr(ws), ws.numel(), st) == 0
+        relu_in = None
+        if relu:
+            relu_in = padded(n, d_out, ld_relu, outp[:, :d_out])
+        gxp = padded(n, d_in, ld_gx)
+        gb, ga, gr = torch.empty_like(basis), torch.empty_like(att), torch.empty_like(root)
+        assert L.tipk_rgcn_bwd_ex(h, ptr(xp), ld_x, d_in, ptr(basis), ptr(att), ptr(root), nb, d_out, ptr(upp), ld_g, ptr(relu_in),
+                                  ld_relu if relu else 0, ptr(gxp), ld_gx, ptr(gb), ptr(ga), ptr(gr), ptr(ws), ws.numel(), flags, st) == 0
+        torch.cuda.synchronize()
+        b64, a64, r64 = (t.double().cpu() for t in (basis, att, root))
+        want, saved = O.rgcn_fwd(x_c.double(), g['dd_idx'], g['dd_range'], b64, a64, r64)
+        g_out = up_c.double()
+        if relu:
+            g_out = torch.where(want > 0, g_out, torch.zeros_like(g_out))
+            want = torch.relu(want)
+        wx, wb, wa, wr = O.rgcn_bwd(g_out, x_c.double(), g['dd_idx'], b64, a64, r64, saved)
+        close(outp[:, :d_out], want, rtol=1e-5, atol=1e-5 * float(want.abs().max()))
+        assert bool((outp[:, d_out:] == sentinel).all()) and bool((gxp[:, d_in:] == sentinel).all())
+        for got, w in ((gxp[:, :d_in], wx), (gb, wb), (ga, wa), (gr, wr)):
+            close(got, w, rtol=1e-4, atol=2e-5 * float(w.abs().max()))
+    finally:
+        assert L.tipk_graph_destroy(h) == 0
+
+
 @pytest.mark.parametrize('name', ['encoder_fast_cat_sym', 'encoder_fast_add_sym', 'encoder_fast_cat_directed'])
 def test_fm_encoder_fast_route_against_reference_golden(name):
     """FMEncoder at the dims of tip.py:14 / :17 against the reference's own forward + autograd on the nasty 61-drug graph: the

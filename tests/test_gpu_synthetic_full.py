@@ -41,6 +41,45 @@ def _brute_rows(rows, x, ei, et, m):
     return out
 
 
+def _check_layer_grads(m, x, upstream, g_x, ei, et, deg, rgc):
+    """One layer's gradients from ITS upstream, fp64 on the GPU (plain torch): g' = upstream / deg(dst);
+    dXB[b, v] = sum_{e: src_e = v} att[r_e, b] g'[dst_e];  dX[v] = upstream[v] root^T + sum_b basis_b dXB[b, v];
+    d basis[b] = X^T dXB[b];  d att[r, b] = sum_{e in r} <X[src_e] basis_b, g'[dst_e]>."""
+    n = x.shape[0]
+    basis, att, root = (t.detach().double() for t in (m.basis, m.att, m.root))
+    gp = upstream / deg[:, None]
+    src, dst = ei[0], ei[1]
+    rows = torch.tensor(sorted(np.random.RandomState(1).choice(n, 6, replace=False).tolist()) + [0, n - 1], device=x.device)
+    bases = torch.tensor([0, 5, 17, 31], device=x.device)
+    in_rows = torch.tensor([0, 3, 64, 127], device=x.device)
+    # dXB restricted to the 8 rows (all bases) and to the 4 bases (all rows): chunks of edges, index_add in fp64
+    pos = torch.full((n,), -1, dtype=torch.long, device=x.device)
+    pos[rows] = torch.arange(rows.numel(), device=x.device)
+    dxb_rows = torch.zeros(rows.numel(), basis.shape[0], gp.shape[1], dtype=torch.float64, device=x.device)
+    dxb_b = torch.zeros(bases.numel(), n, gp.shape[1], dtype=torch.float64, device=x.device)
+    step = 1 << 21
+    for a in range(0, src.numel(), step):
+        s_, d_, r_ = src[a:a + step], dst[a:a + step], et[a:a + step]
+        g_e = gp[d_]
+        for i in range(bases.numel()):
+            dxb_b[i].index_add_(0, s_, att[r_, bases[i]].unsqueeze(1) * g_e)
+        sel = pos[s_] >= 0
+        dxb_rows.index_add_(0, pos[s_[sel]], att[r_[sel]].unsqueeze(2) * g_e[sel].unsqueeze(1))
+    want_x = upstream[rows] @ root.t() + torch.einsum('vbo,bio->vi', dxb_rows, basis)
+    got_x = g_x[rows].double()
+    torch.testing.assert_close(got_x, want_x, rtol=1e-4, atol=2e-5 * float(want_x.abs().max()))
+    want_b = torch.einsum('vi,bvo->bio', x[:, in_rows], dxb_b)
+    got_b = m.basis.grad[bases][:, in_rows].double()
+    torch.testing.assert_close(got_b, want_b, rtol=1e-4, atol=2e-5 * float(want_b.abs().max()))
+    # d att: relations across the range, the last tile (1984 .. 1999) included
+    for r in (0, 7, 640, 1234, 1984, 1990, 1998, 1999):
+        a, b = int(rgc[r, 0]), int(rgc[r, 1])
+        s_, d_ = src[a:b], dst[a:b]
+        want = torch.einsum('ei,bio,eo->b', x[s_], basis, gp[d_])
+        got = m.att.grad[r].double()
+        torch.testing.assert_close(got, want, rtol=1e-4, atol=2e-5 * float(want.abs().max()))
+
+
 @pytest.mark.timeout(1500)
 def test_config5_full_size_two_layers_rows_and_properties(synth):
     dd = synth
@@ -52,7 +91,9 @@ def test_config5_full_size_two_layers_rows_and_properties(synth):
     x0_c = torch.randn(N, 128, generator=g)
     x0 = x0_c.to(DEV).requires_grad_(True)
     h1 = m1(x0, ei, et, rg)
+    h1.retain_grad()
     x1 = torch.relu(h1)
+    x1.retain_grad()
     out = m2(x1, ei, et, rg)
     up_c = torch.randn(N, 128, generator=g)
     (out * up_c.to(DEV)).sum().backward()
@@ -84,6 +125,13 @@ def test_config5_full_size_two_layers_rows_and_properties(synth):
         torch.testing.assert_close(got, want, rtol=1e-4, atol=2e-5 * float(want.abs().max()))
     want_root = x1_c.t() @ up_c.double()
     torch.testing.assert_close(m2.root.grad.double().cpu(), want_root, rtol=1e-4, atol=2e-5 * float(want_root.abs().max()))
+
+    # dX, d basis and d att of EACH layer against that layer's own upstream (layer 2: up; layer 1: the gradient that reached
+    # h1), so that an error in one layer does not feed the other's check; fp64 torch on the GPU, from the edge list
+    ei64, et64 = ei.long(), et.long()
+    deg_d = torch.bincount(ei64[1], minlength=N).clamp(min=1).double()
+    for m, x_in, upstream, gx in ((m2, x1.detach(), up_c.to(DEV), x1.grad), (m1, x0_c.to(DEV), h1.grad, x0.grad)):
+        _check_layer_grads(m, x_in.double(), upstream.double(), gx, ei64, et64, deg_d, dd['dd_train_range'])
 
     # (i) linearity of a layer and the adjoint identity <J x', y> = <x', J^T y> at full size
     xa, xb_ = torch.randn(N, 128, device=DEV), torch.randn(N, 128, device=DEV)

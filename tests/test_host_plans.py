@@ -209,3 +209,77 @@ def test_grouped_gather_plan_matches_plan_py(n_out, n_table, n_edges, d, weights
             assert int((gp.items[:, 3] & 4).ne(0).sum()) > 0                # some row was split
     finally:
         hp.free()
+
+
+# ---------------------------------------------------------------------------------------------
+# the large-graph plans at their packing limits (tip_amd/plan.py; the kernels decode these words as unsigned)
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n_rel,bits', [(256, 8), (257, 9)])
+def test_dest_plan_words_decode_unsigned_past_bit_31(n_rel, bits):
+    """rel | src << bits wrapped to int32: with sources >= 2^(31 - bits) the words carry bit 31, and an unsigned decode gives
+    back every (source, relation) of the edge list, grouped by destination in the edge list's order."""
+    from tip_amd.plan import build_dest_plan
+    n = (1 << (31 - bits)) + 5
+    g = torch.Generator().manual_seed(bits)
+    src = torch.cat([torch.arange(n - 8, n), torch.tensor([0, 1 << (31 - bits)]), torch.randint(0, n, (500,), generator=g)])
+    dst = torch.cat([torch.arange(8), torch.tensor([n - 1, n - 1]), torch.randint(0, n, (500,), generator=g)])
+    rel = torch.cat([torch.full((8,), n_rel - 1), torch.tensor([0, n_rel - 1]), torch.randint(0, n_rel, (500,), generator=g)])
+    dp = build_dest_plan(src, dst, rel, n, n_rel, bits)
+    w = dp.edges.to(torch.int64) & 0xffffffff
+    assert bool((dp.edges < 0).any())
+    order = torch.sort(dst, stable=True).indices
+    assert torch.equal(w >> bits, src[order]) and torch.equal(w & ((1 << bits) - 1), rel[order])
+    desc = dp.node_desc.to(torch.int64)
+    cnt = torch.bincount(dst, minlength=n)
+    assert torch.equal(desc[:, 2], cnt[desc[:, 0]]) and torch.equal(torch.sort(desc[:, 0]).values, torch.arange(n))
+    first = torch.cumsum(cnt, 0) - cnt
+    assert torch.equal(desc[:, 1], first[desc[:, 0]])
+
+
+def _decode_row_plan(plan, wave_uniform):
+    """(key, rel, other, inside) of every non-padding entry, in list order per (node, tile[, half])."""
+    n_t = plan.n_tiles
+    desc = plan.desc.to(torch.int64).view(-1, 2)
+    nbat = desc[:, 1]
+    assert bool((nbat >= 1).all()) and torch.equal(desc[:, 0], torch.cumsum(nbat, 0) - nbat)
+    total = int(nbat.sum())
+    assert plan.entries.shape[0] == total + 8
+    owner = torch.repeat_interleave(torch.arange(desc.shape[0]), nbat)               # (node, tile) of every batch
+    ent = plan.entries[:total].to(torch.int64)
+    out = []
+    for half in ((0,) if wave_uniform else (0, 1)):
+        if wave_uniform:
+            oth, w1 = ent[:, 0, :].reshape(-1), ent[:, 1, :].reshape(-1)
+            row, inside = (w1 & 0xffff) // 260, (w1 >> 23) & 0x7f
+            pad = row == 32
+        else:
+            w = ent[:, half, :].reshape(-1)
+            oth, row, inside = (w >> 8) & 0xffff, (w & 0xff) // 4, w >> 24
+            pad = w == 128
+        own = owner.repeat_interleave(16)
+        keep = ~pad
+        key, tile = own // n_t, own % n_t
+        out.append((key[keep], (tile * 32 + row)[keep], oth[keep], inside[keep], (own * 2 + half)[keep]))
+    return [torch.cat(c) for c in zip(*out)]
+
+
+@pytest.mark.parametrize('wave_uniform', [False, True])
+def test_row_stream_plans_at_65536_nodes(wave_uniform):
+    """The per-lane plan packs `other` into 16 bits: at N = 65 536 with key and other = 65 535 every edge comes back from
+    the words, once, in a list of its own (node, tile); the inside flag is 0 exactly at the first entry of a row."""
+    from tip_amd.plan import build_row_stream_plan, build_row_stream_plan_s
+    n, r = 65536, 40
+    g = torch.Generator().manual_seed(16)
+    key = torch.cat([torch.tensor([n - 1, n - 1, 0, n - 1]), torch.randint(0, n, (20000,), generator=g)])
+    other = torch.cat([torch.tensor([n - 1, 0, n - 1, n - 1]), torch.randint(0, n, (20000,), generator=g)])
+    rel = torch.cat([torch.tensor([r - 1, 0, 31, r - 1]), torch.randint(0, r, (20000,), generator=g)])
+    plan = (build_row_stream_plan_s if wave_uniform else build_row_stream_plan)(key, other, rel, n, r)
+    k, rr, o, inside, lst = _decode_row_plan(plan, wave_uniform)
+    code = lambda a, b, c: (a * r + b) * n + c
+    assert torch.equal(torch.sort(code(k, rr, o)).values, torch.sort(code(key, rel, other)).values)
+    first = torch.ones_like(inside, dtype=torch.bool)
+    first[1:] = (lst[1:] != lst[:-1]) | (rr[1:] != rr[:-1])
+    assert torch.equal(inside == 0, first) and bool((inside <= 1).all() if not wave_uniform else ((inside == 0) | (inside == 0x7f)).all())
+    if not wave_uniform:                                            # the two halves of a (node, tile) hold disjoint rows
+        rows_h = torch.unique(torch.stack([lst, k * r + rr]), dim=1)
+        assert rows_h.shape[1] == torch.unique(k * r + rr).numel()

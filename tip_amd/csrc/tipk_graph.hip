@@ -583,16 +583,23 @@ extern "C" int tipk_rgcn_fwd(const tipk_graph* g, const float* x, int64_t ld_x, 
     if (workspace_bytes < tipk_rgcn_workspace_bytes(g, d_in, d_out, n_bases) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return TIPK_EINVAL;
     int st;
     const PairRoute* pr = route_for(g, n_bases, d_out);
-    if (pr && ld_out == d_out) {
+    if (pr) {
         // PAIR FORM (tip_amd/ops.py `_RGCN.forward`, same launches): sum_r A_r X W_r = sum over the linked pairs (u -> v) of
-        // C[u, v, :] . XB[u],  C[u, v, :] = sum of att[r, :] over the relations linking u -> v
+        // C[u, v, :] . XB[u],  C[u, v, :] = sum of att[r, :] over the relations linking u -> v.  Taken whatever ld_out is: a
+        // backward pass with TIPK_RGCN_WORKSPACE_FROM_FWD on this route reads the cells and XB this pass leaves in the workspace
+        // (a padded `out` is written densely into the backward pass's d XB area, then copied with its stride)
         const PairWs pw = carve_pair(workspace, n, r, n_bases, d_out, pr->n_parts);
         if ((st = pair_operands(g, pr, pw, x, ld_x, d_in, basis, att, root, d_out, stream)) != TIPK_OK) return st;
         const int64_t n_pad = pad_group(n);
         if ((st = tipk_pair_product(pw.cells, pw.xb, n_pad, n, n_bases, d_out, PAIR_KGROUP, pr->symmetric, pr->links, pr->zeros, nullptr,
                                     pw.slabs, stream)) != TIPK_OK)
             return st;
-        return tipk_sum_slabs_ex(pw.slabs, n_pad / PAIR_KGROUP, n * d_out, n * d_out, 1.f, 0, g->inv_deg, d_out, pw.t, relu, out, stream);
+        float* dense = ld_out == d_out ? out : pw.dxb;
+        if ((st = tipk_sum_slabs_ex(pw.slabs, n_pad / PAIR_KGROUP, n * d_out, n * d_out, 1.f, 0, g->inv_deg, d_out, pw.t, relu, dense,
+                                    stream)) != TIPK_OK || dense == out)
+            return st;
+        return tipk_hip_status(hipMemcpy2DAsync(out, (size_t)ld_out * 4, dense, (size_t)d_out * 4, (size_t)d_out * 4, (size_t)n,
+                                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     const Ws w = carve(workspace, n, r, n_bases, d_out);
     // XB_b = X basis_b (one batched product, A shared), X root

@@ -21,7 +21,8 @@
 //     load per batch; lane j of every 16-lane row holds entry j, and entry j reaches the half's lanes as the DPP row
 //     broadcast folded into the instruction that unpacks it;
 //   * per entry ONE 128-byte row piece per lane half is loaded (table[other, 32 channels]) and summed in a REGISTER per
-//     lane (acc = acc * inside + piece: v_cvt_f32_ubyte3 + v_fma), and the running sum is stored to the wave's private
+//     lane (acc = (inside ? acc : +0) + piece: a DPP-broadcast AND of the inside mask + v_add -- not acc * 0.0 at a row's
+//     first entry, which would carry an Inf / NaN of the previous row into it), and the running sum is stored to the wave's private
 //     [32 channels][33] tile -- the last store of a row is its sum.  (ds_add_f32 into the tile: 45 ms instead of 4: LDS
 //     float atomics run lane by lane on this chip.)  Fixed order: the sums are reproducible;
 //   * the tile is the B operand of product 1 (lane = channel) and, read transposed, the A operand of product 2
@@ -59,8 +60,10 @@ __device__ __forceinline__ u32 rp_row_bcast(u32 x) {      // lane I of every 16-
     return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x150 + (I & 15), 0xf, 0xf, true);
 }
 template <int I>
-__device__ __forceinline__ void rp_fmac_row_bcast(float& d, float x, float y) {    // d += (lane I of the row's x) * y
-    asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(d) : "v"(x), "v"(y), "n"(I & 15));
+__device__ __forceinline__ float rp_and_row_bcast(u32 m, float y) {        // (lane I of the row's m) & y
+    float d;
+    asm("v_and_b32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(d) : "v"(m), "v"(y), "n"(I & 15));
+    return d;
 }
 // LDS words written by one lane of the wave and read by another: LDS operations of a wave execute in order; the fences keep
 // the COMPILER from moving them across this point
@@ -138,9 +141,10 @@ __global__ __launch_bounds__(RP_WAVES * 64, 4) void row_products_kernel(RpArgs a
 #pragma unroll
     for (int c = 0; c < CPL; ++c) acc[c] = 0.f;
     float atv[16];
-    // Lane j of a 16-lane row unpacks entry j ONCE per batch (row offset in the table, LDS offset, the 0.0 / 1.0 of byte 3);
-    // per entry the unpacked value reaches the half's lanes as the DPP row broadcast inside the instruction that uses it:
-    // v_add_u32_dpp (load address), v_fmac_f32_dpp per channel (running sum), v_add_u32_dpp (LDS address).
+    // Lane j of a 16-lane row unpacks entry j ONCE per batch (row offset in the table, LDS offset, and byte 3 as a mask: all
+    // ones inside a row, 0 at its first entry); per entry the unpacked value reaches the half's lanes as the DPP row broadcast
+    // inside the instruction that uses it: v_add_u32_dpp (load address), v_and_b32_dpp + v_add_f32 per channel (running sum),
+    // v_add_u32_dpp (LDS address).
     // A batch is consumed in 16 / DEPTH parts, part g through buffer g & 1.
     constexpr int DEPTH = CPL == 2 ? 4 : 8, NQ = 16 / DEPTH;
     auto issue = [&](auto lo_c, float (&val)[DEPTH][CPL], u32 wv) {
@@ -161,16 +165,15 @@ __global__ __launch_bounds__(RP_WAVES * 64, 4) void row_products_kernel(RpArgs a
     };
     auto consume = [&](auto lo_c, float (&val)[DEPTH][CPL], u32 wv) {
         constexpr int LO = decltype(lo_c)::value;
-        float keep = (float)(wv >> 24);                 // v_cvt_f32_ubyte3: 0.0 at the first entry of a row (and padding), else 1.0
+        u32 keep = 0u - (wv >> 24);                     // 0 at the first entry of a row (and padding), else all ones
         const u32 offl = __umul24(wv & 0xffu, (u32)TS); // 4 * row of the tile -> byte offset of that row
         asm volatile("s_nop 1" : "+v"(keep));           // (hand-written DPP below: 2 wait states after the VALU write)
         rp_static_for<DEPTH>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
 #pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                rp_fmac_row_bcast<LO + j>(val[j][c], keep, acc[c]);    // val = inside * acc + piece
-                acc[c] = val[j][c];
-            }
+            for (int c = 0; c < CPL; ++c)               // acc = (inside ? acc : +0) + piece: the previous row's sum is MASKED
+                acc[c] = val[j][c] + rp_and_row_bcast<LO + j>(keep, acc[c]);   // off, so that an Inf / NaN in it (0 * Inf
+                                                                                // = NaN) does not reach the next row
             const u32 off = rp_row_bcast<LO + j>(offl) + tile_c;
             vec_t o;
 #pragma unroll
@@ -308,12 +311,13 @@ __global__ __launch_bounds__(RP_WAVES * 64, 4) void row_products_kernel(RpArgs a
 
 // ---------------------------------------------------------------------------------------------------------------
 // WAVE-UNIFORM entries (channels % 64 == 0).  The fp32 MFMA and the VALU instructions of a SIMD do not overlap on this chip
-// (tools/microbench/mfma_valu_overlap.hip): a launch costs at least MFMA busy + VALU busy, and the kernel above spends 2.5
-// VALU instructions per entry and 64 channels (address add, two running-sum fmacs, LDS address add for two entries a step).
+// (tools/microbench/mfma_valu_overlap.hip): a launch costs at least MFMA busy + VALU busy, and the kernel above spends 4.5
+// VALU instructions per entry and 64 channels (address add, a mask and an add for each of the two running sums, LDS address add
+// for two entries a step).
 // Here ONE entry occupies the whole wave -- lane = channel of the 64-channel block -- so everything that depends on the
 // entry alone is SCALAR: the entry words come through s_load, the table row offset is the soffset of `buffer_load_dword`,
 // the LDS row offset goes into M0 for `ds_write_addtid_b32` (address = M0 + lane * 4) and the inside-row flag is an SGPR
-// operand of the one v_fma that is left: 1 VALU instruction per entry (+ 4 on the scalar port).
+// condition of the running sum's reset: 2 VALU instructions per entry, v_cndmask + v_add (+ 6 on the scalar port).
 // Entry format (plan.RowStreamPlan.scalar()): [batch][2][16] int32, plane 0 = byte offset of the table row (other * bytes
 // per row), plane 1 = byte offset of the tile row (4 * 65 * row; row 32 = padding's dump row) | 0x3f800000 inside a row;
 // one list per (node, tile), sorted by row, padded to 16; desc as above.
@@ -383,8 +387,10 @@ __global__ __launch_bounds__(RP_WAVES * 64, 4) void row_products_s_kernel(RpArgs
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int wd = w1[LO + j];
-            const float keep = __int_as_float(wd & 0x3f800000);
-            acc = fmaf(acc, keep, val[j]);
+            // acc = (inside ? acc : +0) + piece: a mask, not a product with 0.0 -- 0 * Inf = NaN would carry a non-finite
+            // row sum (or the padding's gather of table row 0) into the next row
+            const u32 keep = (wd & 0x3f800000) ? 0xffffffffu : 0u;
+            acc = val[j] + rp_and(acc, keep);
             // M0 = tile base + the entry's plane-1 word as it is: the inside-row bits (23 .. 29) sit above the LDS address
             // bits the add-TID instruction looks at (tools/microbench/ds_addtid.hip); SALU write of M0 -> add-TID LDS
             // instruction needs one wait state, which the compiler cannot see inside inline assembly
