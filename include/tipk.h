@@ -439,7 +439,8 @@ int tipk_rgcn_node_products(const float* dyc, int64_t n_rows, int d, const int32
  *     + table[second + part_first[p] + i] (table = pg: first half = the rows of (u, v), u <= v, second half = the rows of
  *     their mirrors; rows nobody writes hold zeros), wg_part [n_wg] = the partition a workgroup stages, ids = rows counted
  *     from the partition's first, output rows = p * n_rel + r (out [n_parts * n_rel][d], added over p in order by
- *     tipk_sum_slabs(_group)).  d = 32 (one 128-byte row per pair); every partition is staged part_len rows long.
+ *     tipk_sum_slabs(_group)).  d = 32 (one 128-byte row per pair); every partition is staged part_len rows long.  The plan is
+ *     walked with 8 lanes per row (build it for lanes = 8, whatever column split the att table of the forward cells needs).
  */
 int tipk_rgcn_pair_grads_supported(int n_bases, int d);
 int tipk_rgcn_pair_grads(const float* cells, int64_t n_lines, const float* xb, const float* g, int64_t ld_g,

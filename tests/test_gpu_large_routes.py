@@ -13,69 +13,11 @@ import pytest
 import torch
 
 from oracle import tip_oracle as O
+from route_harness import _assert_route, _bits, _close, _graph, _labels
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 Y_BYTES = 192 << 20
-
-ROUTE_LABELS = {'rows_s': 'row_products_s[', 'rows': 'row_products[', 'dest': 'dest_products[', 'csr': 'gather_rows_csr[',
-                'Y': 'gather_sum[dd.fwd', 'gather_sum': 'gather_sum[dd.bwd'}
-
-
-def _graph(N, R, seed, n_random=120000):
-    """edge_index [2, E], edge_type [E], range_list [R, 2] (relation-major, as the reference's data has them)."""
-    g = torch.Generator().manual_seed(seed)
-    used = list(range(1, 32)) + list(range(64, R - 1)) if R >= 66 else list(range(1, R - 1))
-    used = torch.tensor(used)
-    quiet = 64                                                          # nodes 0 .. 63: no in-edges; N - 64 .. N - 1: no out-edges
-    src = torch.randint(0, N - quiet, (n_random,), generator=g)
-    dst = torch.randint(quiet, N, (n_random,), generator=g)
-    hub_src = torch.randint(0, N - quiet, (10000,), generator=g)      # the hub is node N - 1 (edges that touch node N - 1)
-    loops = torch.arange(quiet, N - quiet, max(1, (N - 2 * quiet) // 200))
-    src = torch.cat([src, hub_src, loops, src[:500]])
-    dst = torch.cat([dst, torch.full((10000,), N - 1), loops, dst[:500]])
-    rel = used[torch.randint(0, used.numel(), (src.numel(),), generator=g)]
-    rel[-500:] = rel[:500]                                              # duplicates: same (source, destination, relation)
-    order = torch.sort(rel, stable=True).indices
-    src, dst, rel = src[order], dst[order], rel[order]
-    cnt = torch.bincount(rel, minlength=R)
-    assert int(cnt[0]) == 0 and int(cnt[R - 1]) == 0
-    end = torch.cumsum(cnt, 0)
-    rg = torch.stack([end - cnt, end], 1)
-    return torch.stack([src, dst]), rel, rg
-
-
-def _labels(fn):
-    from tip_amd import ops
-    ops.timing_start()
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        rec = ops.timing_stop()
-    return out, ' '.join(sorted(rec))
-
-
-def _assert_route(labels, want, pass_name):
-    assert ROUTE_LABELS[want] in labels, (pass_name, want, labels)
-    for other, lab in ROUTE_LABELS.items():
-        if other != want and lab.split('[')[0] in ('row_products_s', 'row_products', 'dest_products', 'gather_rows_csr'):
-            assert lab not in labels, (pass_name, want, other, labels)
-
-
-def _close(got, want, rel_tol):
-    want = want.to(torch.float64)
-    got = got.detach().to('cpu', torch.float64)
-    fw, fg = torch.isfinite(want), torch.isfinite(got)
-    assert torch.equal(fw, fg), 'non-finite pattern differs at %d of %d elements' % (int((fw != fg).sum()), fw.numel())
-    w = want[fw]
-    scale = float(w.abs().max()) if w.numel() else 1.0
-    torch.testing.assert_close(got[fw], w, rtol=rel_tol, atol=rel_tol * scale + 1e-12)
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
 
 def _run_case(N, R, d_in, d_out, nb, fwd, bwd, seed, fuse_relu=False, inf_up=False):
     from tip_amd.layers import MyRGCNConv2

@@ -539,7 +539,9 @@ extern "C" int tipk_graph_prepare_rgcn(tipk_graph* g, int n_bases, int d_out) {
         st = tipk_hip_status(hipMemcpy(scale.data(), g->inv_deg, (size_t)n * 4, hipMemcpyDeviceToHost));
         if (st != TIPK_OK) return st;
         tipk_plan::PairBwdH pb;
-        if (!tipk_plan::build_pair_bwd_plan(src.data(), dst.data(), rel.data(), e, n, r, scale.data(), pr->symmetric, n_cu, lanes, piece, pb))
+        // (8 lanes: the d att gather stages 128-byte gradient rows in one column block, whatever split the att table needs)
+        if (!tipk_plan::build_pair_bwd_plan(src.data(), dst.data(), rel.data(), e, n, r, scale.data(), pr->symmetric, n_cu, n_bases / 4, piece,
+                                            pb))
             return TIPK_OK;                                                    // forward in pair form, backward on the generic route
         st = upload(pr, &pr->slots, pb.slots.data(), pb.slots.size());
         if (st == TIPK_OK) st = upload(pr, &pr->node_desc, pb.node_desc.data(), pb.node_desc.size());

@@ -491,8 +491,9 @@ def rgcn_graph(edge_index, rel, n_nodes, n_rel, chunk=DEFAULT_CHUNK, in_degree=N
         if pair_fwd is not None and ops.pair_grads_supported(n_bases, d_out):
             # backward pass in pair form as well (round 5): the cells of the forward pass + one 128-byte gradient row per
             # linked pair; d att walks half the edges of a symmetric graph.  The plan does not depend on the layer's width:
-            # the layers of a model share it
-            sym, lanes_p = pair_fwd.symmetric, (n_bases // split_p) // 4
+            # the layers of a model share it.  Its d att gather stages 128-byte gradient rows in ONE column block (8 lanes a row,
+            # what tipk_stream_gather_parts launches), whatever split the att table of the cell gather needs
+            sym, lanes_p = pair_fwd.symmetric, n_bases // 4
             pair_bwd = lambda: _shared_pair_bwd_plan(src, dst, rel, n_nodes, n_rel, 1.0 / deg, sym, pair_wgs, lanes_p, plan_share)
         if split_s:
             # compact node-major rows when the products of dY can run on them (tipk_rgcn_node_products); with the pair-form

@@ -677,6 +677,7 @@ def pair_att_gather(pb, pg):
     nb = pg.shape[1]
     assert pg.shape[0] == 2 * pb.n_alloc + 1 and pg.is_contiguous()
     gp = pb.gather
+    assert gp.lanes == 8, 'tipk_stream_gather_parts walks 128-byte rows with 8 lanes: the plan was built for another launch shape'
     slabs = torch.empty((pb.n_parts, pb.n_rel, nb), dtype=torch.float32, device=pg.device)
     with _timed('pair_att_gather[parts=%d,edges=%d]' % (pb.n_parts, gp.n_edges)):
         check(lib().tipk_stream_gather_parts(ptr(pg), nb, nb, pb.n_alloc, ptr(pb.part_first), pb.part_len, ptr(pb.wg_part), gp.n_wg,
