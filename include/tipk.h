@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 24
+#define TIPK_ABI_VERSION 25
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -51,6 +51,8 @@ const char* tipk_build_id(void);
  *      "gemm_stream_kk"      1 = lane-per-row streaming body for d att
  *      "rg_occupancy"        workgroups per CU tipk_rel_gather aims for: 1, 2 (0 = library default)
  *      "dm_task_kernel"      1 = fused objective through the k/4-lanes-per-position task kernel (the round-2 kernel; A/B runs)
+ *      "screen_search"       1 = tipk_distmult_screen filters known pairs by binary search even where the LDS bitmap fits
+ *                            (section 4c; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -720,6 +722,40 @@ int tipk_pair_table_loss(const float* s1t, const float* s2t, int64_t ld, int64_t
                          const uint32_t* pos_pairs, const uint32_t* neg_pairs, const int64_t* rel_ptr,
                          const int32_t* order, int64_t n_positions, float eps, double* loss_parts,
                          float* g_s1t /* nullable */, float* g_s2t /* nullable */, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4c. DistMult screen: the k best UNSEEN candidates of a query, ranked on the logit
+ *        s(u, v, r) = sum_k z[u,k] z[v,k] w[r,k]
+ *     (serving; no reference call site: the reference ranks side effects per relation, never the pairs themselves).
+ *
+ *   z [n_nodes x dim], rel_w [n_rel x dim] fp32 row-major (z 16-byte aligned).  queries: HOST int32 [n_q][2] =
+ *   (relation r, drug u); u = -1 is a RELATION query: every unordered pair u < v (no self pairs; DistMult is symmetric,
+ *   so (u, v) and (v, u) are one candidate); u >= 0 is a DRUG query: every partner v != u, returned as (u, v).
+ *   known_keys / known_ptr (nullable together; device): int64 keys u*n+v sorted inside each relation, relation r's block
+ *   [known_ptr[r], known_ptr[r+1]) -- the sampler's pos_key_sorted / rel_ptr layout.  A candidate is dropped when u*n+v
+ *   OR v*n+u is a key of its relation (lists that hold one direction only are handled).
+ *   Output per query (device): out_score fp32 [n_q x k] = LOGITS (sigma saturates to 1.0 in fp32 above ~17, which would
+ *   turn the top of a list into ties), out_u / out_v int32 [n_q x k]; order: descending logit, ties by ascending key
+ *   u*n+v; a query with fewer than k candidates is padded with (-inf, -1, -1).
+ *   Numerics: each logit is fp32, a = z[u,k] * w[r,k] rounded, then fmaf(a, z[v,k], acc) for k ascending from 0 -- one
+ *   value per pair on every route and split; the result is BITWISE repeatable (the merge across workgroups is by rank).
+ *   Filter routes: an LDS bitmap of the relation's known pairs when n_nodes^2 bits fit in 64 KB
+ *   (tipk_distmult_screen_bitmap_route), binary search in the keys otherwise or under option "screen_search"; same bits.
+ *   Supported (tipk_distmult_screen_supported): 1 <= n_nodes <= 46 340 (n^2 < 2^31), dim % 4 == 0 in 4..256, 1 <= k <= 1 024.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k <= 0, a relation outside [0, n_rel), a drug
+ *   outside [-1, n_nodes), keys without offsets (or the reverse), a NULL pointer; then TIPK_EUNSUPPORTED outside the
+ *   supported range; TIPK_OK implies correct numbers.
+ *   workspace: tipk_distmult_screen_workspace_bytes(n_nodes, dim, n_q, k) bytes, 16-byte aligned (-1: unsupported).
+ *   This entry SYNCHRONISES `stream` once: it copies the host query list into the workspace and waits for the copy, so
+ *   the caller may reuse `queries` on return (not for stream capture).
+ */
+int     tipk_distmult_screen_supported(int64_t n_nodes, int dim, int k);
+int64_t tipk_distmult_screen_workspace_bytes(int64_t n_nodes, int dim, int64_t n_q, int k);
+int     tipk_distmult_screen_bitmap_route(int64_t n_nodes);     /* 1 = the LDS bitmap filters this node count (options apply) */
+int     tipk_distmult_screen(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                             const int32_t* queries /* host */, int64_t n_q,
+                             const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                             int k, float* out_score, int32_t* out_u, int32_t* out_v, void* workspace, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libtipk.so')
 CSRC = os.path.join(_HERE, 'csrc')
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class TipkError(RuntimeError):
@@ -149,6 +149,10 @@ SIGNATURES = {
     'tipk_pair_table_fwd': (_I, [_P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _P]),
     'tipk_pair_table_bwd': (_I, [_P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _P, _P]),
     'tipk_pair_table_loss': (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _F, _P, _P, _P, _P]),
+    'tipk_distmult_screen_supported': (_I, [_L, _I, _I]),
+    'tipk_distmult_screen_workspace_bytes': (_L, [_L, _I, _L, _I]),
+    'tipk_distmult_screen_bitmap_route': (_I, [_L]),
+    'tipk_distmult_screen': (_I, [_P, _L, _I, _P, _L, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P]),
     'tipk_negsample_wgs_per_cu': (_I, [_L]),
     'tipk_typed_negative_sampling': (_I, [_P, _P, _L, _L, C.c_uint64, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _P]),
     'tipk_counter_advance': (_I, [_P, _P]),

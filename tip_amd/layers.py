@@ -13,6 +13,7 @@ three TIP graphs are constant during training.  Pass a new tensor (or modify in 
 import math
 import os
 import pickle
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -27,6 +28,9 @@ from .plan import (build_pair_bwd_plan, build_dest_plan, build_row_stream_plan, 
 from .utils import process_edges, auprc_auroc_ap_by_range
 
 EPS = 1e-13                    # src/layers.py:15
+
+# TIP.screen's result: per query row the k best pairs (u, v) of side effect `relation`, best first
+ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP']
@@ -792,6 +796,59 @@ class MultiInnerProductDecoder(nn.Module):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps), fused (K9+K10)."""
         return ops.distmult_objective(z, self.weight, pos_index, neg_index, edge_type)
 
+    def screen(self, z, k, relations=None, drugs=None, known=None):
+        """Screen (extension, `tipk_distmult_screen`): the k best candidates per query by LOGIT -> (logits [Q, k],
+        u int32 [Q, k], v int32 [Q, k]); no autograd.  relations: ids (None = all num_et).  drugs None: one relation query
+        per relation (all pairs u < v); drugs given: one drug query per (drug, relation), DRUG-MAJOR -- row
+        i * len(relations) + j is (drugs[i], relations[j]), its pairs (drugs[i], v).  known: (keys, ptr) of the pairs to
+        drop (`ops.distmult_screen`)."""
+        q = screen_queries(self.num_et, relations, drugs)
+        return ops.distmult_screen(z.detach(), self.weight.detach(), q, k, known)
+
+
+def screen_queries(num_et, relations=None, drugs=None):
+    """int32 [Q, 2] (relation, drug | -1) on the host, in the order `MultiInnerProductDecoder.screen` documents."""
+    rel = torch.arange(num_et, dtype=torch.int64) if relations is None \
+        else torch.as_tensor(relations).to('cpu', torch.int64).reshape(-1)
+    if drugs is None:
+        q = torch.stack([rel, torch.full_like(rel, -1)], 1)
+    else:
+        dr = torch.as_tensor(drugs).to('cpu', torch.int64).reshape(-1)
+        q = torch.stack([rel.repeat(dr.numel()), dr.repeat_interleave(rel.numel())], 1)
+    return q.to(torch.int32)
+
+
+_SCREEN_KEYS = {}
+
+
+def _screen_known(d, exclude):
+    """(keys, ptr) of the pairs `TIP.screen` drops: the training positives ('train', the sampler's cached keys) or
+    train + test ('all', merged once per pair of edge tensors and cached)."""
+    if exclude is None:
+        return None
+    from .neg_sampling import _cached_keys
+    kt, pt = _cached_keys(d.dd_train_idx, d.n_drug, d.dd_train_range)[:2]
+    if exclude == 'train':
+        return kt, pt
+    ti = d.dd_test_idx
+    ident = (d.dd_train_idx.data_ptr(), d.dd_train_idx._version, ti.data_ptr(), tuple(ti.shape), ti._version,
+             str(ti.device), int(d.n_drug))
+    hit = _SCREEN_KEYS.get(ident)
+    if hit is None:
+        ke, pe = _cached_keys(ti, d.n_drug, d.dd_test_range)[:2]
+        n_rel = pt.numel() - 1
+        ids = torch.arange(n_rel, device=kt.device)
+        rel = torch.cat([torch.repeat_interleave(ids, pt[1:] - pt[:-1]), torch.repeat_interleave(ids, pe[1:] - pe[:-1])])
+        keys = torch.cat([kt, ke])
+        order = torch.sort(rel * (int(d.n_drug) ** 2) + keys).indices
+        ptr = torch.zeros(n_rel + 1, dtype=torch.int64, device=kt.device)
+        ptr[1:] = torch.cumsum(torch.bincount(rel, minlength=n_rel), 0)
+        hit = (keys[order].contiguous(), ptr)
+        if len(_SCREEN_KEYS) > 8:
+            _SCREEN_KEYS.clear()
+        _SCREEN_KEYS[ident] = hit
+    return hit
+
 
 class NNDecoder(nn.Module):
     """The paper's DR-NN decoder (reference `src/layers.py:598-637`):
@@ -1001,6 +1058,29 @@ class TIP(nn.Module):
         if not vals:
             return (torch.zeros((0, k), device=pairs.device), torch.zeros((0, k), dtype=torch.int64, device=pairs.device))
         return torch.cat(vals), torch.cat(ids)
+
+    def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
+        """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it
+        (`MultiInnerProductDecoder.screen`, one `tipk_distmult_screen` call on `self.embeddings`, under no_grad).
+        relations: side-effect ids (None = all); drugs: None = relation screen (pairs u < v), else the best partners v of
+        each drug, drug-major.  exclude: 'train' drops the training positives (held-out test pairs can and do appear),
+        'all' drops train and test positives (truly novel pairs), None drops nothing.  Ranking is on the logit; sigmoid
+        = True applies sigma afterwards (padding: score sigma(-inf) = 0, u = v = -1).
+        -> ScreenResult(score [Q, k], u [Q, k], v [Q, k], relation [Q, k]) on the model's device."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('screen ranks DistMult logits over all pairs; the NN decoder has no screen kernel')
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; screen the '
+                                      'unsharded model (tip_amd.dist.gather_state_dict)')
+        if exclude not in ('train', 'all', None):
+            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        known = _screen_known(self.data, exclude)
+        q = screen_queries(self.decoder.num_et, relations, drugs)
+        with torch.no_grad():
+            logit, u, v = self.decoder.screen(self.embeddings, k, relations, drugs, known)
+            score = torch.sigmoid(logit) if sigmoid else logit
+        relation = q[:, 0].to(device=logit.device, dtype=torch.int64)[:, None].expand(-1, logit.shape[1])
+        return ScreenResult(score, u, v, relation)
 
     def test(self, print_output=True):
         self.eval()

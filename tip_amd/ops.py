@@ -1054,6 +1054,38 @@ def distmult_bwd(g_score, score, z, weight, edge_index, edge_type, sigmoid=True)
     return g_z, g_w
 
 
+def distmult_screen(z, rel_w, queries, k, known=None):
+    """The k best candidates of every query by DistMult logit, known pairs dropped (include/tipk.h section 4c).
+
+    queries: int [Q, 2] = (relation r, drug u), u = -1 for a relation query (all pairs u < v), else a drug query (all
+    partners v != u); read on the host.  known: None or (keys int64 u*n+v sorted inside each relation, ptr int64
+    [n_rel + 1]) on z's device -- the sampler's layout (`neg_sampling._cached_keys`).
+    -> (logits float32 [Q, k], u int32 [Q, k], v int32 [Q, k]), descending logit then ascending key; (-inf, -1, -1)
+    pads a query with fewer than k candidates.  Synchronises the current stream once (the query list goes to the device)."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('distmult_screen: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (tuple(z.shape), tuple(rel_w.shape)))
+    keys = kptr = None
+    if known is not None:
+        keys, kptr = known
+        require_device(keys, kptr)
+        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+    q = torch.as_tensor(queries).to('cpu', torch.int32).reshape(-1, 2).contiguous()
+    n, dim, n_q, k = z.shape[0], z.shape[1], q.shape[0], int(k)
+    dev = z.device
+    out_s = torch.empty((n_q, max(k, 0)), dtype=torch.float32, device=dev)
+    out_u = torch.empty((n_q, max(k, 0)), dtype=torch.int32, device=dev)
+    out_v = torch.empty((n_q, max(k, 0)), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().tipk_distmult_screen_workspace_bytes(n, dim, n_q, k))
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    check(lib().tipk_distmult_screen(ptr(z), n, dim, ptr(rel_w), rel_w.shape[0], ptr(q), n_q, ptr(keys), ptr(kptr), k,
+                                     ptr(out_s), ptr(out_u), ptr(out_v), ptr(ws), stream_ptr(dev)),
+          'tipk_distmult_screen')
+    return out_s, out_u, out_v
+
+
 _DET_WS = {}
 
 
