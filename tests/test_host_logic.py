@@ -995,3 +995,106 @@ def test_sampler_spec_wide_branch_matches_python_integers():
                     if cand not in keys:
                         break
                 assert (got[0, e], got[1, e]) == (cand // n, cand % n), (n, e)
+
+
+# ------------------------------------------------------------------ the R-GCN layer's route decision
+def _route_graph(c, calls, row_plans=None):
+    """An `ops.AggGraph` holding, as attribute-only stand-ins, the plans `layers.rgcn_graph` installs on a device for case `c` of
+    the route table (under the switches set right now): the relation-local plans up to 1 024 nodes, the pair plan where the
+    att table fits the LDS, the pair-backward plan where `pair_grads` takes the widths, the transposed stream plan -- lazy, as
+    behind a pair-backward plan -- with or without compact rows.  Every lazy plan notes in `calls` that it was built."""
+    from types import SimpleNamespace as NS
+    from tip_amd import ops
+    N, R, d_out, nb = c['N'], c['R'], c['d_out'], c['nb']
+
+    def lazy(name, plan):
+        return lambda: calls.append(name) or plan
+    kw = {}
+    if N <= 1024:
+        kw['rl_fwd'] = NS(n_nodes=N, n_rel=R)
+        split = ops.stream_gather_split(R, nb) if N * N < 2 ** 24 else 0
+        if split:
+            sym = c['kind'] == 'sym' and bool(ops.lib().tipk_pair_product_supported(nb, d_out))
+            kw['pair_fwd'] = NS(n_table=R, n_rows=N * N, lanes=(nb // split) // 4, symmetric=sym, n_bands=1, n_wg=8, idx_unit=4)
+            if ops.pair_grads_supported(nb, d_out):
+                kw['pair_bwd'] = lazy('pair_bwd', NS())
+        if ops.rel_stream_split(N, d_out) and R * N < 2 ** 24:
+            compact = NS() if ops.node_products_slabs(N, d_out, R, nb) > 0 else None
+            kw['rs_bwd'] = lazy('rs_bwd', NS(compact=compact))
+    if row_plans is not None:
+        kw['row_fwd'] = kw['row_bwd'] = row_plans
+    return ops.AggGraph(lazy('fwd', NS(n_out=N, n_table=R * N)), lazy('bwd', NS()), **kw)
+
+
+def test_rgcn_route_matches_the_route_table(monkeypatch):
+    """`ops.rgcn_route` -- the one route decision of `_RGCN`, asked by `encoder.usable` as well -- names, for EVERY case of the
+    GPU route matrix (tests/test_gpu_rgcn_routes.py: the table is imported, not copied), the forward route and the pair-form
+    backward pass the launch labels must show there, and the XB storage that backward route reads.  No device: plan attributes,
+    switches and the library's support queries only.  A lazy plan is built only on a route that needs it: the transposed
+    stream plan only behind a pair-form forward pass whose backward pass is not the pair form, row plans never here."""
+    import test_gpu_rgcn_routes as T
+    from tip_amd import ops
+
+    def boom():
+        raise AssertionError('a lazy plan was built that the route does not need')
+    for cid in T.CASE_IDS:
+        c = T._case(cid)
+        with monkeypatch.context() as mp:
+            for name in c['switches']:
+                mp.setenv(name, '1')
+            calls = []
+            graph = _route_graph(c, calls, row_plans=boom if c['fwd'] != 'Y' else None)
+            route = ops.rgcn_route(graph, c['N'], c['d_in'], c['d_out'], c['nb'], c['R'])
+            assert route.fwd == c['fwd'], (cid, route)
+            assert route.pair_bwd == (c['bwd'] == 'pair_grads'), (cid, route)
+            pair = c['fwd'].startswith('pair_')
+            assert (route.pair is not None) == pair and (route.pair is None or route.pair is graph.pair_fwd), (cid, route)
+            assert route.xb == ('graph' if c['bwd'] == 'pair_grads' else 'graph+xbt' if c['bwd'] == 'node_products_xbt' else 'own'), (cid, route)
+            assert ('rs_bwd' in calls) == (pair and not route.pair_bwd), (cid, calls)
+            assert ('fwd' in calls) == (c['fwd'] == 'Y') and 'bwd' not in calls, (cid, calls)
+            # a pass that needs no gradient reads neither backward plan
+            calls = []
+            graph = _route_graph(c, calls, row_plans=boom if c['fwd'] != 'Y' else None)
+            cold = ops.rgcn_route(graph, c['N'], c['d_in'], c['d_out'], c['nb'], c['R'], need_grad=False)
+            assert cold.fwd == c['fwd'] and not cold.pair_bwd and not cold.handover and 'rs_bwd' not in calls and 'pair_bwd' not in calls, (cid, cold, calls)
+
+
+def test_rgcn_route_large_graphs_and_handover(monkeypatch):
+    """The large-graph routes by name (`rows` on either row-plan form, `dest` where the row kernels do not take the shape --
+    asked BEFORE the lazy row plan is touched), r = 0, and the two-layer flags: the hand-over of a pending slab sum needs the
+    pair-form backward pass and 32 input columns; `_pair_ok` of the fused encoder step is the same decision."""
+    from types import SimpleNamespace as NS
+    from tip_amd import encoder, ops
+
+    def boom():
+        raise AssertionError('a lazy plan was built that the route does not need')
+    plan = lambda n, r: (lambda: NS(n_nodes=n, n_rel=r))
+    g = ops.AggGraph(boom, boom, row_fwd=plan(8192, 200), row_bwd=boom, dest_fwd=boom)
+    assert ops.rgcn_route(g, 8192, 32, 32, 32, 200)[:3] == ('rows', None, False)
+    g = ops.AggGraph(boom, boom, row_fwd=plan(8192, 100), row_bwd=boom, dest_fwd=boom, row_wave_uniform=True)
+    assert ops.rgcn_route(g, 8192, 64, 64, 5, 100).fwd == 'rows'
+    g = ops.AggGraph(boom, boom, row_fwd=boom, row_bwd=boom, dest_fwd=plan(65537, 40))       # one node past the per-lane form
+    assert ops.rgcn_route(g, 65537, 32, 32, 8, 40).fwd == 'dest'
+    monkeypatch.setenv('TIPK_NO_ROW_PRODUCTS', '1')
+    g = ops.AggGraph(boom, boom, row_fwd=boom, row_bwd=boom, dest_fwd=plan(8192, 200))
+    assert ops.rgcn_route(g, 8192, 32, 32, 32, 200).fwd == 'dest'
+    monkeypatch.delenv('TIPK_NO_ROW_PRODUCTS')
+    assert ops.rgcn_route(ops.AggGraph(boom, boom, pair_fwd=NS(), rl_fwd=boom), 100, 32, 32, 32, 0) == ('Y', None, False, 'own', False, False)
+    # two layers on a pair-form graph, 64 -> 32 -> 16 at 32 bases
+    c = {'N': 97, 'R': 40, 'd_out': 32, 'nb': 32, 'kind': 'sym'}
+    att, basis1, basis2 = torch.zeros(40, 32), torch.zeros(32, 64, 32), torch.zeros(32, 32, 16)
+    g1, g2 = _route_graph(c, []), _route_graph(dict(c, d_out=16), [])
+    r1 = ops.rgcn_route(g1, 97, 64, 32, 32, 40, operands=(None, None, att), partner=(att, g2, 16))
+    r2 = ops.rgcn_route(g2, 97, 32, 16, 32, 40)
+    assert (r1.fwd, r1.pair_bwd, r1.handover, r1.cells_two) == ('pair_sym', True, False, True)      # (64 input columns: no hand-over INTO layer 1)
+    assert (r2.fwd, r2.pair_bwd, r2.handover, r2.cells_two) == ('pair_sym', True, True, False)
+    assert encoder._pair_ok(g1, att, basis1, 97) and encoder._pair_ok(g2, att, basis2, 97)
+    for switch, want in (('TIPK_NO_LAYER_HANDOVER', (True, False, True)), ('TIPK_NO_CELLS_TWO', (True, True, False)),
+                         ('TIPK_NO_PAIR_BWD', (False, False, True))):
+        monkeypatch.setenv(switch, '1')
+        r1 = ops.rgcn_route(g1, 97, 64, 32, 32, 40, operands=(None, None, att), partner=(att, g2, 16))
+        r2 = ops.rgcn_route(g2, 97, 32, 16, 32, 40)
+        assert (r2.pair_bwd, r2.handover, r1.cells_two) == want, (switch, r1, r2)
+        assert encoder._pair_ok(g2, att, basis2, 97) == want[0]
+        monkeypatch.delenv(switch)
+    assert not encoder._pair_ok(_route_graph(dict(c, nb=16), []), torch.zeros(40, 16), torch.zeros(16, 64, 32), 97)   # no pair_grads at 16 bases

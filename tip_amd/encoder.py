@@ -30,6 +30,8 @@ another stamp than its forward pass left recomputes them.
 
 `usable(...)` says whether a call can take this node (identity protein features, a pair-form D-D graph for both layers, widths
 the fused kernels take, no relation sharding); everything else runs on the per-layer nodes of tip_amd/ops.py, unchanged.
+Whether a layer takes the pair form is asked of `ops.rgcn_route`, the one route decision of `ops._RGCN`; launches 10 and 13 are
+`ops.rgcn_dense_tail`, the dense tail the per-layer node runs as well.
 """
 import torch
 
@@ -46,18 +48,9 @@ class EncoderPlans(object):
 
 
 def _pair_ok(graph, att, basis, n):
-    """The pair form applies to this layer exactly as `_RGCN.forward` decides it (tip_amd/ops.py)."""
-    r, nb = att.shape
-    d_out = basis.shape[2]
-    pair = graph.pair_fwd if r > 0 else None
-    if pair is None:
-        return False
-    if pair.symmetric and not lib().tipk_pair_product_supported(nb, d_out):
-        return False
-    split = ops.stream_gather_split(r, nb)
-    if not (pair.n_table == r and pair.n_rows == n * n and split and (nb // split) // 4 == pair.lanes):
-        return False
-    return ops.pair_grads_supported(nb, d_out) and graph.pair_bwd is not None
+    """This layer takes the pair form, forward and backward: `ops.rgcn_route`, the decision `_RGCN.forward` itself takes."""
+    route = ops.rgcn_route(graph, n, basis.shape[1], basis.shape[2], att.shape[1], att.shape[0])
+    return route.pair is not None and route.pair_bwd
 
 
 def usable(plans, xd, w_h, d_norm, c2_weight, c1_bias, c2_bias, basis1, att1, basis2, att2):
@@ -155,37 +148,6 @@ def pair_att_gather_two(pb, pg_a, pg_b):
     return ops.slab_job(sa), ops.slab_job(sb)
 
 
-def rgcn_dense_backward(x, basis, root, g, g_xb, gate_x, slab_jobs):
-    """(dX, d basis, d root) of an R-GCN layer given dXB [bases, N, d_out] and g [N, d_out] (1/deg not applied to the root
-    term), plus the pending ordered slab sums `slab_jobs` (d att) finished in the same launch where the reductions fit one
-    workgroup per tile (`tipk_gemm_wg_group`); otherwise the grouped split-K products of `_RGCN.backward`."""
-    n, d_in = x.shape
-    nb = basis.shape[0]
-    slab_jobs = list(slab_jobs)
-    if len(slab_jobs) <= ops._lib.WG_SUMS_MAX:
-        w_basis = ops.wg_gemm_job(x.t(), g_xb)
-        w_root = ops.wg_gemm_job(x.t(), g)
-        w_x = ops.wg_gemm_job(g_xb, basis.transpose(1, 2), reduce_batch=True, a2=g, b2=root.t(), gate=gate_x)
-        if w_basis is not None and w_root is not None and w_x is not None:
-            ops.wg_gemm_group([w_basis, w_root, w_x], slab_jobs)
-            return w_x.out, w_basis.out, w_root.out
-    j_root = ops.gemm_job(x.t(), g)
-    j_basis = ops.gemm_job(x.t(), g_xb)
-    j_xr = ops.gemm_job(g, root.t(), ksplit=1)
-    g_x = j_xr.out
-    j_xq = ops.gemm_job(g_xb, basis.transpose(1, 2), out=g_x, c_in=g_x, reduce_batch=True, kgroup=ops.large_kgroup(n, nb))
-    if j_xq.slabs is not None:
-        if gate_x is not None:
-            j_xq.gate = gate_x
-        ops.gemm_group([j_basis, j_root, j_xr, j_xq], slab_jobs)
-    else:
-        ops.gemm_group([j_basis, j_root, j_xr], slab_jobs)
-        ops.gemm_group([j_xq])
-        if gate_x is not None:
-            g_x = ops.rows_affine(g_x, gate=gate_x)
-    return g_x, j_basis.out, j_root.out
-
-
 class _EncoderStep(torch.autograd.Function):
     """z = FMEncoder.forward(...) for identity protein features on a pair-form D-D graph (module docstring)."""
 
@@ -249,13 +211,13 @@ class _EncoderStep(torch.autograd.Function):
         pb = g1.pair_bwd
         # 9. / 10. layer 2: dXB2 and the gradient rows of the linked pairs; then the dense gradients (dX1 gated by x1 > 0)
         pg2, dxb2 = ops.pair_grads(pb, cells2, xb2, g, table=1)
-        g_x1, g_basis2, g_root2 = rgcn_dense_backward(x1, basis2, root2, g, dxb2, x1, [])
+        g_x1, g_basis2, g_root2 = ops.rgcn_dense_tail(x1, basis2, root2, g, dxb2, x1, [])
         # 11. layer 1
         pg1, dxb1 = ops.pair_grads(pb, cells1, xb1, g_x1, table=0)
         # 12. d att of both layers: one launch over the shared plan
         j_att1, j_att2 = pair_att_gather_two(pb, pg1, pg2)
         # 13. layer 1's dense gradients + both d att slab sums
-        g_x0, g_basis1, g_root1 = rgcn_dense_backward(x0, basis1, root1, g_x1, dxb1, None, [j_att1, j_att2])
+        g_x0, g_basis1, g_root1 = ops.rgcn_dense_tail(x0, basis1, root1, g_x1, dxb1, None, [j_att1, j_att2])
         # 14. the P -> D stage down to conv2's g W, d W2 / d b2 as slabs
         g_xd, j_wh, gw, j_w2, j_b2 = pd_stage_bwd(g_x0, d_norm, mean, w_h, ctx.ne, plans.cat, plans.pd, agg2, w2, plans.pp_rows.scale,
                                                  want_xd=ctx.needs_input_grad[0])

@@ -5,6 +5,7 @@ path is executed by the HIP kernels in `tip_amd/csrc` through the C ABI (`includ
 Backward passes are explicit (no autograd tracing through E x d tensors): each Function saves
 only N x d activations and the static graph plans.
 """
+import collections
 import os
 
 import torch
@@ -634,12 +635,6 @@ def sum_slabs_xb_supported(d_in, d_out):
     return d_in == 32 and 1 <= d_out <= 32 and not switches.on('TIPK_NO_LAYER_HANDOVER')
 
 
-def _finish_pending(x, pend):
-    """Materialise a layer output whose final slab sum was left to its consumer (`_RGCN.forward(defer_output=True)`)."""
-    slabs, scale, addend, relu = pend
-    sum_slabs(slabs, out=x, row_scale=scale, addend=addend, relu=relu)
-
-
 def pair_grads_supported(nb, d):
     return bool(lib().tipk_rgcn_pair_grads_supported(int(nb), int(d))) and not switches.on('TIPK_NO_PAIR_BWD')
 
@@ -1245,7 +1240,7 @@ def pair_product(cells, xb_nb, symmetric=False, links=None, zeros=None, xbt=None
     assert xbt is None or (tuple(xbt.shape) == (n, d, nb) and xbt.is_contiguous() and xbt.dtype == torch.float32)
     assert cells.is_contiguous() and xb_nb.shape[:2] == (n_pad, nb) and n_pad % PAIR_KGROUP == 0
     padded = xb_nb.stride() == (nb * 32, 32, 1) and d <= 32
-    if (not lib().tipk_pair_product_supported(nb, d) or switches.on('TIPK_NO_PAIR_PRODUCT') or not padded) and not symmetric:
+    if pair_product_on_gemm(nb, d, symmetric, padded):
         job = gemm_job(cells, xb_nb, reduce_batch=True, kgroup=PAIR_KGROUP)      # same sums on the tiled GEMM
         with _timed('gemm[%s]' % job.label):
             check(lib().tipk_gemm_f32(job.desc, stream_ptr(cells.device)), 'tipk_gemm_f32')
@@ -1260,8 +1255,23 @@ def pair_product(cells, xb_nb, symmetric=False, links=None, zeros=None, xbt=None
     return slabs
 
 
+def _lazy_plan(name):
+    """Property of a plan that may be given as a zero-argument callable: it is called once, on first read."""
+    slot = '_' + name
+
+    def get(self):
+        plan = getattr(self, slot)
+        if callable(plan):
+            plan = plan()
+            setattr(self, slot, plan)
+        return plan
+    return property(get)
+
+
 class AggGraph(object):
     """fwd: out rows <- table rows;  bwd: the transpose.  scale = per-out-row factor (1/deg)."""
+    fwd, bwd, csr_bwd, rl_fwd, rl_bwd, rs_bwd, pair_bwd, dest_fwd, row_fwd, row_bwd = (
+        _lazy_plan(name) for name in ('fwd', 'bwd', 'csr_bwd', 'rl_fwd', 'rl_bwd', 'rs_bwd', 'pair_bwd', 'dest_fwd', 'row_fwd', 'row_bwd'))
 
     def __init__(self, fwd, bwd, scale=None, rl_fwd=None, rl_bwd=None, bwd_scaled=False, csr_bwd=None, rs_bwd=None,
                  pair_fwd=None, pair_bwd=None, dest_fwd=None, row_fwd=None, row_bwd=None, row_wave_uniform=False):
@@ -1287,60 +1297,6 @@ class AggGraph(object):
         self.bwd_scaled = bwd_scaled                       # bwd plan's edge weights already carry `scale`
         self.fwd_route = {}                                # sharded layers: timed choice pair form | Y route (ops._fwd_route)
 
-    @property
-    def rs_bwd(self):
-        if callable(self._rs_bwd):
-            self._rs_bwd = self._rs_bwd()
-        return self._rs_bwd
-
-    @property
-    def row_fwd(self):
-        if callable(self._row_fwd):
-            self._row_fwd = self._row_fwd()
-        return self._row_fwd
-
-    @property
-    def row_bwd(self):
-        if callable(self._row_bwd):
-            self._row_bwd = self._row_bwd()
-        return self._row_bwd
-
-    @property
-    def dest_fwd(self):
-        if callable(self._dest_fwd):
-            self._dest_fwd = self._dest_fwd()
-        return self._dest_fwd
-
-    @property
-    def pair_bwd(self):
-        if callable(self._pair_bwd):
-            self._pair_bwd = self._pair_bwd()
-        return self._pair_bwd
-
-    @property
-    def rl_fwd(self):
-        if callable(self._rl_fwd):
-            self._rl_fwd = self._rl_fwd()
-        return self._rl_fwd
-
-    @property
-    def rl_bwd(self):
-        if callable(self._rl_bwd):
-            self._rl_bwd = self._rl_bwd()
-        return self._rl_bwd
-
-    @property
-    def fwd(self):
-        if callable(self._fwd):
-            self._fwd = self._fwd()
-        return self._fwd
-
-    @property
-    def bwd(self):
-        if callable(self._bwd):
-            self._bwd = self._bwd()
-        return self._bwd
-
     def pair_buffers(self, n, nb, d_out, device):
         """(cells C[u, v, b] as [N_pad, N, bases], XB as [N_pad, bases, out] -- a column slice of rows padded to 32)
         of the pair-form forward, N_pad = N
@@ -1365,12 +1321,6 @@ class AggGraph(object):
         if buf is None:
             buf = self._pair_cells[key] = torch.empty((n, d_out, nb), dtype=torch.float32, device=device)
         return buf
-
-    @property
-    def csr_bwd(self):
-        if callable(self._csr_bwd):
-            self._csr_bwd = self._csr_bwd()
-        return self._csr_bwd
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1530,14 +1480,315 @@ def _fwd_route(graph, x, basis, att, pair, shard):
     return choice if pair is not None else 'y'
 
 
+# What `rgcn_route` decides for one pass through an R-GCN layer:
+#   fwd        'pair_sym' | 'pair_dir' | 'pair_gemm' (pair form: cells of att rows, then `tipk_pair_product` on half / all the cells,
+#              or the tiled GEMM), 'rows' | 'dest' (large graphs: `row_products` / `dest_products`), 'rel_gather' | 'Y' (Y = att . XB,
+#              then the LDS-resident gather or `gather_sum`)
+#   pair       the pair plan (`graph.pair_fwd`) of a pair-form pass, else None
+#   pair_bwd   the backward pass is the pair form as well (`pair_grads` on the cells and XB the forward pass leaves with the graph)
+#   xb         where XB of the forward pass lives: 'graph' (the graph's node-major buffer, stamped), 'graph+xbt' (the same, and a
+#              second copy [N, out, bases] for `node_products`), 'own' (a tensor saved for the backward pass)
+#   handover   this layer can finish a pending slab sum of its input in the launch of its own XB (`sum_slabs_xb`)
+#   cells_two  this layer's cell launch can gather the cells of `partner` (the next layer) too (`stream_gather_two`)
+RgcnRoute = collections.namedtuple('RgcnRoute', 'fwd pair pair_bwd xb handover cells_two')
+
+
+def pair_product_on_gemm(nb, d, symmetric, padded):
+    """True where `pair_product` runs on the tiled GEMM instead of `tipk_pair_product` (only the kernel reads mirrored cells)."""
+    return (not lib().tipk_pair_product_supported(nb, d) or switches.on('TIPK_NO_PAIR_PRODUCT') or not padded) and not symmetric
+
+
+def rgcn_route(graph, n, d_in, d_out, nb, r, shard=None, need_grad=True, operands=None, partner=None):
+    """-> RgcnRoute: THE route decision of an R-GCN layer [n, d_in] -> [n, d_out] with `nb` bases and `r` relations on `graph`,
+    from plan attributes, switches and the library's `tipk_*_supported` queries alone (no device needed, nothing launched).
+    `_RGCN.forward` asks once per pass and keeps the answer on its ctx; `encoder.usable` asks the same function.
+
+    operands = (x, basis, att): needed by a relation-sharded layer (`_fwd_route`: in 'timed' mode it times both routes and
+    holds a collective every rank must reach) and with `partner` = (att, graph, d_out[, token]) of the next layer.
+    Plans are built on first use: a lazy plan is only read where the route that is being chosen needs it."""
+    pair = graph.pair_fwd if r > 0 else None
+    if pair is not None and pair.symmetric and not lib().tipk_pair_product_supported(nb, d_out):
+        pair = None                                          # only the dedicated product kernel reads mirrored cells
+    split = stream_gather_split(r, nb) if pair is not None else 0
+    if pair is not None and not (pair.n_table == r and pair.n_rows == n * n and split and (nb // split) // 4 == pair.lanes):
+        pair = None
+    if shard is not None and shard.world > 1:
+        # the pair form's dense product reads the whole N x N cell matrix on EVERY rank (16 us at BioSNAP, whatever
+        # the rank's share of the relations); the Y route (Y = att . XB + unit gather) scales with the share.  One
+        # decision for the whole job, the same from run to run unless timing is asked for; every rank asks, whether or
+        # not it could take the pair form itself (`_fwd_route`: the timed mode's all-reduce is a collective)
+        if _fwd_route(graph, operands[0], operands[1], operands[2], pair, shard) == 'y':
+            pair = None
+    if pair is not None:
+        pair_bwd = bool(need_grad and pair_grads_supported(nb, d_out) and graph.pair_bwd is not None)
+        # (the stream plan of the transposed pass is only read where the backward pass is not the pair form)
+        rs = None if (pair_bwd or not need_grad) else graph.rs_bwd
+        xb = 'graph' if pair_bwd else ('graph+xbt' if (rs is not None and rs.compact is not None) else 'own')
+        on_gemm = pair_product_on_gemm(nb, d_out, pair.symmetric, d_out <= 32)      # (`pair_buffers` pads rows of <= 32 columns)
+        two = partner is not None and shard is None and pair_cells_partner_ok(graph, operands[2], partner[1], partner[0], n)
+        return RgcnRoute('pair_gemm' if on_gemm else ('pair_sym' if pair.symmetric else 'pair_dir'), pair, pair_bwd, xb,
+                         pair_bwd and shard is None and sum_slabs_xb_supported(d_in, d_out), two)
+    fwd, plan = 'Y', None
+    if r > 0:
+        if rel_gather_split(n, d_out, False) > 0 and graph.rl_fwd is not None:      # (the unit plan is built here, on first use)
+            fwd, plan = 'rel_gather', graph.rl_fwd
+        # LARGE node sets (round 5; include/tipk.h sections 2h / 2f): Y = att . XB [R N, out] is never formed -- the (relation,
+        # node) row sums are multiplied where they are assembled, or per destination T[:, v, :] = sum_e att[r_e, :]^T (x) X[src_e]
+        elif _row_plan(graph, False, n, r, nb, d_in) is not None:
+            fwd, plan = 'rows', graph.row_fwd
+        elif graph.dest_fwd is not None:
+            fwd, plan = 'dest', graph.dest_fwd
+        if plan is not None:
+            assert plan.n_nodes == n and plan.n_rel == r, 'graph/plan mismatch'
+        else:                                                                       # (the generic plan is built here, on first use)
+            assert graph.fwd.n_out == n and graph.fwd.n_table == r * n, 'graph/plan mismatch'
+    return RgcnRoute(fwd, None, False, 'own', False, False)
+
+
+def _take_pending(x, handover):
+    """x may be the output of the previous layer with its final slab sum still PENDING (`defer_output`): the consumer then
+    finishes it in the launch that computes its own XB / X root (`sum_slabs_xb`; the pending sum is returned), or -- on any
+    other route -- right here (None is returned)."""
+    pend = x.__dict__.pop('_tipk_pending', None) if hasattr(x, '__dict__') else None
+    if pend is not None and not handover:
+        slabs, scale, addend, relu = pend
+        sum_slabs(slabs, out=x, row_scale=scale, addend=addend, relu=relu)
+        pend = None
+    return pend
+
+
+def _cells_from_partner(graph, cells_token):
+    """True if the previous layer gathered this layer's cells in THIS pass.  The token is an OBJECT the caller made for this
+    forward pass and handed to both layers (FMEncoder.forward) -- not a (pointer, version) pair, which a raw-pointer parameter
+    update (tipk_adam_step does not bump `_version`) would leave looking current."""
+    tok = getattr(graph, 'cells_token', None)
+    graph.cells_token = None
+    return cells_token is not None and tok is not None and tok[0] is cells_token and tok[1] == graph.pair_stamp - 1
+
+
+def _finish_agg(agg, graph, shard, xroot, relu):
+    """out = relu?(agg / deg + X root), after the all-reduce of a shard's partial aggregate."""
+    if shard is not None:
+        shard.all_reduce(agg)
+    return sum_slabs(agg.view(1, *agg.shape), row_scale=graph.scale, addend=xroot, relu=bool(relu))
+
+
+def _rgcn_fwd_pair(route, x, basis, att, root, graph, shard, relu, pend, defer, partner, cells_token):
+    """The pair form: cells of att rows per linked (source, destination) pair, one dense product, the ordered slab sum."""
+    # sum_r A_r X W_r = sum_{(u -> v)} sum_b C[v, u, b] XB_b[u],  C[v, u, :] = sum of att[r, :] over the relations r that link
+    # u -> v.  A BioSNAP drug pair is linked by 66 relations on average, so the per-EDGE work shrinks to adding one att row
+    # (LDS-resident for the whole launch: a wave-stream gather like the transposed pass) and the per-PAIR work is one dense
+    # product -- Y = att . XB [R N, out] (91 MB written and gathered back at layer 1) is never formed.
+    # cells are kept SOURCE-major, C[u, v, :]: the product  sum_u C[u] (N x bases) . XB[u] (bases x out)  then reads
+    # 16 KB contiguous per operand tile (destination-major cells made every tile 128 separate 128-byte rows:
+    # 2.5 TB/s); the u range is padded to a multiple of PAIR_KGROUP with cells / XB rows that stay zero
+    pair = route.pair
+    n = x.shape[0]
+    nb, _, d_out = basis.shape
+    cells, xb_nb, zeros = graph.pair_buffers(n, nb, d_out, x.device)
+    xb = xbt = None
+    if pend is not None:                                 # x itself + XB + X root in ONE launch (layer hand-over)
+        xroot = sum_slabs_xb(pend[0], pend[1], pend[2], pend[3], x, basis, root, xb_nb)
+    elif route.xb == 'own':
+        xb, _, xroot = gemm_group([gemm_job(x, basis), gemm_job(x, basis, out=xb_nb[:n].permute(1, 0, 2)), gemm_job(x, root)])
+    else:
+        # XB is computed ONCE, into the node-major buffer the pair product reads; the backward pass (`pair_grads`, or
+        # `node_products` on the compact dY: a node's 32 rows are one 4-KB block there) takes the same buffer.  It belongs to
+        # the graph and the next forward pass rewrites it: the stamp tells a backward pass that runs after ANOTHER forward
+        # to recompute XB instead of reading someone else's
+        _, xroot = gemm_group([gemm_job(x, basis, out=xb_nb[:n].permute(1, 0, 2)), gemm_job(x, root)])
+        if route.xb == 'graph+xbt':
+            # ... and the pair product, which stages every node's XB block in LDS anyway, writes it back a second time as
+            # [N, out, bases]: what the d att product of the backward pass reads (`node_products` xbt)
+            xbt = graph.xbt_buffer(n, nb, d_out, x.device)
+    if _cells_from_partner(graph, cells_token):
+        pass                                             # this layer's cells were gathered with the previous layer's (below)
+    elif route.cells_two:
+        # the cells depend on the parameters only: the NEXT layer's (same graph, its own att) are gathered in this
+        # launch too -- one launch ramp and one tail instead of two.  The partner's buffers are rewritten: its stamp
+        # moves on, and it is told for which token and stamp its cells are current
+        att2, g2, d_out2 = partner[0].contiguous(), partner[1], partner[2]
+        cells2 = g2.pair_buffers(n, nb, d_out2, x.device)[0]
+        stream_gather_two(pair, att, att2, cells.view(-1, nb)[:n * n], cells2.view(-1, nb)[:n * n])
+        g2.pair_stamp += 1
+        g2.cells_token = (partner[3] if len(partner) > 3 else None, g2.pair_stamp)
+    else:
+        stream_gather(pair, att, write_zeros=False, out=cells.view(-1, nb)[:n * n], label='pair_cells[dd.fwd]', kind=1)
+    slabs = pair_product(cells, xb_nb, symmetric=pair.symmetric, links=getattr(pair, 'links', None), zeros=zeros, xbt=xbt)
+    slabs = slabs.view(-1, n, d_out)
+    if defer:
+        # the ordered slab sum is left to the ONE consumer of this output (the next R-GCN layer, which runs it in the
+        # launch of its own XB product): until then `out` is storage only
+        out = torch.empty((n, d_out), dtype=torch.float32, device=x.device)
+        out._tipk_pending = (slabs, graph.scale, xroot, True)
+    elif shard is None:
+        out = sum_slabs(slabs, row_scale=graph.scale, addend=xroot, relu=bool(relu))
+    else:
+        out = _finish_agg(sum_slabs(slabs), graph, shard, xroot, relu)
+    return out, xb
+
+
+def _rgcn_fwd_large(route, x, basis, att, root, graph, shard, relu):
+    """LARGE node sets: T_b = the att-weighted row sums of X, by (relation, destination) row or per destination, then
+    sum_b T_b basis_b (row sums first: 0.16 TFLOP per layer at config 5 instead of the 0.41 of the per-edge product)."""
+    n = x.shape[0]
+    nb = basis.shape[0]
+    xb, xroot = gemm_group([gemm_job(x, basis), gemm_job(x, root)])      # XB and X root: one grouped launch
+    t_b = row_products(graph.row_fwd, x, att) if route.fwd == 'rows' else dest_products(graph.dest_fwd, x, att)
+    agg = gemm(t_b, basis, reduce_batch=True, kgroup=large_kgroup(n, nb))
+    return _finish_agg(agg, graph, shard, xroot, relu), xb
+
+
+def _rgcn_fwd_y(route, x, basis, att, root, graph, shard, relu):
+    """Y = att . XB [R N, out], then one gather-sum over its rows: the LDS-resident `rel_gather` or the generic `gather_sum`."""
+    n = x.shape[0]
+    nb, _, d_out = basis.shape
+    r = att.shape[0]
+    xb, xroot = gemm_group([gemm_job(x, basis), gemm_job(x, root)])      # XB and X root: one grouped launch
+    y = gemm(att, xb.view(nb, n * d_out)).view(r * n, d_out) if r > 0 else None
+    if route.fwd == 'rel_gather':
+        # LDS-resident gather -> per-workgroup partial slabs; unsharded, the ordered slab sum also applies
+        # 1/deg, adds X root and the ReLU: the layer is finished in one pass
+        part = rel_gather(graph.rl_fwd, y, backward=False, reduce=False)
+        if shard is None:
+            return sum_slabs(part, row_scale=graph.scale, addend=xroot, relu=bool(relu)), xb
+        agg = sum_slabs(part)
+    elif shard is None:
+        agg = gather_sum(graph.fwd, y, row_scale=graph.scale)
+        return sum_slabs(agg.view(1, n, d_out), addend=xroot, relu=bool(relu)), xb
+    elif r == 0:
+        agg = torch.zeros((n, d_out), dtype=torch.float32, device=x.device)
+    else:
+        agg = gather_sum(graph.fwd, y)
+    # partial aggregate of this rank's relations -> one all-reduce -> 1/deg(global), + X root, ReLU
+    return _finish_agg(agg, graph, shard, xroot, relu), xb
+
+
+def _rgcn_grad_att_xb(ctx, x, basis, att, xb, g):
+    """(d att, dXB [bases, N, out]) of the pass `ctx` describes; d att is the finished tensor, or a slab job whose ordered sum
+    rides in the dense tail's grouped slab sum.  What depends on the state the backward pass finds -- the graph's stamp, the
+    layout of the operands -- is decided here."""
+    graph = ctx.graph
+    n = x.shape[0]
+    nb, _, d_out = basis.shape
+    r = att.shape[0]
+    if r == 0:
+        return (torch.zeros((0, nb), dtype=torch.float32, device=x.device),
+                torch.zeros((nb, n, d_out), dtype=torch.float32, device=x.device))
+    xbt = None
+    if ctx.route.pair_bwd:
+        cells, xb_nb, _ = graph.pair_buffers(n, nb, d_out, x.device)
+        if graph.pair_stamp != ctx.xb_stamp:
+            # another forward pass has rewritten the graph's buffers: the same values again -- and a new stamp, so that
+            # THAT pass's backward pass recomputes its own as well
+            gemm(x, basis, out=xb_nb[:n].permute(1, 0, 2))
+            stream_gather(graph.pair_fwd, att, write_zeros=False, out=cells.view(-1, nb)[:n * n], label='pair_cells[dd.fwd]', kind=1)
+            graph.pair_stamp += 1
+            ctx.xb_stamp = graph.pair_stamp
+        return pair_backward(graph.pair_bwd, cells, xb_nb, g)
+    if ctx.xb_stamp is not None:                                     # XB lives in the graph's node-major buffer (forward)
+        if graph.pair_stamp == ctx.xb_stamp:
+            xb = graph.pair_buffers(n, nb, d_out, x.device)[1][:n].permute(1, 0, 2)
+            xbt = graph.xbt_buffer(n, nb, d_out, x.device)
+        else:                                                        # another forward pass has rewritten it: same values again
+            xb = gemm(x, basis)
+    xb2 = xb.view(nb, n * d_out) if xb.is_contiguous() else None
+    rs = graph.rs_bwd
+    used = None
+    if rs is not None and rs.compact is not None:
+        assert rel_stream_split(n, d_out) and (d_out // rel_stream_split(n, d_out)) // 4 == rs.lanes and rs.n_rel == r
+        # dY_r = A_r^T (D^-1 g) in COMPACT node-major form: only the (relation, source) rows that have an edge
+        # exist; both products of dY run on that form (d XB complete, d att as a few small slabs)
+        dyc = rel_stream_bwd(rs, g, row_scale=graph.scale)
+        return node_products(dyc, rs.compact, att, xb, xbt)
+    if rs is not None and rel_stream_split(n, d_out) and (d_out // rel_stream_split(n, d_out)) // 4 == rs.lanes:
+        # dY_r = A_r^T (D^-1 g), 1/deg fused.  Rows (relation, node) without edges -- half of them -- are
+        # neither written here nor read as data by the fused products (row mask)
+        masked = dy_products_fused(r, n * d_out, nb) and xb.stride(-1) == 1
+        g_y = rel_stream_bwd(rs, g, row_scale=graph.scale, write_zeros=not masked)
+        used = rs.row_used if masked else None
+    elif rel_gather_usable(graph.rl_bwd, n, d_out, True):
+        g_y = rel_gather(graph.rl_bwd, g, backward=True, row_scale=graph.scale)
+    elif xb2 is not None and n * d_out * 4 < 2 ** 31 and _row_plan(graph, True, n, r, nb, d_out) is not None:
+        # LARGE node sets: dY = A_r^T (D^-1 g') is never written -- its rows are summed in LDS and multiplied there
+        gs = rows_affine(g, row_mul=graph.scale)
+        j_rows, g_xb = row_products(graph.row_bwd, gs, att, xb2)
+        gemm_group([], [j_rows])                                     # (thousands of slabs: a slab sum of its own, as dy_products')
+        return j_rows.out, g_xb
+    else:
+        gs = rows_affine(g, row_mul=graph.scale)
+        csr = graph.csr_bwd if (d_out % 4 == 0 and 8 <= d_out <= 256 and gs.numel() * 4 < 2 ** 32) else None   # (32-bit row offsets)
+        # R N short rows: contiguous streams, no descriptors -- else the generic transposed gather
+        g_y = gather_rows_csr(csr, gs) if csr is not None else gather_sum(graph.bwd, gs)
+    # both consumers of dY in one pass over it (+ one grouped slab sum)
+    g_att, g_xb = dy_products(g_y.view(r, n * d_out), att, xb2, used, n)
+    return g_att, g_xb.view(nb, n, d_out)
+
+
+def rgcn_dense_tail(x, basis, root, g, g_xb, gate_x, slab_jobs, shard=None):
+    """(dX, d basis, d root) of an R-GCN layer given dXB [bases, N, d_out] and g [N, d_out] (1/deg not applied to the root
+    term); gate_x: dX is masked with (gate_x > 0); slab_jobs: pending ordered slab sums (d att) that ride along."""
+    # d basis, d root and both halves of dX are independent given dXB and g: one grouped launch.  When the reductions
+    # fit the waves of one workgroup per output tile (BioSNAP: 645 and 1 056 terms) the products are FINISHED by that
+    # launch, together with the d att slab sum (round 4: 10.4 + 7.6 us of split-K slabs + their sum per layer before);
+    # otherwise grouped split-K products.  With a `shard`, [partial dX | partial d basis] live in ONE flat buffer the
+    # products write into: a single all-reduce, no pack / unpack copies; d att (this rank's rows) and d root (replicated
+    # operands: identical on every rank) need no collective
+    n, d_in = x.shape
+    nb, _, d_out = basis.shape
+    slab_jobs = list(slab_jobs)
+    flat = x_out = b_out = None
+    if shard is not None:
+        flat = torch.empty(n * d_in + nb * d_in * d_out, dtype=torch.float32, device=x.device)
+        x_out, b_out = flat[:n * d_in].view(n, d_in), flat[n * d_in:].view(nb, d_in, d_out)
+    jobs = None
+    if len(slab_jobs) <= _lib.WG_SUMS_MAX:
+        jobs = [wg_gemm_job(x.t(), g_xb, out=b_out), wg_gemm_job(x.t(), g)]
+        if shard is None:
+            jobs.append(wg_gemm_job(g_xb, basis.transpose(1, 2), reduce_batch=True, a2=g, b2=root.t(), gate=gate_x))
+        else:
+            jobs.append(wg_gemm_job(g_xb, basis.transpose(1, 2), reduce_batch=True, out=x_out))
+    if jobs is not None and None not in jobs:
+        wg_gemm_group(jobs, slab_jobs)
+        j_basis, j_root, g_x = jobs[0], jobs[1], jobs[2].out
+    else:
+        j_root = gemm_job(x.t(), g)
+        j_basis = gemm_job(x.t(), g_xb, out=b_out)                       # [B, in, out]
+        if shard is None:
+            j_xr = gemm_job(g, root.t(), ksplit=1)                       # written by the GEMM launch itself: the
+            g_x = j_xr.out                                               # basis half is summed on top of it afterwards
+            j_xq = gemm_job(g_xb, basis.transpose(1, 2), out=g_x, c_in=g_x, reduce_batch=True, kgroup=large_kgroup(n, nb))
+            if j_xq.slabs is not None:                                   # summed on top of g root^T afterwards
+                j_xq.gate = gate_x                                       # ... and masked with (x > 0) in the same pass
+                gemm_group([j_basis, j_root, j_xr, j_xq], slab_jobs)
+            else:                                                        # reads g_x while accumulating
+                gemm_group([j_basis, j_root, j_xr], slab_jobs)
+                gemm_group([j_xq])
+                if gate_x is not None:
+                    g_x = rows_affine(g_x, gate=gate_x)
+        else:
+            g_x = x_out
+            j_xq = gemm_job(g_xb, basis.transpose(1, 2), out=g_x, reduce_batch=True, kgroup=large_kgroup(n, nb))   # partial over this shard
+            gemm_group([j_basis, j_root, j_xq], slab_jobs)
+    if shard is not None:
+        shard.all_reduce(flat)
+        g_x = gemm(g, root.t(), out=g_x, c_in=g_x)                       # replicated term, added once
+        if gate_x is not None:
+            g_x = rows_affine(g_x, gate=gate_x)
+    return g_x, j_basis.out, j_root.out
+
+
 class _RGCN(torch.autograd.Function):
     """One basis-decomposed R-GCN layer with global-mean aggregation
     (reference MyRGCNConv2 / MyRGCNConv, src/layers.py:102-193 / :21-99):
 
         out = D^-1 sum_r A_r X W_r + X root,   W_r = sum_b att[r,b] basis[b]
 
-    evaluated basis-first / transform-then-gather: XB_b = X basis_b, Y = att . XB, then one
-    gather-sum over the rows of Y (no E x d intermediates).
+    evaluated basis-first / transform-then-gather: XB_b = X basis_b, then the aggregate on the route `rgcn_route` names --
+    the pair form, the row sums of large graphs, or Y = att . XB and one gather-sum over the rows of Y (no E x d
+    intermediates) -- each route a function of its own (`_rgcn_fwd_pair`, `_rgcn_fwd_large`, `_rgcn_fwd_y`).  The route is
+    decided ONCE per pass and kept on the ctx; the backward pass is `_rgcn_grad_att_xb` (d att, dXB on the matching route;
+    what depends on the graph's stamp or the operands' layout is decided there) and `rgcn_dense_tail` (dX, d basis, d root).
 
     With a `shard` (tip_amd/dist.py) the graph, `att` and its gradient hold only this rank's relations
     (`graph.scale` = 1 / GLOBAL in-degree): the partial aggregate is all-reduced before the 1/deg
@@ -1553,275 +1804,35 @@ class _RGCN(torch.autograd.Function):
         x, basis, att, root = _f32c(x), basis.contiguous(), att.contiguous(), root.contiguous()
         n, d_in = x.shape
         nb, _, d_out = basis.shape
-        r = att.shape[0]
-        # x may be the output of the previous layer with its final slab sum still PENDING (`defer_output`): this layer then
-        # finishes it in the launch that computes its own XB / X root (`sum_slabs_xb`), or right here if it takes another route
-        pend = x.__dict__.pop('_tipk_pending', None) if hasattr(x, '__dict__') else None
-        pair = graph.pair_fwd if r > 0 else None
-        if pair is not None and pair.symmetric and not lib().tipk_pair_product_supported(nb, d_out):
-            pair = None                                      # only the dedicated product kernel reads mirrored cells
-        if pair is not None and not (pair.n_table == r and pair.n_rows == n * n and stream_gather_split(r, nb)
-                                     and (nb // stream_gather_split(r, nb)) // 4 == pair.lanes):
-            pair = None
-        if shard is not None and shard.world > 1:
-            # the pair form's dense product reads the whole N x N cell matrix on EVERY rank (16 us at BioSNAP, whatever
-            # the rank's share of the relations); the Y route (Y = att . XB + unit gather) scales with the share.  One
-            # decision for the whole job, the same from run to run unless timing is asked for; every rank asks, whether or
-            # not it could take the pair form itself (`_fwd_route`: the timed mode's all-reduce is a collective)
-            if _fwd_route(graph, x, basis, att, pair, shard) == 'y':
-                pair = None
-        if pend is not None and not (pair is not None and shard is None and any(ctx.needs_input_grad[:3]) and pair_grads_supported(nb, d_out)
-                                     and graph.pair_bwd is not None and sum_slabs_xb_supported(d_in, d_out)):
-            _finish_pending(x, pend)
-            pend = None
-        if pair is not None:
-            # PAIR FORM.  sum_r A_r X W_r = sum_{(u -> v)} sum_b C[v, u, b] XB_b[u],  C[v, u, :] = sum of att[r, :] over
-            # the relations r that link u -> v.  A BioSNAP drug pair is linked by 66 relations on average, so the
-            # per-EDGE work shrinks to adding one att row (LDS-resident for the whole launch: a wave-stream gather
-            # like the transposed pass) and the per-PAIR work is one dense product -- Y = att . XB [R N, out]
-            # (91 MB written and gathered back at layer 1) is never formed.
-            # cells are kept SOURCE-major, C[u, v, :]: the product  sum_u C[u] (N x bases) . XB[u] (bases x out)  then reads
-            # 16 KB contiguous per operand tile (destination-major cells made every tile 128 separate 128-byte rows:
-            # 2.5 TB/s); the u range is padded to a multiple of PAIR_KGROUP with cells / XB rows that stay zero
-            cells, xb_nb, zeros = graph.pair_buffers(n, nb, d_out, x.device)
-            need_grad = any(ctx.needs_input_grad[:3])
-            ctx.pair_bwd = need_grad and pair_grads_supported(nb, d_out) and graph.pair_bwd is not None
-            rs = None if (ctx.pair_bwd or not need_grad) else graph.rs_bwd
+        route = rgcn_route(graph, n, d_in, d_out, nb, att.shape[0], shard, any(ctx.needs_input_grad[:3]), (x, basis, att), partner)
+        pend = _take_pending(x, route.handover)
+        ctx.xb_stamp = None
+        if route.pair is not None:
             # every pass through here rewrites the graph's cell / XB buffers: a backward pass that finds another stamp than
             # its own forward pass left knows they are no longer its operands
             graph.pair_stamp += 1
-            if ctx.pair_bwd:
-                # PAIR-FORM BACKWARD (round 5; include/tipk.h section 2e): the backward pass reads the cells and the node-major
-                # XB this pass leaves in the graph's buffers -- nothing else is saved, nothing is transposed
-                if pend is not None:                         # x itself + XB + X root in ONE launch (layer hand-over)
-                    xroot = sum_slabs_xb(pend[0], pend[1], pend[2], pend[3], x, basis, root, xb_nb)
-                    pend = None
-                else:
-                    _, xroot = gemm_group([gemm_job(x, basis, out=xb_nb[:n].permute(1, 0, 2)), gemm_job(x, root)])
-                xb, xbt = None, None
+            if route.xb != 'own':
                 ctx.xb_stamp = graph.pair_stamp
-            elif rs is not None and rs.compact is not None:
-                # XB is computed ONCE, into the node-major buffer the pair product reads; the backward pass
-                # (`node_products` on the compact dY) takes the same buffer through strides -- a node's 32 rows are one
-                # 4-KB block there.  The buffer belongs to the graph and the next forward pass rewrites it: the stamp tells
-                # a backward pass that runs after ANOTHER forward to recompute XB instead of reading someone else's.
-                _, xroot = gemm_group([gemm_job(x, basis, out=xb_nb[:n].permute(1, 0, 2)), gemm_job(x, root)])
-                # ... and the pair product, which stages every node's XB block in LDS anyway, writes it back a second time as
-                # [N, out, bases]: what the d att product of the backward pass reads (`node_products` xbt)
-                xbt = graph.xbt_buffer(n, nb, d_out, x.device)
-                xb = xb_nb[:n].permute(1, 0, 2)
-                ctx.xb_stamp = graph.pair_stamp
-            else:
-                xb, _, xroot = gemm_group([gemm_job(x, basis), gemm_job(x, basis, out=xb_nb[:n].permute(1, 0, 2)), gemm_job(x, root)])
-                ctx.xb_stamp, xbt = None, None
-            # the token is an OBJECT the caller made for this forward pass and handed to both layers (FMEncoder.forward): it says
-            # "the previous layer gathered your cells in THIS pass" -- not a (pointer, version) pair, which a raw-pointer parameter
-            # update (tipk_adam_step does not bump `_version`) would leave looking current
-            tok = getattr(graph, 'cells_token', None)
-            graph.cells_token = None
-            if cells_token is not None and tok is not None and tok[0] is cells_token and tok[1] == graph.pair_stamp - 1:
-                pass                                         # this layer's cells were gathered with the previous layer's (below)
-            elif partner is not None and shard is None and pair_cells_partner_ok(graph, att, partner[1], partner[0], n):
-                # the cells depend on the parameters only: the NEXT layer's (same graph, its own att) are gathered in this
-                # launch too -- one launch ramp and one tail instead of two.  The partner's buffers are rewritten: its stamp
-                # moves on, and it is told for which att (object, version) and stamp its cells are current
-                att2, g2, d_out2 = partner[0].contiguous(), partner[1], partner[2]
-                cells2 = g2.pair_buffers(n, nb, d_out2, x.device)[0]
-                stream_gather_two(pair, att, att2, cells.view(-1, nb)[:n * n], cells2.view(-1, nb)[:n * n])
-                g2.pair_stamp += 1
-                g2.cells_token = (partner[3] if len(partner) > 3 else None, g2.pair_stamp)
-            else:
-                stream_gather(pair, att, write_zeros=False, out=cells.view(-1, nb)[:n * n], label='pair_cells[dd.fwd]', kind=1)
-            slabs = pair_product(cells, xb_nb, symmetric=pair.symmetric, links=getattr(pair, 'links', None), zeros=zeros, xbt=xbt)
-            if shard is None and defer_output and relu == 'gated_downstream' and d_out == 32:
-                # the ordered slab sum is left to the ONE consumer of this output (the next R-GCN layer, which runs it in the
-                # launch of its own XB product): until then `out` is storage only
-                out = torch.empty((n, d_out), dtype=torch.float32, device=x.device)
-                out._tipk_pending = (slabs.view(-1, n, d_out), graph.scale, xroot, True)
-            elif shard is None:
-                out = sum_slabs(slabs.view(-1, n, d_out), row_scale=graph.scale, addend=xroot, relu=bool(relu))
-            else:
-                agg = sum_slabs(slabs.view(-1, n, d_out))
-                shard.all_reduce(agg)
-                out = sum_slabs(agg.view(1, n, d_out), row_scale=graph.scale, addend=xroot, relu=bool(relu))
-            ctx.graph, ctx.shard, ctx.relu, ctx.gate_input = graph, shard, relu, gate_input
-            ctx.save_for_backward(x, basis, att, root, xb if ctx.xb_stamp is None else None, out if relu is True else None)
-            return out
-        ctx.xb_stamp, ctx.pair_bwd = None, False
-        use_rl = r > 0 and rel_gather_usable(graph.rl_fwd, n, d_out, False)   # (the unit plan is built here, on first use)
-        # LARGE node sets (round 5; include/tipk.h sections 2h / 2f): Y = att . XB [R N, out] is never formed -- the (relation,
-        # node) row sums are multiplied where they are assembled, or per destination T[:, v, :] = sum_e att[r_e, :]^T (x) X[src_e]
-        # (a product over the node's incoming edges); then sum_b T_b basis_b
-        rows = _row_plan(graph, False, n, r, nb, d_in) if (r > 0 and not use_rl) else None
-        dest = graph.dest_fwd if (r > 0 and not use_rl and rows is None) else None
-        if use_rl:
-            assert graph.rl_fwd.n_nodes == n and graph.rl_fwd.n_rel == r, 'graph/plan mismatch'
-        elif rows is not None:
-            assert rows.n_nodes == n and rows.n_rel == r, 'graph/plan mismatch'
-        elif r > 0 and dest is None:                                         # (the generic plan is built here, on first use)
-            assert graph.fwd.n_out == n and graph.fwd.n_table == r * n, 'graph/plan mismatch'
-        xb, xroot = gemm_group([gemm_job(x, basis), gemm_job(x, root)])      # XB and X root: one grouped launch
-        if dest is not None or rows is not None:
-            # (row sums first: 0.16 TFLOP per layer at config 5 instead of the 0.41 of the per-edge product)
-            t_b = row_products(rows, x, att) if rows is not None else dest_products(dest, x, att)
-            agg = gemm(t_b, basis, reduce_batch=True, kgroup=large_kgroup(n, nb))
-            if shard is not None:
-                shard.all_reduce(agg)
-            out = sum_slabs(agg.view(1, n, d_out), row_scale=graph.scale, addend=xroot, relu=bool(relu))
-            ctx.graph, ctx.shard, ctx.relu, ctx.gate_input = graph, shard, relu, gate_input
-            ctx.save_for_backward(x, basis, att, root, xb, out if relu is True else None)
-            return out
-        y = gemm(att, xb.view(nb, n * d_out)).view(r * n, d_out) if r > 0 else None     # [R N, out]
-        if shard is None:
-            if use_rl:
-                # LDS-resident gather -> per-workgroup partial slabs; the ordered slab sum also applies
-                # 1/deg, adds X root and the ReLU: the layer is finished in one pass
-                part = rel_gather(graph.rl_fwd, y, backward=False, reduce=False)
-                out = sum_slabs(part, row_scale=graph.scale, addend=xroot, relu=bool(relu))
-            else:
-                agg = gather_sum(graph.fwd, y, row_scale=graph.scale)
-                out = sum_slabs(agg.view(1, n, d_out), addend=xroot, relu=bool(relu))
+            defer = shard is None and defer_output and relu == 'gated_downstream' and d_out == 32
+            out, xb = _rgcn_fwd_pair(route, x, basis, att, root, graph, shard, relu, pend, defer, partner, cells_token)
         else:
-            # partial aggregate of this rank's relations -> one all-reduce -> 1/deg(global), + X root, ReLU
-            if r == 0:
-                agg = torch.zeros((n, d_out), dtype=torch.float32, device=x.device)
-            elif use_rl:
-                agg = sum_slabs(rel_gather(graph.rl_fwd, y, backward=False, reduce=False))
-            else:
-                agg = gather_sum(graph.fwd, y)
-            shard.all_reduce(agg)
-            out = sum_slabs(agg.view(1, n, d_out), row_scale=graph.scale, addend=xroot, relu=bool(relu))
-        del y
-        ctx.graph, ctx.shard, ctx.relu, ctx.gate_input = graph, shard, relu, gate_input
+            fwd = _rgcn_fwd_large if route.fwd in ('rows', 'dest') else _rgcn_fwd_y
+            out, xb = fwd(route, x, basis, att, root, graph, shard, relu)
+        ctx.route, ctx.graph, ctx.shard, ctx.relu, ctx.gate_input = route, graph, shard, relu, gate_input
         ctx.save_for_backward(x, basis, att, root, xb, out if relu is True else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, basis, att, root, xb, out = ctx.saved_tensors
-        graph, shard = ctx.graph, ctx.shard
         g = _f32c(g).contiguous()
         if ctx.relu is True:
             g = rows_affine(g, gate=out)                                 # ReLU gate of the fused epilogue
-        n, d_in = x.shape
-        nb, _, d_out = basis.shape
-        r = att.shape[0]
-        xbt = None
-        j_att = None
-        if ctx.pair_bwd and r > 0:
-            cells, xb_nb, _ = graph.pair_buffers(n, nb, d_out, x.device)
-            if graph.pair_stamp != ctx.xb_stamp:
-                # another forward pass has rewritten the graph's buffers: the same values again -- and a new stamp, so that
-                # THAT pass's backward pass recomputes its own as well
-                pair = graph.pair_fwd
-                gemm(x, basis, out=xb_nb[:n].permute(1, 0, 2))
-                stream_gather(pair, att, write_zeros=False, out=cells.view(-1, nb)[:n * n], label='pair_cells[dd.fwd]', kind=1)
-                graph.pair_stamp += 1
-                ctx.xb_stamp = graph.pair_stamp
-            j_att, g_xb = pair_backward(graph.pair_bwd, cells, xb_nb, g)
-        elif ctx.xb_stamp is not None:                                   # XB lives in the graph's node-major buffer (forward)
-            if graph.pair_stamp == ctx.xb_stamp:
-                xb = graph.pair_buffers(n, nb, d_out, x.device)[1][:n].permute(1, 0, 2)
-                xbt = graph.xbt_buffer(n, nb, d_out, x.device)
-            else:                                                        # another forward pass has rewritten it: same values again
-                xb = gemm(x, basis)
-        xb2 = xb.view(nb, n * d_out) if (xb is not None and xb.is_contiguous()) else None
-        if j_att is not None:
-            pass
-        elif r > 0:
-            rs = graph.rs_bwd
-            used = None
-            if rs is not None and rs.compact is not None:
-                assert rel_stream_split(n, d_out) and (d_out // rel_stream_split(n, d_out)) // 4 == rs.lanes and rs.n_rel == r
-                # dY_r = A_r^T (D^-1 g) in COMPACT node-major form: only the (relation, source) rows that have an edge
-                # exist; both products of dY run on that form (d XB complete, d att as a few small slabs)
-                dyc = rel_stream_bwd(rs, g, row_scale=graph.scale)
-                j_att, g_xb = node_products(dyc, rs.compact, att, xb, xbt)
-            elif rs is not None and rel_stream_split(n, d_out) and (d_out // rel_stream_split(n, d_out)) // 4 == rs.lanes:
-                # dY_r = A_r^T (D^-1 g), 1/deg fused.  Rows (relation, node) without edges -- half of them -- are
-                # neither written here nor read as data by the fused products (row mask)
-                masked = dy_products_fused(r, n * d_out, nb) and xb.stride(-1) == 1
-                g_y = rel_stream_bwd(rs, g, row_scale=graph.scale, write_zeros=not masked).view(r, n * d_out)
-                used = rs.row_used if masked else None
-            elif rel_gather_usable(graph.rl_bwd, n, d_out, True):
-                g_y = rel_gather(graph.rl_bwd, g, backward=True, row_scale=graph.scale).view(r, n * d_out)
-            elif xb2 is not None and n * d_out * 4 < 2 ** 31 and _row_plan(graph, True, n, r, nb, d_out) is not None:
-                # LARGE node sets: dY = A_r^T (D^-1 g') is never written -- its rows are summed in LDS and multiplied there
-                gs = rows_affine(g, row_mul=graph.scale)
-                j_rows, g_xb = row_products(graph.row_bwd, gs, att, xb2)
-                gemm_group([], [j_rows])                                 # (thousands of slabs: a slab sum of its own, as dy_products')
-                g_att, g_y = j_rows.out, None
-            else:
-                gs = rows_affine(g, row_mul=graph.scale)
-                csr = graph.csr_bwd if (d_out % 4 == 0 and 8 <= d_out <= 256 and gs.numel() * 4 < 2 ** 32) else None   # (32-bit row offsets)
-                if csr is not None:                                      # R N short rows: contiguous streams, no descriptors
-                    g_y = gather_rows_csr(csr, gs).view(r, n * d_out)
-                else:
-                    g_y = gather_sum(graph.bwd, gs).view(r, n * d_out)
-            if j_att is None and g_y is not None:
-                # both consumers of dY in one pass over it (+ one grouped slab sum)
-                g_att, g_xb = dy_products(g_y, att, xb2, used, n)
-                g_xb = g_xb.view(nb, n, d_out)
-        else:
-            g_att = torch.zeros((0, nb), dtype=torch.float32, device=x.device)
-            g_xb = torch.zeros((nb, n, d_out), dtype=torch.float32, device=x.device)
-        extra = [] if j_att is None else [j_att]                         # the d att slabs ride in this layer's grouped slab sum
-        if j_att is not None:
-            g_att = j_att.out
-        # d basis, d root and both halves of dX are independent given dXB and g: one grouped launch.  When the reductions
-        # fit the waves of one workgroup per output tile (BioSNAP: 645 and 1 056 terms) the products are FINISHED by that
-        # launch, together with the d att slab sum (round 4: 10.4 + 7.6 us of split-K slabs + their sum per layer before)
-        if len(extra) <= _lib.WG_SUMS_MAX:
-            flat = None
-            if shard is not None:
-                flat = torch.empty(n * d_in + nb * d_in * d_out, dtype=torch.float32, device=x.device)
-            w_basis = wg_gemm_job(x.t(), g_xb, out=None if flat is None else flat[n * d_in:].view(nb, d_in, d_out))
-            w_root = wg_gemm_job(x.t(), g)
-            if shard is None:
-                w_x = wg_gemm_job(g_xb, basis.transpose(1, 2), reduce_batch=True, a2=g, b2=root.t(),
-                                  gate=x if ctx.gate_input else None)
-            else:
-                w_x = wg_gemm_job(g_xb, basis.transpose(1, 2), reduce_batch=True, out=flat[:n * d_in].view(n, d_in))
-            if w_basis is not None and w_root is not None and w_x is not None:
-                wg_gemm_group([w_basis, w_root, w_x], extra)
-                g_x = w_x.out
-                if shard is not None:
-                    shard.all_reduce(flat)
-                    g_x = gemm(g, root.t(), out=g_x, c_in=g_x)           # replicated term, added once
-                    if ctx.gate_input:
-                        g_x = rows_affine(g_x, gate=x)
-                return g_x, w_basis.out, g_att, w_root.out, None, None, None, None, None, None, None
-        j_root = gemm_job(x.t(), g)
-        if shard is None:
-            j_basis = gemm_job(x.t(), g_xb)                              # [B, in, out]
-            j_xr = gemm_job(g, root.t(), ksplit=1)                       # written by the GEMM launch itself: the
-            g_x = j_xr.out                                               # basis half is summed on top of it afterwards
-            j_xq = gemm_job(g_xb, basis.transpose(1, 2), out=g_x, c_in=g_x, reduce_batch=True, kgroup=large_kgroup(n, nb))
-            if j_xq.slabs is not None:                                   # summed on top of g root^T afterwards
-                if ctx.gate_input:
-                    j_xq.gate = x                                        # ... and masked with (x > 0) in the same pass
-                gemm_group([j_basis, j_root, j_xr, j_xq], extra)
-            else:                                                        # reads g_x while accumulating
-                gemm_group([j_basis, j_root, j_xr], extra)
-                gemm_group([j_xq])
-                if ctx.gate_input:
-                    g_x = rows_affine(g_x, gate=x)
-            g_basis, g_root = j_basis.out, j_root.out
-        else:
-            # [partial dX | partial d basis] live in ONE flat buffer the products write into: a single
-            # all-reduce, no pack / unpack copies; d att (this rank's rows) and d root (replicated
-            # operands: identical on every rank) need no collective
-            flat = torch.empty(n * d_in + nb * d_in * d_out, dtype=torch.float32, device=x.device)
-            g_x = flat[:n * d_in].view(n, d_in)
-            g_basis = flat[n * d_in:].view(nb, d_in, d_out)
-            j_basis = gemm_job(x.t(), g_xb, out=g_basis)
-            j_xq = gemm_job(g_xb, basis.transpose(1, 2), out=g_x, reduce_batch=True, kgroup=large_kgroup(n, nb))   # partial over this shard
-            gemm_group([j_basis, j_root, j_xq], extra)
-            g_root = j_root.out
-            shard.all_reduce(flat)
-            g_x = gemm(g, root.t(), out=g_x, c_in=g_x)                   # replicated term, added once
-            if ctx.gate_input:
-                g_x = rows_affine(g_x, gate=x)
+        g_att, g_xb = _rgcn_grad_att_xb(ctx, x, basis, att, xb, g)
+        pending = [] if torch.is_tensor(g_att) else [g_att]              # the d att slabs ride in the tail's grouped slab sum
+        g_x, g_basis, g_root = rgcn_dense_tail(x, basis, root, g, g_xb, x if ctx.gate_input else None, pending, ctx.shard)
+        if pending:
+            g_att = g_att.out
         return g_x, g_basis, g_att, g_root, None, None, None, None, None, None, None
 
 
