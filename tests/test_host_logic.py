@@ -196,6 +196,114 @@ def test_library_exports_every_declared_symbol():
     assert L.tipk_strerror(0) == b'ok' and b'invalid' in L.tipk_strerror(-1)
 
 
+_I, _L, _F, _D, _U, _P, _S = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p,
+                              ctypes.c_char_p)
+
+
+def test_binding_reads_the_header_by_its_type_rules():
+    """Signatures typed here from include/tipk.h by hand, one for every rule of the reader: the derived table cannot be wrong entry
+    by entry, but the reader could be wrong as a whole."""
+    slab, wg = ctypes.POINTER(_lib.SlabSumDesc), ctypes.POINTER(_lib.WgGemmDesc)
+    want = {
+        'tipk_strerror': (_S, [_I]),                                                       # const char* result
+        'tipk_sum_slabs': (_I, [_P, _L, _L, _L, _F, _I, _P, _P]),                          # float among ints
+        'tipk_adam_step': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _D, _P]),  # float* const*, uint64_t* const*, double
+        'tipk_device_info': (_I, [_I, _P, _P, _P, _S, _I]),                                # int*, char*
+        'tipk_gemm_wg_group': (_I, [wg, ctypes.c_int32, slab, ctypes.c_int32, _P]),        # pointers to structs with a body, int32_t
+        'tipk_rgcn_row_products_slabs': (_L, [_L, _I]),                                    # int64_t result
+        'tipk_host_plan_free': (None, [_P]),                                               # void result, opaque handle
+        'tipk_stream_gather_piece': (_I, []),                                              # (void)
+        'tipk_gather_sum_riders': (_I, [_P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, slab,
+                                        ctypes.c_int32, _P]),                              # const struct x* before the body of x
+        'tipk_typed_negative_sampling': (_I, [_P, _P, _L, _L, _U, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _P]),   # uint64_t by value
+    }
+    for name, sig in want.items():
+        assert _lib.SIGNATURES[name] == sig, name
+
+
+def test_binding_structs_have_the_layout_of_the_header():
+    """Sizes and offsets worked out by hand from the struct bodies of include/tipk.h under the LP64 rules (8-byte pointers and
+    int64_t, 4-byte int and float, members aligned to their size, the struct to its widest member)."""
+    p8 = ['embed', 'pp_w1', 'pp_b1', 'pp_w2', 'pp_b2', 'hgcn_w', 'basis1', 'att1', 'root1', 'basis2', 'att2', 'root2']
+    want = {
+        'GemmDesc': (192, ['m', 'n', 'k', 'batch', 'kbatch', 'ksplit', 'a', 'a_sm', 'a_sk', 'a_sq', 'a_sz', 'b', 'b_sk', 'b_sn', 'b_sq',
+                           'b_sz', 'c', 'c_sm', 'c_sz', 'c_ss', 'c_in', 'cin_sm', 'cin_sz', ('alpha', 184, 4), ('relu', 188, 4)]),
+        'SlabSumDesc': (88, ['in_', 'n_slabs', 'slab_stride', 'count', ('alpha', 32, 4), ('accumulate', 36, 4), ('row_scale', 40, 8),
+                             ('cols', 48, 8), ('addend', 56, 8), ('relu', 64, 4), ('gate', 72, 8), ('out', 80, 8)]),
+        'WgGemmDesc': (272, [('p', 0, 192), ('a2', 192, 8), ('a2_sm', 200, 8), ('a2_sk', 208, 8), ('b2', 216, 8), ('b2_sk', 224, 8),
+                             ('b2_sn', 232, 8), ('k2', 240, 8), ('gate', 248, 8), ('gate_sm', 256, 8), ('gate_sz', 264, 8)]),
+        'EncoderDims': (24, [(n, 4 * i, 4) for i, n in enumerate(['n_embed', 'prot_drug_dim', 'n_hid1', 'n_hid2', 'num_base', 'cat'])]),
+        'EncoderParams': (104, p8 + [('lin_layout', 96, 4)]),
+        'EncoderGrads': (96, p8),
+    }
+    for name, (size, fields) in want.items():
+        cls = getattr(_lib, name)
+        fields = [f if isinstance(f, tuple) else (f, 8 * i, 8) for i, f in enumerate(fields)]      # a bare name: i-th 8-byte member
+        assert cls.__name__ == name and ctypes.sizeof(cls) == size, name
+        assert [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, _ in cls._fields_] == fields, name
+    assert _lib.WgGemmDesc._fields_[0][1] is _lib.GemmDesc
+    assert _lib.ENCODER_PARAMS == tuple(p8)
+    assert (_lib.GROUP_MAX, _lib.WG_GEMM_MAX, _lib.WG_SUMS_MAX, _lib.ENCODER_FROM_FWD) == (6, 4, 3, 1)
+
+
+def test_header_reader_on_a_small_header():
+    constants, structs, sigs = _lib.read_header('''
+        #ifndef TIPK_H
+        #define TIPK_H
+        #define TIPK_EINVAL (-1)     /* a comment with a ; and a ( in it */
+        #define TIPK_MAX 6
+        typedef void* tipk_stream_t;
+        struct tipk_late;
+        typedef struct tipk_handle tipk_handle;
+        typedef struct tipk_inner { const float* in; int64_t a, b; int relu; } tipk_inner;
+        typedef struct tipk_outer { tipk_inner p; float alpha; } tipk_outer;
+        int64_t tipk_f(const struct tipk_late* x /* host */, tipk_handle** out,
+                       const tipk_outer* d, tipk_stream_t stream);
+        typedef struct tipk_late { double v; } tipk_late;
+        #endif
+    ''')
+    assert constants == {'EINVAL': -1, 'MAX': 6}
+    assert [n for n, _ in structs['tipk_inner']._fields_] == ['in_', 'a', 'b', 'relu'] and structs['tipk_inner'].__name__ == 'Inner'
+    assert ctypes.sizeof(structs['tipk_outer']) == 40 and structs['tipk_outer'].alpha.offset == 32
+    assert sigs == {'tipk_f': (_L, [ctypes.POINTER(structs['tipk_late']), _P, ctypes.POINTER(structs['tipk_outer']), _P])}
+
+
+@pytest.mark.parametrize('text, named', [
+    ('int tipk_first(int a);\nint tipk_bad_type(unsigned a, int b);', 'tipk_bad_type'),           # a type outside the mapping
+    ('int tipk_bad_pointee(const size_t* a);', 'tipk_bad_pointee'),
+    ('int tipk_unbalanced(int a, int64_t b;\nint tipk_next(void);', 'tipk_unbalanced'),           # a prototype that does not close
+    ('int tipk_no_end(int a)', 'tipk_no_end'),
+    ('typedef struct tipk_bad_member { int64_t n; const float* a, b; } tipk_bad_member;', 'tipk_bad_member'),
+    ('typedef struct tipk_bad_array { int n; float w[4]; } tipk_bad_array;', 'tipk_bad_array'),  # members it cannot split
+    ('#define TIPK_SHIFTED (1 << 3)\nint tipk_ok(void);', 'TIPK_SHIFTED'),
+])
+def test_header_reader_refuses_what_it_cannot_read(text, named):
+    with pytest.raises(_lib.TipkError, match=named):
+        _lib.read_header(text)
+
+
+@pytest.mark.parametrize('example', ['c_abi_host', 'c_abi_encoder_host'])
+def test_foreign_hosts_bind_what_the_header_declares(example):
+    """The example hosts must not import the package, so they keep short argtypes lists of their own: each must be call-compatible
+    with the table read from the header (same arity, the same scalar types, a pointer where the header has a pointer)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(example, os.path.join(ROOT, 'examples', example + '.py'))
+    host = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(host)
+    handle = host.load_library()                                       # opens the .so and sets argtypes / restype: no GPU
+
+    def kind(t):
+        return 'pointer' if t is not None and issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)) else t
+
+    bound = [n for n in _lib.SIGNATURES if getattr(handle, n).argtypes is not None]
+    assert len(bound) >= 6, bound
+    for name in bound:
+        res, args = _lib.SIGNATURES[name]
+        fn = getattr(handle, name)
+        assert kind(fn.restype) == kind(res), name
+        assert [kind(t) for t in fn.argtypes] == [kind(t) for t in args], name
+
+
 def test_product_never_imports_the_oracle():
     """The product path must not route through the oracle (or any CPU fallback)."""
     pkg = os.path.join(ROOT, 'tip_amd')

@@ -1,5 +1,8 @@
 """ctypes binding of libtipk.so -- every symbol `include/tipk.h` declares, nothing else.
 
+The binding is READ from the header when this module is imported (`read_header`): signatures, struct layouts and constants
+have no second copy here, and a header this module cannot read stops the import before any kernel runs.
+
 The library is built in-tree (`tip_amd/libtipk.so`, see `__graft_entry__.build()` /
 `tip_amd/csrc/Makefile`).  There is NO fallback: if the shared object is missing or a call returns
 a non-zero status, an exception is raised -- the product path never computes on the CPU.
@@ -7,7 +10,9 @@ a non-zero status, an exception is raised -- the product path never computes on 
 import ctypes as C
 import glob
 import hashlib
+import keyword
 import os
+import re
 import subprocess
 
 import torch
@@ -15,195 +20,111 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libtipk.so')
 CSRC = os.path.join(_HERE, 'csrc')
-
-ABI_VERSION = 25
+HEADER_PATH = os.path.join(_HERE, '..', 'include', 'tipk.h')
 
 
 class TipkError(RuntimeError):
     pass
 
 
-class GemmDesc(C.Structure):
-    """struct tipk_gemm_desc (include/tipk.h)."""
-    _fields_ = [('m', C.c_int64), ('n', C.c_int64), ('k', C.c_int64),
-                ('batch', C.c_int64), ('kbatch', C.c_int64), ('ksplit', C.c_int64),
-                ('a', C.c_void_p), ('a_sm', C.c_int64), ('a_sk', C.c_int64), ('a_sq', C.c_int64), ('a_sz', C.c_int64),
-                ('b', C.c_void_p), ('b_sk', C.c_int64), ('b_sn', C.c_int64), ('b_sq', C.c_int64), ('b_sz', C.c_int64),
-                ('c', C.c_void_p), ('c_sm', C.c_int64), ('c_sz', C.c_int64), ('c_ss', C.c_int64),
-                ('c_in', C.c_void_p), ('cin_sm', C.c_int64), ('cin_sz', C.c_int64),
-                ('alpha', C.c_float), ('relu', C.c_int)]
+# The ONE mapping from C type to ctypes type.  Scalars by exact type; `char*` is c_char_p; a pointer to a struct whose body
+# the header gives is POINTER(<that Structure>); every other pointer, at any depth, is c_void_p -- the header cannot tell a
+# host out-parameter from a device buffer, and c_void_p takes byref(...), ctypes arrays, integers and None alike.
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
+            'float': C.c_float, 'double': C.c_double}
+_POINTEES = set(_SCALARS) | {'void', 'char', 'uint8_t', 'uint16_t', 'uint32_t'}
+_TOKEN = re.compile(r'\w+|\S')
+_DECLARATION = re.compile(r'\s*((?:[^;{}]|\{[^{}]*\})*);')
 
 
-class SlabSumDesc(C.Structure):
-    """struct tipk_slab_sum_desc (include/tipk.h)."""
-    _fields_ = [('in_', C.c_void_p), ('n_slabs', C.c_int64), ('slab_stride', C.c_int64), ('count', C.c_int64),
-                ('alpha', C.c_float), ('accumulate', C.c_int),
-                ('row_scale', C.c_void_p), ('cols', C.c_int64),
-                ('addend', C.c_void_p), ('relu', C.c_int),
-                ('gate', C.c_void_p),
-                ('out', C.c_void_p)]
+def read_header(text):
+    """(constants, structs, signatures) of a header in the C subset include/tipk.h is written in: block comments,
+    `#define TIPK_<NAME> <integer>`, `typedef void* <name>;`, forward declarations of structs (opaque types),
+    `typedef struct tipk_x { members } tipk_x;` and prototypes `type tipk_name(parameters);`.  Whatever else it meets raises a
+    TipkError that names the declaration: no type is ever guessed."""
+    def fail(what, decl):
+        raise TipkError('include/tipk.h: %s: "%s"' % (what, decl if len(decl) < 200 else decl[:200] + ' ...'))
+
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', ' ', text, flags=re.S)           # extern "C" { and its }
+    constants, structs, signatures = {}, {}, {}
+    for line in re.findall(r'^[ \t]*#[ \t]*define.*$', text, flags=re.M):
+        m = re.fullmatch(r'#\s*define\s+TIPK_(\w+)(?:\s+\(?(-?\d+)\)?)?', line.strip())
+        if m is None:
+            fail('#define that is not TIPK_<NAME> <integer>', line.strip())
+        if m.group(2) is not None:                                                 # (the include guard has no value)
+            constants[m.group(1)] = int(m.group(2))
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M).rstrip()
+    pointees, handles = set(_POINTEES), set()                                      # + opaque structs; `typedef void*` names
+
+    def ctype(tokens, decl):
+        words = [t for t in tokens if t not in ('const', 'struct')]
+        base, stars = (words[0] if words else ''), words[1:]
+        if stars.count('*') == len(stars):
+            if not stars and base in _SCALARS:
+                return _SCALARS[base]
+            if not stars and base in structs:
+                return structs[base]
+            if stars == ['*'] and base == 'char':
+                return C.c_char_p
+            if stars == ['*'] and base in structs:
+                return C.POINTER(structs[base])
+            if base in handles or (stars and base in pointees):
+                return C.c_void_p
+        fail('unknown type "%s"' % ' '.join(tokens), decl)
+
+    def fields(name, body):
+        out = []
+        for member in filter(None, (m.strip() for m in body.split(';'))):
+            first, *more = [_TOKEN.findall(p) for p in member.split(',')]
+            names = first[-1:] + [''.join(p) for p in more]
+            if len(first) < 2 or not all(n.isidentifier() for n in names) or (more and '*' in first):
+                fail('struct %s: cannot split member' % name, member)
+            t = ctype(first[:-1], 'struct %s: %s' % (name, member))
+            out += [(n + '_' if keyword.iskeyword(n) else n, t) for n in names]
+        return out
+
+    prototypes, pos = [], 0
+    while pos < len(text):
+        m = _DECLARATION.match(text, pos)
+        if m is None:
+            fail('declaration without end', ' '.join(text[pos:].split()))
+        pos, decl = m.end(), ' '.join(m.group(1).split())
+        m = re.fullmatch(r'typedef struct (tipk_\w+) \{(.*)\} \1', decl)
+        if m is not None:
+            python_name = ''.join(w.capitalize() for w in m.group(1)[5:].split('_'))
+            structs[m.group(1)] = type(python_name, (C.Structure,), {
+                '_fields_': fields(*m.groups()), '__doc__': 'struct %s (include/tipk.h).' % m.group(1)})
+            continue
+        m = re.fullmatch(r'typedef void ?\* ?(tipk_\w+)|(?:typedef )?struct (tipk_\w+)(?: \2)?', decl)
+        if m is not None:
+            (handles if m.group(1) else pointees).add(m.group(1) or m.group(2))
+        elif re.fullmatch(r'[\w *]+\btipk_\w+ ?\(.*\)', decl):
+            prototypes.append(decl)                                                # after every struct body is known
+        else:
+            fail('declaration that is neither a typedef, a struct nor a prototype', decl)
+    for decl in prototypes:
+        res, name, params = re.fullmatch(r'([\w *]+?) ?\b(tipk_\w+) ?\((.*)\)', decl).groups()
+        args = []
+        for p in ([] if params.strip() == 'void' else params.split(',')):
+            tokens = _TOKEN.findall(p)
+            if len(tokens) < 2 or not tokens[-1].isidentifier():
+                fail('parameter without a name "%s"' % p.strip(), decl)
+            args.append(ctype(tokens[:-1], decl))
+        signatures[name] = (None if res.strip() == 'void' else ctype(_TOKEN.findall(res), decl), args)
+    return constants, structs, signatures
 
 
-class WgGemmDesc(C.Structure):
-    """struct tipk_wg_gemm_desc (include/tipk.h)."""
-    _fields_ = [('p', GemmDesc),
-                ('a2', C.c_void_p), ('a2_sm', C.c_int64), ('a2_sk', C.c_int64),
-                ('b2', C.c_void_p), ('b2_sk', C.c_int64), ('b2_sn', C.c_int64),
-                ('k2', C.c_int64),
-                ('gate', C.c_void_p), ('gate_sm', C.c_int64), ('gate_sz', C.c_int64)]
+with open(HEADER_PATH) as _f:
+    _CONSTANTS, _STRUCTS, SIGNATURES = read_header(_f.read())      # SIGNATURES: name -> (restype, argtypes)
 
-
-ENCODER_PARAMS = ('embed', 'pp_w1', 'pp_b1', 'pp_w2', 'pp_b2', 'hgcn_w', 'basis1', 'att1', 'root1', 'basis2', 'att2', 'root2')
-ENCODER_FROM_FWD = 1                           # TIPK_ENCODER_FROM_FWD
-
-
-class EncoderDims(C.Structure):
-    """struct tipk_encoder_dims (include/tipk.h section 10d)."""
-    _fields_ = [('n_embed', C.c_int), ('prot_drug_dim', C.c_int), ('n_hid1', C.c_int), ('n_hid2', C.c_int), ('num_base', C.c_int),
-                ('cat', C.c_int)]
-
-
-class EncoderParams(C.Structure):
-    """struct tipk_encoder_params."""
-    _fields_ = [(k, C.c_void_p) for k in ENCODER_PARAMS] + [('lin_layout', C.c_int)]
-
-
-class EncoderGrads(C.Structure):
-    """struct tipk_encoder_grads."""
-    _fields_ = [(k, C.c_void_p) for k in ENCODER_PARAMS]
-
-
-GROUP_MAX = 6                                  # TIPK_GROUP_MAX
-WG_GEMM_MAX, WG_SUMS_MAX = 4, 3                # TIPK_WG_GEMM_MAX, TIPK_WG_SUMS_MAX
-
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-# name -> (restype, argtypes); must list exactly the functions of include/tipk.h
-SIGNATURES = {
-    'tipk_abi_version': (_I, []),
-    'tipk_strerror': (C.c_char_p, [_I]),
-    'tipk_build_id': (C.c_char_p, []),
-    'tipk_set_option': (_I, [C.c_char_p, _I]),
-    'tipk_get_option': (_I, [C.c_char_p, C.POINTER(_I)]),
-    'tipk_device_info': (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.c_char_p, _I]),
-    'tipk_gather_sum': (_I, [_P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _P]),
-    'tipk_gather_sum_finalize': (_I, [_P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P]),
-    'tipk_gather_sum_riders_supported': (_I, [_I, _I]),
-    'tipk_gather_sum_riders': (_I, [_P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, C.POINTER(SlabSumDesc), C.c_int32, _P]),
-    'tipk_gather_sum_lin_supported': (_I, [_I, _I, _I]),
-    'tipk_gather_sum_lin': (_I, [_P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _L, _L, _P, _I, _P, _L, _I, _I, _I, _P]),
-    'tipk_gather_rows_csr': (_I, [_P, _L, _L, _P, _P, _L, _P, _L, _I, _P]),
-    'tipk_rel_gather_supported': (_I, [_L, _I, _I]),
-    'tipk_rel_gather_occupancy': (_I, [_L, _I, _I]),
-    'tipk_rel_gather_chunk': (_I, [_L, _I, _I]),
-    'tipk_pair_product_supported': (_I, [_I, _I]),
-    'tipk_pair_product': (_I, [_P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    'tipk_rgcn_pair_grads_supported': (_I, [_I, _I]),
-    'tipk_rgcn_pair_grads': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _L, _P, _L, _P]),
-    'tipk_stream_gather_parts': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
-    'tipk_stream_gather_parts_two': (_I, [_P, _P, _L, _I, _L, _P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    'tipk_rgcn_dest_products_supported': (_I, [_L, _L, _I, _I]),
-    'tipk_rgcn_dest_products': (_I, [_P, _L, _I, _P, _L, _I, _L, _L, _P, _P, _P, _L, _L, _P]),
-    'tipk_rgcn_row_products_supported': (_I, [_L, _L, _I, _I]),
-    'tipk_rgcn_row_products_slabs': (_L, [_L, _I]),
-    'tipk_rgcn_row_products': (_I, [_P, _L, _L, _I, _P, _L, _L, _I, _P, _P, _P, _L, _P, _P, _P]),
-    'tipk_rgcn_row_products_s_supported': (_I, [_L, _L, _I, _I]),
-    'tipk_rgcn_row_products_s': (_I, [_P, _L, _L, _I, _P, _L, _L, _I, _P, _P, _P, _L, _P, _P, _P]),
-    'tipk_sum_slabs_xb': (_I, [_P, _L, _L, _L, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
-    'tipk_stream_gather_supported': (_I, [_L, _I, _I]),
-    'tipk_stream_gather_piece': (_I, []),
-    'tipk_stream_gather_two': (_I, [_P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _P, _P, _L, _P]),
-    'tipk_stream_gather': (_I, [_P, _L, _L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _I, _P, _P, _I, _P]),
-    'tipk_rel_gather': (_I, [_I, _P, _L, _L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    'tipk_gemm_f32': (_I, [C.POINTER(GemmDesc), _P]),
-    'tipk_gemm_f32_group': (_I, [C.POINTER(GemmDesc), C.c_int32, _P]),
-    'tipk_sum_slabs_group': (_I, [C.POINTER(SlabSumDesc), C.c_int32, _P]),
-    'tipk_gemm_wg_group_supported': (_I, [C.POINTER(WgGemmDesc)]),
-    'tipk_gemm_wg_group': (_I, [C.POINTER(WgGemmDesc), C.c_int32, C.POINTER(SlabSumDesc), C.c_int32, _P]),
-    'tipk_rgcn_dy_products_plan': (_I, [_L, _L, _I, C.POINTER(_I), C.POINTER(_I)]),
-    'tipk_rgcn_dy_products': (_I, [_P, _L, _P, _L, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]),
-    'tipk_rgcn_node_products_plan': (_I, [_L, _I, _L, _I, C.POINTER(_I)]),
-    'tipk_rgcn_node_products': (_I, [_P, _L, _I, _P, _P, _P, _L, _L, _P, _L, _I, _P, _L, _L, _P, _P, _L, _L, _P, _P]),
-    'tipk_sum_slabs': (_I, [_P, _L, _L, _L, _F, _I, _P, _P]),
-    'tipk_sum_slabs_ex': (_I, [_P, _L, _L, _L, _F, _I, _P, _L, _P, _I, _P, _P]),
-    'tipk_transpose': (_I, [_P, _L, _L, _P, _P]),
-    'tipk_rows_affine': (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _L, _L, _I, _P]),
-    'tipk_gate_colsum_groups': (_I, [_L, _L]),
-    'tipk_gate_colsum': (_I, [_P, _L, _P, _L, _P, _L, _L, _L, _P, _P]),
-    'tipk_drug_mix_fwd': (_I, [_P, _L, _P, _P, _L, _P, _I, _I, _L, _I, _I, _P, _L, _P]),
-    'tipk_drug_mix_gather_supported': (_I, [_I, _I]),
-    'tipk_drug_mix_gather_fwd': (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _I, _I, _L, _I, _I, _P, _L, _P, _P]),
-    'tipk_drug_mix_bwd': (_I, [_P, _L, _P, _P, _P, _I, _I, _L, _I, _I, _P, _L, _P, _P, _P]),
-    'tipk_drug_mix_gather_xb_supported': (_I, [_I, _I, _I, _I, _I, _I]),
-    'tipk_drug_mix_gather_xb_fwd': (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _I, _I, _L, _I, _I, _P, _L, _P, _P, _P, _I, _I, _P, _P, _P]),
-    'tipk_pd_stage_bwd_supported': (_I, [_I, _I, _L, _I]),
-    'tipk_pd_stage_bwd_limits': (_I, [C.POINTER(_I), C.POINTER(_I)]),
-    'tipk_pd_stage_bwd_wh_slabs': (_I, []),
-    'tipk_pd_stage_bwd': (_I, [_P, _L, _P, _P, _P, _I, _I, _L, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _I, _P, _L, _L, _P, _P, _L, _P, _P, _P]),
-    'tipk_col_sum': (_I, [_P, _L, _L, _L, _P, _P, _P]),
-    'tipk_distmult_fwd': (_I, [_P, _L, _I, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _P]),
-    'tipk_distmult_bwd': (_I, [_P, _P, _P, _L, _I, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _L, _P, _P, _P]),
-    'tipk_distmult_workspace_bytes': (_L, [_L, _I, _L]),
-    'tipk_distmult_loss': (_I, [_P, _L, _I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P]),
-    'tipk_distmult_loss_store': (_I, [_P, _L, _I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P]),
-    'tipk_pair_table_fwd': (_I, [_P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _P]),
-    'tipk_pair_table_bwd': (_I, [_P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _P, _P, _P]),
-    'tipk_pair_table_loss': (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _F, _P, _P, _P, _P]),
-    'tipk_distmult_screen_supported': (_I, [_L, _I, _I]),
-    'tipk_distmult_screen_workspace_bytes': (_L, [_L, _I, _L, _I]),
-    'tipk_distmult_screen_bitmap_route': (_I, [_L]),
-    'tipk_distmult_screen': (_I, [_P, _L, _I, _P, _L, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P]),
-    'tipk_negsample_wgs_per_cu': (_I, [_L]),
-    'tipk_typed_negative_sampling': (_I, [_P, _P, _L, _L, C.c_uint64, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _P]),
-    'tipk_counter_advance': (_I, [_P, _P]),
-    'tipk_rank_metrics': (_I, [_P, _P, _P, _L, _L, _P, _P]),
-    'tipk_peer_mailbox_bytes': (_L, [_I, _L]),
-    'tipk_peer_alloc': (_I, [_L, C.POINTER(_P)]),
-    'tipk_peer_free': (_I, [_P]),
-    'tipk_ipc_get_handle': (_I, [_P, _P]),
-    'tipk_ipc_open': (_I, [_P, C.POINTER(_P)]),
-    'tipk_ipc_close': (_I, [_P]),
-    'tipk_peer_allreduce': (_I, [_P, _L, C.POINTER(_P), _I, _I, _L, _P]),
-    'tipk_peer_set_timeout_ms': (_I, [_L]),
-    'tipk_peer_status': (_I, [_P, _I, _L, C.POINTER(C.c_uint64)]),
-    'tipk_adam_step': (_I, [_I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), _P,
-                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
-    'tipk_graph_build': (_I, [_P, _P, _P, _I, _L, _L, _L, _P, C.POINTER(C.c_void_p)]),
-    'tipk_graph_destroy': (_I, [_P]),
-    'tipk_graph_info': (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(C.c_void_p)]),
-    'tipk_rgcn_workspace_bytes': (_L, [_P, _I, _I, _I]),
-    'tipk_rgcn_fwd': (_I, [_P, _P, _L, _I, _P, _P, _P, _I, _I, _I, _P, _L, _P, _L, _P]),
-    'tipk_rgcn_bwd': (_I, [_P, _P, _L, _I, _P, _P, _P, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P]),
-    'tipk_gcn_graph_build': (_I, [_P, _I, _L, _L, C.POINTER(C.c_void_p)]),
-    'tipk_gcn_workspace_bytes': (_L, [_P, _I, _I]),
-    'tipk_gcn_fwd': (_I, [_P, _P, _L, _I, _P, _L, _L, _P, _I, _I, _P, _L, _P, _L, _P]),
-    'tipk_gcn_bwd': (_I, [_P, _P, _L, _I, _P, _L, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _P]),
-    'tipk_hier_graph_build': (_I, [_P, _I, _L, _L, _L, C.POINTER(C.c_void_p)]),
-    'tipk_hier_workspace_bytes': (_L, [_P, _I, _I]),
-    'tipk_hier_fwd': (_I, [_P, _P, _L, _I, _P, _I, _P, _L, _P, _L, _P]),
-    'tipk_hier_bwd': (_I, [_P, _P, _L, _I, _P, _I, _P, _L, _P, _L, _P, _P, _L, _P]),
-    'tipk_rgcn_bwd_ex': (_I, [_P, _P, _L, _I, _P, _P, _P, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _P]),
-    'tipk_graph_prepare_rgcn': (_I, [_P, _I, _I]),
-    'tipk_graph_rgcn_route': (_I, [_P, _I, _I]),
-    'tipk_graph_release_host': (_I, [_P]),
-    'tipk_plan_stream_rows': (_I, [_P, _P, _L, _L, _L, _I, _I, _I, _I, _I, _P]),
-    'tipk_plan_pair_bwd': (_I, [_P, _P, _P, _L, _L, _L, _P, _I, _I, _I, _I, _P]),
-    'tipk_plan_link_words': (_I, [_P, _P, _L, _L, _P]),
-    'tipk_plan_gather': (_I, [_P, _P, _P, _L, _L, _L, _I, _I, _P]),
-    'tipk_host_plan_array': (_I, [_P, C.c_char_p, _P, _P, _P]),
-    'tipk_host_plan_scalar': (_L, [_P, C.c_char_p]),
-    'tipk_host_plan_free': (None, [_P]),
-    'tipk_plan_hier_csr': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P]),
-    'tipk_plan_gcn_norm': (_I, [_P, _P, _L, _L, _P, _L, _I, _P]),
-    'tipk_encoder_build': (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _I, _L, _L, _P, C.POINTER(C.c_void_p)]),
-    'tipk_encoder_workspace_bytes': (_L, [_P]),
-    'tipk_encoder_workspace_init': (_I, [_P, _P, _L, _P]),
-    'tipk_encoder_fwd': (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _L, _P]),
-    'tipk_encoder_bwd': (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _I, _P, _L, _P]),
-    'tipk_encoder_destroy': (_I, [_P]),
-    'tipk_split_flags': (_I, [_P, _L, _L, C.c_double, C.c_uint64, _P, _P, _P]),
-    'tipk_split_scatter': (_I, [_P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-}
+ABI_VERSION = _CONSTANTS['ABI_VERSION']
+GROUP_MAX = _CONSTANTS['GROUP_MAX']
+WG_GEMM_MAX, WG_SUMS_MAX = _CONSTANTS['WG_GEMM_MAX'], _CONSTANTS['WG_SUMS_MAX']
+ENCODER_FROM_FWD = _CONSTANTS['ENCODER_FROM_FWD']
+GemmDesc, SlabSumDesc, WgGemmDesc = (_STRUCTS['tipk_' + n] for n in ('gemm_desc', 'slab_sum_desc', 'wg_gemm_desc'))
+EncoderDims, EncoderParams, EncoderGrads = (_STRUCTS['tipk_encoder_' + n] for n in ('dims', 'params', 'grads'))
+ENCODER_PARAMS = tuple(n for n, t in EncoderParams._fields_ if t is C.c_void_p)
 
 _lib = None
 
@@ -220,7 +141,7 @@ def source_digest():
     for n in names:
         with open(os.path.join(CSRC, n), 'rb') as f:
             h.update(f.read())
-    with open(os.path.join(_HERE, '..', 'include', 'tipk.h'), 'rb') as f:
+    with open(HEADER_PATH, 'rb') as f:
         h.update(f.read())
     return h.hexdigest()[:16]
 
@@ -242,7 +163,6 @@ def _stale_reason(path):
     """None if `path` was built from the sources next to it, else a description."""
     if not os.path.exists(path):
         return '%s is missing' % path
-    import re
     with open(path, 'rb') as f:                      # read the marker from the file: no dlopen (see tipk_api.cpp)
         m = re.search(rb'TIPK_BUILD_ID=([0-9a-f]{16})', f.read())
     if m is None:
