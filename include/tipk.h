@@ -810,6 +810,16 @@ int tipk_counter_advance(uint64_t* call_counter /* device */, tipk_stream_t stre
  * (labels 1 / 0).  out is fp64 [3][n_rel] = (AUPRC, AUROC, AP) rows.  Ties share one operating
  * point, exactly as sklearn's curves do.  max_pairs (host) = largest slice; 2*max_pairs <= 16384
  * (one workgroup sorts a relation in LDS), else TIPK_EUNSUPPORTED and the caller evaluates on the host.
+ *
+ * Score policy (tip_amd/utils.py follows the same one on the host path):
+ *   zeros     -0.0 and +0.0 are one score, hence one threshold (as sklearn and numpy compare them);
+ *   +-inf     ordinary scores, the largest and the smallest; equal infinities tie;
+ *   NaN       a relation whose block holds a NaN score reports NaN in all three metrics (sklearn raises; a
+ *             diverged model must not report an AUROC).  The other relations of the launch are unaffected;
+ *   empty     a relation with range_ptr[r+1] <= range_ptr[r] reports NaN in all three metrics;
+ *   max_pairs sizes the LDS of the launch.  A relation larger than an understated max_pairs is not sorted and
+ *             reports NaN (the kernel decides that from range_ptr alone and never indexes LDS beyond its size).
+ * Every cell of out is written by every successful launch.
  */
 int tipk_rank_metrics(const float* pos_score, const float* neg_score, const int64_t* range_ptr /* [n_rel+1] */,
                       int64_t n_rel, int64_t max_pairs, double* out, tipk_stream_t stream);

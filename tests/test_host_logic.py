@@ -143,6 +143,64 @@ def test_metrics_by_range_matches_reference_record():
     np.testing.assert_allclose(rec, g['record'].numpy(), rtol=1e-6)
 
 
+def _host_case(name):
+    import eval_cases as E
+    return {'signed_zeros': lambda: E.signed_zeros(500, 0), 'all_tied': lambda: E.all_equal(300),
+            'perfect': lambda: E.separated(513, 1), 'inverted': lambda: E.separated(513, 1, inverted=True),
+            'infinities': lambda: E.infinities(513, 2)}[name]()
+
+
+@pytest.mark.parametrize('case', ['signed_zeros', 'all_tied', 'perfect', 'inverted', 'infinities'])
+def test_host_metrics_policy_vs_sklearn(case):
+    """The numpy path (`utils.auprc_auroc_ap`, and `auprc_auroc_ap_by_range` on host tensors) == sklearn where scores tie
+    across the sign of zero, all tie, separate perfectly or the wrong way round, or are infinite (sklearn is fed
+    +-FLT_MAX there)."""
+    import eval_cases as E
+    pos, neg = _host_case(case)
+    n = pos.size
+    want = E.sklearn_metrics(pos, neg)
+    got = utils.auprc_auroc_ap(np.r_[np.ones(n), np.zeros(n)], np.r_[pos, neg])
+    np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12)
+    # the same list as the middle relation of three
+    other = E.continuous(7, 5)
+    rec = utils.auprc_auroc_ap_by_range(torch.from_numpy(np.r_[other[0], pos, other[0]]),
+                                        torch.from_numpy(np.r_[other[1], neg, other[1]]),
+                                        torch.tensor([[0, 7], [7, 7 + n], [7 + n, 14 + n]]))
+    assert rec.shape == (3, 3) and rec.dtype == np.float64
+    np.testing.assert_allclose(rec[:, 1], want, rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(rec[:, 0], E.sklearn_metrics(*other), rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(rec[:, 2], rec[:, 0], rtol=0, atol=0)
+    if case == 'all_tied':
+        assert got[1] == 0.5
+    if case == 'perfect':
+        assert got[1] == 1.0 and got[2] == 1.0
+    if case == 'inverted':
+        assert got[1] == 0.0
+
+
+def test_host_metrics_empty_and_nan_relations_report_nan():
+    """One call serves all relations, so an empty relation or a NaN score must not raise: that relation reports NaN in all
+    three metrics and the others are what sklearn gives."""
+    import eval_cases as E
+    assert np.isnan(utils.auprc_auroc_ap(np.zeros(0), np.zeros(0))).all()
+    assert np.isnan(utils.auprc_auroc_ap(np.r_[1.0, 1.0, 0.0, 0.0], np.r_[0.3, np.nan, 0.2, 0.1])).all()
+    sizes = [0, 5, 40, 0, 40, 3, 0]
+    ptr = np.r_[0, np.cumsum(sizes)]
+    pos, neg = E.continuous(int(ptr[-1]), 9)
+    clean = (pos.copy(), neg.copy())
+    pos[ptr[2] + 11] = np.nan                                          # relation 2: NaN among the positives
+    neg[ptr[4] + 39] = np.nan                                          # relation 4: NaN among the negatives
+    rec = utils.auprc_auroc_ap_by_range(torch.from_numpy(pos), torch.from_numpy(neg),
+                                        torch.tensor(np.stack([ptr[:-1], ptr[1:]], 1)))
+    assert rec.shape == (3, len(sizes)) and rec.dtype == np.float64
+    for r, n in enumerate(sizes):
+        if n == 0 or r in (2, 4):
+            assert np.isnan(rec[:, r]).all(), (r, rec[:, r])
+        else:
+            np.testing.assert_allclose(rec[:, r], E.sklearn_metrics(clean[0][ptr[r]:ptr[r + 1]], clean[1][ptr[r]:ptr[r + 1]]),
+                                       rtol=1e-9, atol=1e-12)
+
+
 # ------------------------------------------------------------------ data ingest
 def test_biosnap_data_dict_schema_and_sizes():
     d = build_data_dict(max_relations=5)

@@ -12,6 +12,10 @@
 //   AP    = sum (rec_k - rec_{k-1}) prec_k
 //   AUPRC = trapezoid of (recall, precision) from (0, 1) up to the first point with full recall
 //           (= metrics.auc over metrics.precision_recall_curve).
+//
+// Score policy (the host path of tip_amd/utils.py follows the same one): -0.0 is keyed as +0.0 (equal scores are one
+// threshold); +-inf are the largest / smallest score; a relation whose block holds a NaN score, an empty relation and a
+// relation larger than the launch's LDS (an understated max_pairs) report NaN in all three metrics.
 #include "tipk_common.h"
 
 namespace {
@@ -19,8 +23,9 @@ namespace {
 constexpr int RM_MAX = 16384;           // keys per relation (LDS: 8 B each)
 constexpr int RM_T = 1024;
 
-__device__ __forceinline__ uint32_t orderable(float f) {       // larger float -> larger uint
-    const uint32_t u = __float_as_uint(f);
+__device__ __forceinline__ uint32_t orderable(float f) {       // larger float -> larger uint; -0.0 == +0.0
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) == 0u) u = 0u;                       // (on the bits: denormals stay distinct from zero)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -32,7 +37,7 @@ struct Carry {                           // last operating point at or before a 
 __global__ __launch_bounds__(RM_T) void rank_metrics_kernel(const float* __restrict__ pos,
                                                             const float* __restrict__ neg,
                                                             const int64_t* __restrict__ range_ptr, int64_t n_rel,
-                                                            double* __restrict__ out) {
+                                                            int cap, double* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     __shared__ int s_cnt[RM_T];
     __shared__ Carry s_carry[RM_T];
@@ -40,21 +45,31 @@ __global__ __launch_bounds__(RM_T) void rank_metrics_kernel(const float* __restr
     const int t = threadIdx.x;
     const int64_t rel = blockIdx.x;
     const int64_t a = range_ptr[rel], b = range_ptr[rel + 1];
-    const int n = (int)(b - a);                       // positives = negatives = n
-    const int m = 2 * n;
-    if (n <= 0) {                                     // empty relation: sklearn would raise; report NaN
-        if (t < 3) out[t * n_rel + rel] = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    // empty relation (sklearn would raise), or more keys than the launch reserved LDS for: report NaN.  Decided from
+    // range_ptr alone, before anything else is read.
+    if (b <= a || 2 * (b - a) > (int64_t)cap) {
+        if (t < 3) out[t * n_rel + rel] = nan;
         return;
     }
+    const int n = (int)(b - a);                       // positives = negatives = n
+    const int m = 2 * n;
     int npad = 1;
     while (npad < m) npad <<= 1;
+    int bad = 0;                                      // a NaN score has no rank
     for (int i = t; i < npad; i += RM_T) {
         unsigned long long k = 0ull;                  // padding sorts to the end (smallest key)
-        if (i < n) k = ((unsigned long long)orderable(pos[a + i]) << 1) | 1ull;
-        else if (i < m) k = ((unsigned long long)orderable(neg[a + i - n]) << 1);
-        keys[i] = i < m ? k + 2ull : 0ull;            // +2: every real key is above the padding key 0
+        if (i < m) {
+            const float f = i < n ? pos[a + i] : neg[a + i - n];
+            bad |= (__float_as_uint(f) & 0x7fffffffu) > 0x7f800000u;
+            k = (((unsigned long long)orderable(f) << 1) | (i < n ? 1ull : 0ull)) + 2ull;   // +2: above the padding key 0
+        }
+        keys[i] = k;
     }
-    __syncthreads();
+    if (__syncthreads_or(bad)) {                      // (also the barrier between the key stores and the sort)
+        if (t < 3) out[t * n_rel + rel] = nan;
+        return;
+    }
     // bitonic sort, descending
     for (int k = 2; k <= npad; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -165,6 +180,6 @@ extern "C" int tipk_rank_metrics(const float* pos_score, const float* neg_score,
                                        (int)lds);
     if (e != hipSuccess) return tipk_hip_status(e);
     hipLaunchKernelGGL(rank_metrics_kernel, dim3((unsigned)n_rel), dim3(RM_T), lds, (hipStream_t)stream, pos_score,
-                       neg_score, range_ptr, n_rel, out);
+                       neg_score, range_ptr, n_rel, npad, out);
     TIPK_RETURN_LAUNCH();
 }

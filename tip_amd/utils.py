@@ -89,11 +89,12 @@ def sparse_id(n):
 # ---------------------------------------------------------------------------------------------
 def _binary_curve(y, s):
     """Cumulative TP/FP at each distinct threshold, scores descending (sklearn
-    `_binary_clf_curve` semantics: ties share one operating point)."""
+    `_binary_clf_curve` semantics: ties share one operating point).  Scores are compared, not
+    subtracted: -0.0 ties with +0.0, and equal infinities tie (their difference would be NaN)."""
     order = np.argsort(-s, kind='mergesort')
     y = y[order]
     s = s[order]
-    last = np.r_[np.flatnonzero(np.diff(s)), y.size - 1]
+    last = np.r_[np.flatnonzero(s[1:] != s[:-1]), y.size - 1]
     tps = np.cumsum(y, dtype=np.float64)[last]
     fps = 1.0 + last - tps
     return tps, fps
@@ -102,9 +103,15 @@ def _binary_curve(y, s):
 def auprc_auroc_ap(target_tensor, score_tensor):
     """(AUPRC, AUROC, AP) of one relation, as the reference computes them:
     AUROC = trapezoid over the ROC curve, AP = sum (R_n - R_{n-1}) P_n, AUPRC = trapezoid over the
-    precision-recall curve (`metrics.auc(recall, precision)`)."""
+    precision-recall curve (`metrics.auc(recall, precision)`).
+
+    Score policy, the same as `tipk_rank_metrics` (include/tipk.h section 6): -0.0 ties with +0.0, +-inf are
+    the largest / smallest score, and an empty relation or one that holds a NaN score reports NaN in all
+    three metrics (sklearn raises on both; a diverged model must not report an AUROC)."""
     y = torch.as_tensor(target_tensor).detach().cpu().numpy().astype(np.float64).ravel()
     s = torch.as_tensor(score_tensor).detach().cpu().numpy().astype(np.float64).ravel()
+    if s.size == 0 or np.isnan(s).any():
+        return float('nan'), float('nan'), float('nan')
     tps, fps = _binary_curve(y, s)
     P, N = tps[-1], fps[-1]
     if P == 0 or N == 0:
@@ -126,8 +133,11 @@ def auprc_auroc_ap(target_tensor, score_tensor):
 def auprc_auroc_ap_by_range(pos_score, neg_score, range_list):
     """[3, R] record of (AUPRC, AUROC, AP) per relation block (`src/layers.py:355-368`).
     Device tensors are evaluated by `tipk_rank_metrics` (one launch for all relations); host tensors,
-    non-consecutive ranges or oversized relations take the numpy path below."""
-    if torch.is_tensor(pos_score) and pos_score.is_cuda:
+    non-consecutive ranges, oversized relations and fp64 scores (the kernel ranks fp32) take the numpy
+    path below.  Both paths return float64 [3, R] and follow one score policy (`auprc_auroc_ap`)."""
+    pos_score, neg_score = (t.float() if torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16) else t
+                            for t in (pos_score, neg_score))                     # exact in fp32
+    if all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (pos_score, neg_score)):
         rg = torch.as_tensor(range_list).to(torch.int64).cpu()
         consecutive = rg.numel() > 0 and int(rg[0, 0]) == 0 and bool((rg[1:, 0] == rg[:-1, 1]).all())
         if consecutive and int(rg[-1, 1]) == pos_score.numel() == neg_score.numel():
