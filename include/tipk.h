@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 25
+#define TIPK_ABI_VERSION 26
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -53,6 +53,8 @@ const char* tipk_build_id(void);
  *      "dm_task_kernel"      1 = fused objective through the k/4-lanes-per-position task kernel (the round-2 kernel; A/B runs)
  *      "screen_search"       1 = tipk_distmult_screen filters known pairs by binary search even where the LDS bitmap fits
  *                            (section 4c; both routes return the same bits)
+ *      "pair_topk_stream"    1 = tipk_distmult_pair_topk streams rel_w through LDS in tiles even where all of it fits
+ *                            (section 4d; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -756,6 +758,53 @@ int     tipk_distmult_screen(const float* z, int64_t n_nodes, int dim, const flo
                              const int32_t* queries /* host */, int64_t n_q,
                              const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
                              int k, float* out_score, int32_t* out_u, int32_t* out_v, void* workspace, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4d. Pair top-k: the k best relations (side effects) of every pair of a list, known ones dropped, ranked on the logit
+ *     (serving; the transposed question of 4c; no reference call site: `TIP.pred` scores given triples only).
+ *
+ *   pair_u / pair_v: DEVICE int32 [n_pairs].  The candidates of pair (u, v) are all relations r in [0, n_rel); self pairs
+ *   and repeated pairs are legal and are scored like any other.  A pair with an index outside [0, n_nodes) gets a fully
+ *   padded row and reads nothing out of bounds (device data cannot be validated on the host without a sync).
+ *   DistMult (tipk_distmult_pair_topk): z [n_nodes x dim], rel_w [n_rel x dim] fp32 row-major (rel_w 16-byte aligned).
+ *   Each logit is fp32: h_k = z[u,k] * z[v,k] rounded, then acc = fmaf(h_k, w[r,k], acc) for k ascending from 0 -- one
+ *   value per pair on every route, and (u, v) and (v, u) give identical bits.
+ *   Table variant (tipk_pair_table_pair_topk; the NN decoder of 4b): node-major tables s1, s2 [n_nodes x ld], ld >= n_rel,
+ *   as NNDecoder.forward forms them; the logit is the single fp32 add s1[u,r] + s2[v,r]; NOT symmetric in (u, v).
+ *   Known filter, pair-major (nullable together; device): known_pair_keys int64 [n_known_pairs], strictly ascending keys
+ *   min(u,v)*n_nodes + max(u,v); known_pair_ptr int64 [n_known_pairs + 1]; known_rel int32, ascending relation ids inside
+ *   each pair's block [known_pair_ptr[i], known_pair_ptr[i+1]).  A relation listed for the pair's UNORDERED key is dropped
+ *   in either pair direction, for both decoders.  One search per pair finds the block; the block is then merged into a
+ *   bitmap of the wavefront: never a search per (pair, relation).
+ *   Output per pair (device): out_score fp32 [n_pairs x k] = LOGITS (for the reason 4c gives: sigma saturates in fp32),
+ *   out_rel int32 [n_pairs x k]; order: descending logit, ties by ascending relation id; a row with fewer than k candidates
+ *   is padded with (-inf, -1).  A NaN logit is never returned.  The result is a set fixed by that total order and is
+ *   BITWISE repeatable.
+ *   Routes (DistMult): rel_w is staged in LDS once per workgroup when it fits beside the wavefronts' lists
+ *   (tipk_distmult_pair_topk_lds_route: 1 097 x 16 does), and streamed through LDS in tiles, one pass per block of 16
+ *   pairs, otherwise or under option "pair_topk_stream"; same bits.
+ *   Supported: 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult), 1 <= n_rel <= 65 536, 1 <= k <= 128.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k <= 0, a negative size, n_nodes or n_rel < 1,
+ *   ld < n_rel, a NULL required pointer (with n_pairs > 0), known arrays given only in part; then TIPK_EUNSUPPORTED outside
+ *   the supported range; n_pairs == 0 is TIPK_OK with no launch; TIPK_OK implies correct numbers.
+ *   workspace: tipk_distmult_pair_topk_workspace_bytes(...) bytes (-1: unsupported).  Every list lives in LDS, so this is
+ *   0 for every supported shape today and `workspace` may then be NULL.
+ *   Unlike 4c nothing lives in host memory: these entries do NOT synchronise and may be captured into a hipGraph.
+ */
+int     tipk_distmult_pair_topk_supported(int64_t n_nodes, int dim, int64_t n_rel, int k);
+int64_t tipk_distmult_pair_topk_workspace_bytes(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_pairs, int k);
+int     tipk_distmult_pair_topk_lds_route(int dim, int64_t n_rel);   /* 1 = rel_w is staged in LDS once (options apply) */
+int     tipk_distmult_pair_topk(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                const int32_t* pair_u, const int32_t* pair_v /* device */, int64_t n_pairs,
+                                const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                int64_t n_known_pairs /* nullable together */,
+                                int k, float* out_score, int32_t* out_rel, void* workspace, tipk_stream_t stream);
+int     tipk_pair_table_pair_topk_supported(int64_t n_nodes, int64_t n_rel, int k);
+int     tipk_pair_table_pair_topk(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                  const int32_t* pair_u, const int32_t* pair_v /* device */, int64_t n_pairs,
+                                  const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                  int64_t n_known_pairs /* nullable together */,
+                                  int k, float* out_score, int32_t* out_rel, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

@@ -33,7 +33,8 @@ enum {
     TIPK_OPT_DM_DEBUG = 6,            // debug builds only (decoder kernels)
     TIPK_OPT_DM_TASK_KERNEL = 7,      // fused objective through distmult_task_kernel (k / 4 lanes per position) -- A/B runs
     TIPK_OPT_SCREEN_SEARCH = 8,       // tipk_distmult_screen: known-pair filter by binary search even where the LDS bitmap fits
-    TIPK_OPT_COUNT = 9
+    TIPK_OPT_PAIR_TOPK_STREAM = 9,    // tipk_distmult_pair_topk: rel_w streamed through LDS in tiles even where all of it fits
+    TIPK_OPT_COUNT = 10
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

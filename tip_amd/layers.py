@@ -31,6 +31,8 @@ EPS = 1e-13                    # src/layers.py:15
 
 # TIP.screen's result: per query row the k best pairs (u, v) of side effect `relation`, best first
 ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
+# TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
+SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP']
@@ -805,6 +807,15 @@ class MultiInnerProductDecoder(nn.Module):
         q = screen_queries(self.num_et, relations, drugs)
         return ops.distmult_screen(z.detach(), self.weight.detach(), q, k, known)
 
+    def top_relations(self, z, pairs, k, known=None, relations=None):
+        """Pair top-k (extension, `tipk_distmult_pair_topk`): the k best relations of every pair of `pairs` [2, P] by LOGIT ->
+        (logits [P, k], relation int32 [P, k]); no autograd.  known: (pair_keys, pair_ptr, rel) to drop
+        (`ops.known_relations_by_pair`).  relations: candidate ids (None = all); the returned ids are positions in it."""
+        w = self.weight.detach()
+        if relations is not None:
+            w = w[relations]
+        return ops.distmult_pair_topk(z.detach(), w, pairs, k, known)
+
 
 def screen_queries(num_et, relations=None, drugs=None):
     """int32 [Q, 2] (relation, drug | -1) on the host, in the order `MultiInnerProductDecoder.screen` documents."""
@@ -880,6 +891,18 @@ class NNDecoder(nn.Module):
         s1 = ops.matmul(p, self.w1_l2.t())                       # [N, R]: every (node, relation) dot product
         s2 = ops.matmul(q, self.w2_l2.t())
         return ops.pair_table_score(s1, s2, edge_index, edge_type, sigmoid=True)
+
+    def top_relations(self, z, pairs, k, known=None, relations=None):
+        """Pair top-k (extension, `tipk_pair_table_pair_topk`) on the two tables `forward` forms -> (logits [P, k], relation
+        int32 [P, k]); no autograd.  relations: candidate ids (None = all): columns of the tables, i.e. rows of w*_l2; the
+        returned ids are positions in it."""
+        with torch.no_grad():
+            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
+            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
+            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
+            s1 = ops.matmul(p, w1.t())
+            s2 = ops.matmul(q, w2.t())
+        return ops.pair_table_pair_topk(s1, s2, pairs, k, known)
 
     def objective(self, z, pos_index, neg_index, edge_type):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps) (src/layers.py:335-340 with this decoder as
@@ -1039,7 +1062,8 @@ class TIP(nn.Module):
         """Serving helper (extension): for every drug pair (u, v) of
         `dd_pairs` [2, P] the k most likely side effects -> (scores [P, k], relation ids [P, k]).
         All num_et relations of a pair are scored by the decoder kernel in one launch (pairs are
-        processed in slices of at most `max_triples` triples)."""
+        processed in slices of at most `max_triples` triples).  `side_effects` answers the same question from one fused
+        launch and can leave out the side effects already recorded for a pair."""
         R = self.data.n_dd_et
         k = min(int(k), R)
         pairs = dd_pairs.to(self.embeddings.device).to(torch.int64)
@@ -1058,6 +1082,54 @@ class TIP(nn.Module):
         if not vals:
             return (torch.zeros((0, k), device=pairs.device), torch.zeros((0, k), dtype=torch.int64, device=pairs.device))
         return torch.cat(vals), torch.cat(ids)
+
+    def side_effects(self, pairs, k=10, exclude=None, relations=None, sigmoid=True):
+        """Serving (extension): the k side effects the model scores highest for every drug pair of `pairs` [2, P], among
+        those not already recorded for the pair (`decoder.top_relations`: one `tipk_distmult_pair_topk` /
+        `tipk_pair_table_pair_topk` launch on `self.embeddings`, under no_grad; both decoder kinds).
+        exclude: 'train' drops the pair's training side effects (held-out ones can and do appear), 'all' drops train and
+        test ones, None drops nothing; a recorded side effect is dropped in either pair direction.  relations: candidate
+        side-effect ids (None = all); the returned ids are global.  Ranking is on the logit, ties by ascending position in
+        `relations`; sigmoid = True applies sigma afterwards (padding: score sigma(-inf) = 0, relation -1).
+        -> SideEffects(score [P, k], relation int64 [P, k]) on the model's device."""
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
+                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
+        if exclude not in ('train', 'all', None):
+            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        d = self.data
+        dev = self.embeddings.device
+        pairs = torch.as_tensor(pairs).to(dev)
+        if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype.is_floating_point:
+            raise ValueError('pairs: an int tensor [2, P] expected, got %s %s' % (pairs.dtype, tuple(pairs.shape)))
+        if pairs.numel():
+            lo, hi = torch.stack([pairs.min(), pairs.max()]).tolist()
+            if lo < 0 or hi >= d.n_drug:
+                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
+        known = None
+        if exclude is not None:
+            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
+            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
+        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
+        if rel is not None and known is not None:
+            # the lists hold global ids: keep the candidates' entries and renumber them to positions in `relations`
+            keys, kptr, krel = known
+            pos = torch.full((d.n_dd_et,), -1, dtype=torch.int64, device=dev)
+            pos[rel] = torch.arange(rel.numel(), device=dev)
+            owner = torch.repeat_interleave(torch.arange(keys.numel(), device=dev), kptr[1:] - kptr[:-1])
+            new = pos[krel.long()]
+            keep = new >= 0
+            order = torch.sort(owner[keep] * max(1, rel.numel()) + new[keep]).indices
+            kptr2 = torch.zeros_like(kptr)
+            kptr2[1:] = torch.cumsum(torch.bincount(owner[keep], minlength=keys.numel()), 0)
+            known = (keys, kptr2, new[keep][order].to(torch.int32))
+        with torch.no_grad():
+            logit, idx = self.decoder.top_relations(self.embeddings, pairs, k, known, rel)
+            score = torch.sigmoid(logit) if sigmoid else logit
+            idx = idx.to(torch.int64)
+            if rel is not None:
+                idx = torch.where(idx >= 0, rel[idx.clamp(min=0)], idx)
+        return SideEffects(score, idx)
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

@@ -1081,6 +1081,110 @@ def distmult_screen(z, rel_w, queries, k, known=None):
     return out_s, out_u, out_v
 
 
+_PAIR_KNOWN = {}
+
+
+def known_relations_by_pair(edge_index, range_list, n_nodes, extra=None):
+    """The pair-major known lists of include/tipk.h section 4d from edges grouped by relation -> (pair_keys int64
+    strictly ascending min(u,v)*n+max(u,v), pair_ptr int64 [n_keys + 1], rel int32 ascending inside a pair's block), built
+    with torch ops on edge_index's device (CPU tensors work too).  range_list [R, 2]: relation r owns the edge positions
+    [begin, end) (the blocks tile the list in relation order).  Mirrored halves and duplicate edges collapse into one
+    entry.  extra = (edge_index, range_list) of a second list to merge (train + test).  Cached per edge tensor(s)."""
+    def ident(ei):
+        return (ei.data_ptr(), ei._version, tuple(ei.shape), str(ei.device))
+
+    def combined(ei, rl, n_rel):
+        ends = torch.as_tensor(rl).to(device=ei.device, dtype=torch.int64).reshape(-1, 2)[:, 1].contiguous()
+        rel = torch.bucketize(torch.arange(ei.shape[1], device=ei.device), ends, right=True)
+        u, v = ei[0].to(torch.int64), ei[1].to(torch.int64)
+        return (torch.minimum(u, v) * int(n_nodes) + torch.maximum(u, v)) * n_rel + rel
+
+    n_rel = int(torch.as_tensor(range_list).reshape(-1, 2).shape[0])
+    tag = (ident(edge_index), int(n_nodes), n_rel, None if extra is None else ident(extra[0]))
+    hit = _PAIR_KNOWN.get(tag)
+    if hit is None:
+        c = combined(edge_index, range_list, n_rel)
+        if extra is not None:
+            c = torch.cat([c, combined(extra[0].to(edge_index.device), extra[1], n_rel)])
+        c = torch.unique(c)                                              # sorted by (key, relation), duplicates gone
+        keys, counts = torch.unique_consecutive(torch.div(c, n_rel, rounding_mode='floor'), return_counts=True)
+        ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=c.device)
+        ptr[1:] = torch.cumsum(counts, 0)
+        hit = (keys.contiguous(), ptr, (c % n_rel).to(torch.int32).contiguous())
+        if len(_PAIR_KNOWN) > 8:
+            _PAIR_KNOWN.clear()
+        _PAIR_KNOWN[tag] = hit
+    return hit
+
+
+def _pair_topk_lists(pairs, known, dev):
+    """(pair_u, pair_v int32 [P], keys, ptr, rel, n_keys) of the pair top-k entries, all on `dev`."""
+    pairs = torch.as_tensor(pairs)
+    require_device(pairs)
+    if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype.is_floating_point:
+        raise _lib.TipkError('pairs: an int tensor [2, P] expected, got %s %s' % (pairs.dtype, tuple(pairs.shape)))
+    pu, pv = pairs[0].to(torch.int32).contiguous(), pairs[1].to(torch.int32).contiguous()
+    keys = kptr = krel = None
+    n_keys = 0
+    if known is not None:
+        keys, kptr, krel = known
+        require_device(keys, kptr, krel)
+        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+        krel = krel.to(torch.int32).contiguous()
+        n_keys = keys.numel()
+        if kptr.numel() != n_keys + 1:
+            raise _lib.TipkError('known: pair_ptr has %d entries for %d keys' % (kptr.numel(), n_keys))
+        if n_keys == 0 or krel.numel() == 0:                             # nothing to drop (empty tensors have no address)
+            keys = kptr = krel = None
+            n_keys = 0
+    return pu, pv, keys, kptr, krel, n_keys
+
+
+def distmult_pair_topk(z, rel_w, pairs, k, known=None):
+    """The k best relations of every pair by DistMult logit, known ones dropped (include/tipk.h section 4d).
+
+    pairs: int tensor [2, P] on the device.  known: None or (pair_keys, pair_ptr, rel) on the device, the pair-major lists
+    of `known_relations_by_pair`.  -> (logits float32 [P, k], relation int32 [P, k]), descending logit then ascending
+    relation id; (-inf, -1) pads a row with fewer than k candidates.  Does not synchronise."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('distmult_pair_topk: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (tuple(z.shape), tuple(rel_w.shape)))
+    dev = z.device
+    pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
+    n, dim, n_rel, n_p, k = z.shape[0], z.shape[1], rel_w.shape[0], pu.numel(), int(k)
+    out_s = torch.empty((n_p, max(k, 0)), dtype=torch.float32, device=dev)
+    out_r = torch.empty((n_p, max(k, 0)), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().tipk_distmult_pair_topk_workspace_bytes(n, dim, n_rel, n_p, k))
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    check(lib().tipk_distmult_pair_topk(ptr(z), n, dim, ptr(rel_w), n_rel, ptr(pu), ptr(pv), n_p, ptr(keys), ptr(kptr),
+                                        ptr(krel), n_keys, k, ptr(out_s), ptr(out_r), ptr(ws), stream_ptr(dev)),
+          'tipk_distmult_pair_topk')
+    return out_s, out_r
+
+
+def pair_table_pair_topk(s1, s2, pairs, k, known=None):
+    """`distmult_pair_topk` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for both):
+    the logit of (u, v, r) is s1[u, r] + s2[v, r] (not symmetric); `known` drops a relation in either pair direction."""
+    s1, s2 = _f32c(s1), _f32c(s2)
+    require_device(s1, s2)
+    if s1.dim() != 2 or s1.shape != s2.shape:
+        raise _lib.TipkError('pair_table_pair_topk: two tables [n, n_rel] expected, got %s and %s'
+                             % (tuple(s1.shape), tuple(s2.shape)))
+    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1]:
+        s1, s2 = s1.contiguous(), s2.contiguous()
+    dev = s1.device
+    pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
+    n, n_rel, n_p, k = s1.shape[0], s1.shape[1], pu.numel(), int(k)
+    out_s = torch.empty((n_p, max(k, 0)), dtype=torch.float32, device=dev)
+    out_r = torch.empty((n_p, max(k, 0)), dtype=torch.int32, device=dev)
+    check(lib().tipk_pair_table_pair_topk(ptr(s1), ptr(s2), s1.stride(0), n, n_rel, ptr(pu), ptr(pv), n_p, ptr(keys),
+                                          ptr(kptr), ptr(krel), n_keys, k, ptr(out_s), ptr(out_r), stream_ptr(dev)),
+          'tipk_pair_table_pair_topk')
+    return out_s, out_r
+
+
 _DET_WS = {}
 
 
