@@ -94,6 +94,24 @@ int         tipk_device_info(int device, int* n_cu, int* lds_bytes_per_cu, int* 
  * (multiples of 4 when d % 4 == 0; table/out/partial 16-byte aligned in that case).
  * n_table = rows of `table`: below 4 GB a gathered row is addressed as table base + 32-bit byte offset
  * (one multiply per row instead of a 64-bit multiply-add); 0 = unknown (general path).
+ *
+ * Contracts pinned by tests/test_gpu_gather_paths.py (bit for bit against fp64 on exactly representable sums):
+ *   - EVERY output row of the plan is written, rows without edges included: they hold the epilogue of a zero
+ *     sum (relu?(bias), or +0).  Nothing outside columns [0, d) of a row is touched (ld_out > d is a column slice).
+ *   - E = 0: the plan is one empty item per output row and the launch writes those rows; `row_id` must still be
+ *     a non-NULL device address (it is never read) -- n_items > 0 with a NULL table or row_id is TIPK_EINVAL.
+ *     tip_amd.ops passes the item list's address for it.  tipk_gather_rows_csr accepts row_id = NULL for E = 0.
+ *   - Non-finite table values are added as IEEE values (unweighted sums): +-inf / NaN of a table row reach
+ *     exactly the output rows that gather that row (+inf and -inf in one row: NaN) and no other row; lanes
+ *     and slots without an edge load nothing.
+ *   - The 2^32 switch: n_table * ld_table * 4 < 2^32 takes 32-bit UNSIGNED byte offsets (valid up to the last
+ *     row below 4 GiB), anything else (or n_table = 0) 64-bit row addresses -- same results.  tipk_gather_sum
+ *     and tipk_gather_sum_finalize serve both; tipk_gather_sum_riders with colsum, tipk_gather_sum_lin and
+ *     tipk_gather_rows_csr exist with 32-bit offsets only and return TIPK_EUNSUPPORTED from 2^32 bytes on.
+ *   - A table, bias, out or partial that is not 16-byte aligned (or a row stride that is no multiple of 4) takes
+ *     the scalar kernels: d <= 64, and a grouped plan must be built for THEIR lane count (next pow2 of d);
+ *     wider rows are TIPK_EUNSUPPORTED and nothing is written.
+ *   - Two launches on the same inputs give the same bits (fixed summation order, no atomics).
  */
 int tipk_gather_sum(const float* table, int64_t ld_table, int64_t n_table /* rows of table (0 = unknown) */,
                     const int32_t* row_id, const float* edge_w /* nullable */,

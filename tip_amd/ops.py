@@ -58,6 +58,12 @@ class _timed(object):
 # ---------------------------------------------------------------------------------------------
 # launch wrappers (one C call each)
 # ---------------------------------------------------------------------------------------------
+def _row_id_ptr(plan):
+    """The plan's edge ids; a graph WITHOUT edges has none and an empty tensor has no storage (NULL, which the C entries refuse
+    next to a non-empty item list): every item of such a plan is empty and no id is ever read, so any device address serves."""
+    return ptr(plan.row_id if plan.n_edges else plan.items)
+
+
 def gather_sum_epilogue_supported(plan, d):
     """True if `gather_sum(..., gate=, colsum=True, riders=)` runs as ONE launch on this plan (grouped, 1024-thread workgroups)."""
     return bool(not plan.n_slots and plan.items.shape[0] > 0 and d % 4 == 0 and lib().tipk_gather_sum_riders_supported(d, plan.group_slots))
@@ -88,7 +94,7 @@ def gather_sum(plan, table, row_scale=None, bias=None, relu=False, out=None, rid
         if gate is not None:
             assert tuple(gate.shape) == tuple(out.shape) and gate.stride(1) == 1 and gate.dtype == torch.float32
         with _timed('gather_sum[%s,d=%d]+%d sums' % (plan.tag, d, len(riders))):
-            check(L.tipk_gather_sum_riders(ptr(table), table.stride(0), table.shape[0], ptr(plan.row_id), ptr(plan.edge_w),
+            check(L.tipk_gather_sum_riders(ptr(table), table.stride(0), table.shape[0], _row_id_ptr(plan), ptr(plan.edge_w),
                                            ptr(plan.items), plan.items.shape[0], ptr(out), out.stride(0), ptr(row_scale),
                                            ptr(bias), int(relu), d, plan.group_slots, ptr(gate),
                                            gate.stride(0) if gate is not None else 0, ptr(parts), arr, len(riders), st),
@@ -98,7 +104,7 @@ def gather_sum(plan, table, row_scale=None, bias=None, relu=False, out=None, rid
     if plan.n_slots:
         partial = torch.empty((plan.n_slots, d), dtype=torch.float32, device=table.device)
     with _timed('gather_sum[%s,d=%d]' % (plan.tag, d)):
-        check(L.tipk_gather_sum(ptr(table), table.stride(0), table.shape[0], ptr(plan.row_id), ptr(plan.edge_w), ptr(plan.items),
+        check(L.tipk_gather_sum(ptr(table), table.stride(0), table.shape[0], _row_id_ptr(plan), ptr(plan.edge_w), ptr(plan.items),
                                 plan.items.shape[0], ptr(out), out.stride(0), ptr(partial), ptr(row_scale),
                                 ptr(bias), int(relu), d, plan.group_slots, st), 'tipk_gather_sum')
     gather_sum_finish(plan, partial, out, row_scale, bias, relu)
@@ -130,7 +136,7 @@ def gather_sum_lin(plan, table, weight, bias=None, relu=False, row_scale=None):
     agg = torch.empty((plan.n_out, d), dtype=torch.float32, device=table.device)
     out2 = torch.empty((plan.n_out, d2), dtype=torch.float32, device=table.device)
     with _timed('gather_sum_lin[%s,d=%d->%d]' % (plan.tag, d, d2)):
-        check(lib().tipk_gather_sum_lin(ptr(table), table.stride(0), table.shape[0], ptr(plan.row_id), ptr(plan.edge_w),
+        check(lib().tipk_gather_sum_lin(ptr(table), table.stride(0), table.shape[0], _row_id_ptr(plan), ptr(plan.edge_w),
                                         ptr(plan.items), plan.items.shape[0], ptr(agg), agg.stride(0), ptr(row_scale),
                                         ptr(weight), weight.stride(0), weight.stride(1), ptr(bias), int(relu), ptr(out2),
                                         out2.stride(0), d, d2, plan.group_slots, stream_ptr(table.device)), 'tipk_gather_sum_lin')
