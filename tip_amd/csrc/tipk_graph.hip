@@ -848,6 +848,9 @@ extern "C" int tipk_gcn_bwd(const tipk_graph* g, const float* x, int64_t ld_x, i
         return TIPK_EINVAL;
     const int64_t n = g->n_nodes;
     if (workspace_bytes < tipk_gcn_workspace_bytes(g, d_in, d_out) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return TIPK_EINVAL;
+    // support is decided before the first launch: an unsupported call leaves every output untouched.  Identity features: d W is
+    // the transposed aggregate written in place (unit-stride columns); dense x: the rows of d W are contiguous
+    if (x ? gw_si != 1 : gw_so != 1) return TIPK_EUNSUPPORTED;
     hipStream_t hs = (hipStream_t)stream;
     char* wp = (char*)workspace;
     float* gp_buf = (float*)wp;
@@ -864,16 +867,15 @@ extern "C" int tipk_gcn_bwd(const tipk_graph* g, const float* x, int64_t ld_x, i
     // d (x W^T) = A_hat^T g'
     float* gxl_out = gxl;
     int64_t ld_gxl = d_out;
-    if (!x && gw_so == 1) { gxl_out = g_weight; ld_gxl = gw_si; }              // identity features: d W = (d lin)^T, written in place
+    if (!x) { gxl_out = g_weight; ld_gxl = gw_si; }                            // identity features: d W = (d lin)^T, written in place
     GrArgs a;
     memset(&a, 0, sizeof(a));
     a.table = gp; a.ld_t = ld_gp; a.ptr = g->bwd_ptr; a.row = g->bwd_row; a.n_out = n; a.edge_w = g->bwd_w; a.d = d_out; a.plan = g->pb;
     a.out = gxl_out; a.ld_out = ld_gxl;
     if ((st = gr_launch(a, hs)) != TIPK_OK) return st;
-    if (!x) return gw_so == 1 ? TIPK_OK : TIPK_EUNSUPPORTED;
+    if (!x) return TIPK_OK;
     // d W (o, i) = sum_v gxl[v, o] x[v, i];  d x = gxl W
     tipk_gemm_desc d = gemm_desc(d_out, d_in, n, gxl, 1, d_out, x, ld_x, 1, g_weight, gw_so);
-    if (gw_si != 1) return TIPK_EUNSUPPORTED;
     if ((st = reduce_gemm(d, scratch + align256(256 * (int64_t)d_out * 4) / 4, stream)) != TIPK_OK) return st;
     if (g_x) {
         d = gemm_desc(n, d_in, d_out, gxl, d_out, 1, weight, w_so, w_si, g_x, ld_gx);

@@ -104,7 +104,7 @@ def _sparse_feature_graph(x, chunk):
     xc = x.coalesce()
     r, c, v = xc.indices()[0], xc.indices()[1], xc.values().to(torch.float32)
     n, m = x.shape
-    return ops.AggGraph(build_gather_plan(r, c, n, m, v, chunk), build_gather_plan(c, r, m, n, v, chunk))
+    return ops.AggGraph(build_gather_plan(r, c, n, m, v, chunk, 'feat.fwd'), build_gather_plan(c, r, m, n, v, chunk, 'feat.bwd'))
 
 
 class _FeatureInput(nn.Module):

@@ -1959,13 +1959,14 @@ class _DrugMix(torch.autograd.Function):
     def forward(ctx, xd, pd, d_norm, cat):
         xd, pd = _f32c(xd), _f32c(pd)
         n, ne = xd.shape
-        if cat:
-            out = torch.empty((n, ne + pd.shape[1]), dtype=torch.float32, device=xd.device)
-            rows_affine(xd, row_div=d_norm, out=out[:, :ne])
-            rows_affine(pd, out=out[:, ne:])
-        else:
-            out = rows_affine(xd, row_div=d_norm)
-            rows_affine(pd, out=out, accumulate=True)
+        with _timed('drug_mix[%dx%d,%s]' % (n, pd.shape[1], 'cat' if cat else 'add')):      # (spans two launches, whose own labels are recorded as well)
+            if cat:
+                out = torch.empty((n, ne + pd.shape[1]), dtype=torch.float32, device=xd.device)
+                rows_affine(xd, row_div=d_norm, out=out[:, :ne])
+                rows_affine(pd, out=out[:, ne:])
+            else:
+                out = rows_affine(xd, row_div=d_norm)
+                rows_affine(pd, out=out, accumulate=True)
         ctx.cat, ctx.ne = cat, ne
         ctx.save_for_backward(d_norm)
         return out
@@ -1998,18 +1999,20 @@ class _DrugMixMM(torch.autograd.Function):
         ctx.fused = p <= 64 and pd_dim <= 64 and weight.is_contiguous() and d_norm.is_contiguous()
         if ctx.fused:                                                     # scaling, cat | add and the dense map: one launch
             out = torch.empty((n, ne + pd_dim if cat else ne), dtype=torch.float32, device=xd.device)
-            check(lib().tipk_drug_mix_fwd(ptr(xd), xd.stride(0), ptr(d_norm), ptr(mean), mean.stride(0), ptr(weight), p, pd_dim,
-                                          n, ne, int(cat), ptr(out), out.stride(0), stream_ptr(xd.device)), 'tipk_drug_mix_fwd')
+            with _timed('drug_mix_mm[%dx%dx%d,fused]' % (n, p, pd_dim)):
+                check(lib().tipk_drug_mix_fwd(ptr(xd), xd.stride(0), ptr(d_norm), ptr(mean), mean.stride(0), ptr(weight), p, pd_dim,
+                                              n, ne, int(cat), ptr(out), out.stride(0), stream_ptr(xd.device)), 'tipk_drug_mix_fwd')
             ctx.cat, ctx.ne = cat, ne
             ctx.save_for_backward(mean, weight, d_norm)
             return out
-        if cat:
-            out = torch.empty((n, ne + pd_dim), dtype=torch.float32, device=xd.device)
-            rows_affine(xd, row_div=d_norm, out=out[:, :ne])
-            gemm(mean, weight, out=out[:, ne:])
-        else:
-            out = rows_affine(xd, row_div=d_norm)
-            gemm(mean, weight, out=out, c_in=out)
+        with _timed('drug_mix_mm[%dx%dx%d,unfused]' % (n, p, pd_dim)):                       # (spans two launches, whose own labels are recorded as well)
+            if cat:
+                out = torch.empty((n, ne + pd_dim), dtype=torch.float32, device=xd.device)
+                rows_affine(xd, row_div=d_norm, out=out[:, :ne])
+                gemm(mean, weight, out=out[:, ne:])
+            else:
+                out = rows_affine(xd, row_div=d_norm)
+                gemm(mean, weight, out=out, c_in=out)
         ctx.cat, ctx.ne = cat, ne
         ctx.save_for_backward(mean, weight, d_norm)
         return out
