@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 26
+#define TIPK_ABI_VERSION 27
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -55,6 +55,8 @@ const char* tipk_build_id(void);
  *                            (section 4c; both routes return the same bits)
  *      "pair_topk_stream"    1 = tipk_distmult_pair_topk streams rel_w through LDS in tiles even where all of it fits
  *                            (section 4d; both routes return the same bits)
+ *      "regimen_global"      1 = tipk_distmult_regimen_topk reads rel_w rows from global memory even where the LDS image
+ *                            fits (section 4e; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -823,6 +825,66 @@ int     tipk_pair_table_pair_topk(const float* s1, const float* s2, int64_t ld, 
                                   const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
                                   int64_t n_known_pairs /* nullable together */,
                                   int k, float* out_score, int32_t* out_rel, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4e. Regimen top-k: the k best relations (side effects) of every drug LIST, aggregated over the list's pairs, with the pair
+ *     that drives each (serving; polypharmacy beyond one pair; no reference call site).
+ *
+ *   Regimen lists, CSR, DEVICE: reg_drugs int32 [n_entries], reg_ptr int64 [n_regimens + 1].  Regimen g is the list
+ *   d_0 .. d_{m-1} = reg_drugs[reg_ptr[g] .. reg_ptr[g+1]); its pairs are the POSITION pairs (i, j), i < j, in lexicographic
+ *   order, with u = d_i and v = d_j.  Equal ids at two positions are scored as a self pair, as 4d does.
+ *   Logit of a triple (pair, r): exactly that of 4d.  DistMult: h_k = z[u,k] * z[v,k] rounded once, then
+ *   acc = fmaf(h_k, w[r,k], acc) for k ascending from 0.  Table variant: the single fp32 add s1[u,r] + s2[v,r], u being the
+ *   EARLIER list position.
+ *   Skipped triples: a triple contributes nothing when it is KNOWN -- listed for the pair's unordered key in the pair-major
+ *   lists (known_pair_keys, known_pair_ptr, known_rel) of 4d, nullable together -- or when its logit is NaN.  A relation
+ *   whose every triple is skipped is not a candidate.
+ *   Aggregate per (regimen, relation), chosen by `aggregate`:
+ *     TIPK_REGIMEN_MAX       A = the largest contributing logit; exact: the score is bit-identical to that triple's 4d logit.
+ *     TIPK_REGIMEN_NOISY_OR  A = sum over the contributing triples, in pair order, in fp32 (A starts at 0.0f and each term is
+ *                            added with one rounding), of
+ *                                softplus(s) = fmaxf(s, 0) + log1pf(expf(-fabsf(s)))
+ *                            which is -log(1 - P) of the noisy-or probability P = 1 - prod (1 - sigma(s)).  The ranking is
+ *                            on A, not on P: P saturates to 1 in fp32.  P = -expm1(-A).
+ *   Driver pair, for either aggregate: the positions (i, j) of the contributing triple with the largest logit, ties to the
+ *   first in pair order, packed i | j << 16 into an int32.
+ *   Output per regimen (device): the k best relations by (A descending, relation id ascending) in out_score fp32
+ *   [n_regimens x k], out_rel int32 [n_regimens x k], out_pair int32 [n_regimens x k]; a row with fewer than k candidates
+ *   is padded with (-inf, -1, -1).  A regimen with fewer than 2 entries, with more than tipk_regimen_max_drugs() entries
+ *   (64) or with any drug id outside [0, n_nodes) gets a fully padded row and nothing of it is read out of bounds.
+ *   The result is a set fixed by that total order and is BITWISE repeatable (the noisy-or sum has a fixed order).
+ *   Routes (DistMult): rel_w is staged in LDS once per workgroup when it fits beside the wavefronts' state
+ *   (tipk_distmult_regimen_topk_lds_route: 1 097 x 16 does); otherwise, or under option "regimen_global", every lane reads
+ *   its rows from global memory; same bits.
+ *   Supported: as 4d -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; rel_w 16-byte aligned), 1 <= n_rel <=
+ *   65 536, 1 <= k <= 128; regimen length 2..tipk_regimen_max_drugs().
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k <= 0, a negative size, n_nodes or n_rel < 1,
+ *   ld < n_rel, an unknown `aggregate`, a NULL required pointer (reg_ptr, reg_drugs, the tables, the three outputs; with
+ *   n_regimens > 0), known arrays given only in part; then TIPK_EUNSUPPORTED outside the supported range; n_regimens == 0
+ *   is TIPK_OK with no launch; TIPK_OK implies correct numbers.
+ *   workspace: tipk_distmult_regimen_topk_workspace_bytes(...) bytes (-1: unsupported); every list lives in LDS, so this is
+ *   0 for every supported shape today and `workspace` may then be NULL.
+ *   Nothing lives in host memory: these entries do NOT synchronise and may be captured into a hipGraph.
+ */
+#define TIPK_REGIMEN_MAX      0
+#define TIPK_REGIMEN_NOISY_OR 1
+int     tipk_regimen_max_drugs(void);
+int     tipk_distmult_regimen_topk_supported(int64_t n_nodes, int dim, int64_t n_rel, int k);
+int64_t tipk_distmult_regimen_topk_workspace_bytes(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_regimens, int k);
+int     tipk_distmult_regimen_topk_lds_route(int dim, int64_t n_rel);   /* 1 = rel_w is staged in LDS once (options apply) */
+int     tipk_distmult_regimen_topk(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                   const int32_t* reg_drugs, const int64_t* reg_ptr /* device */, int64_t n_regimens,
+                                   const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                   int64_t n_known_pairs /* nullable together */,
+                                   int aggregate, int k, float* out_score, int32_t* out_rel, int32_t* out_pair,
+                                   void* workspace, tipk_stream_t stream);
+int     tipk_pair_table_regimen_topk_supported(int64_t n_nodes, int64_t n_rel, int k);
+int     tipk_pair_table_regimen_topk(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                     const int32_t* reg_drugs, const int64_t* reg_ptr /* device */, int64_t n_regimens,
+                                     const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                     int64_t n_known_pairs /* nullable together */,
+                                     int aggregate, int k, float* out_score, int32_t* out_rel, int32_t* out_pair,
+                                     tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

@@ -34,7 +34,8 @@ enum {
     TIPK_OPT_DM_TASK_KERNEL = 7,      // fused objective through distmult_task_kernel (k / 4 lanes per position) -- A/B runs
     TIPK_OPT_SCREEN_SEARCH = 8,       // tipk_distmult_screen: known-pair filter by binary search even where the LDS bitmap fits
     TIPK_OPT_PAIR_TOPK_STREAM = 9,    // tipk_distmult_pair_topk: rel_w streamed through LDS in tiles even where all of it fits
-    TIPK_OPT_COUNT = 10
+    TIPK_OPT_REGIMEN_GLOBAL = 10,     // tipk_distmult_regimen_topk: rel_w rows read from global memory even where the LDS image fits
+    TIPK_OPT_COUNT = 11
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

@@ -15,8 +15,7 @@
 //   wave's LDS buffer by ballot; when the buffer reaches max(64, 2k) entries (at most 192 of 256) the wave sorts it (bitonic,
 //   logit desc, relation asc) and keeps k, which raises the threshold.  Dropping a candidate below the threshold is exact:
 //   k kept entries are better.  The result is a set fixed by the total order, whatever the order of the appends.
-#include "tipk_common.h"
-#include <math.h>
+#include "tipk_wave_topk.h"
 
 namespace {
 
@@ -30,7 +29,7 @@ constexpr int64_t PT_RMAX = 65536;
 constexpr int PT_WIN = 2048;                // relations per bitmap window (64 words: lane l clears word l)
 constexpr int PT_LDS_BYTES = 152 * 1024;    // dynamic LDS a workgroup may ask for
 constexpr int PT_TILE_BYTES = 48 * 1024;    // rel_w tile of the streamed route (at least 64 rows)
-constexpr int PT_REL_PAD = 0x7fffffff;
+constexpr int PT_REL_PAD = WT_REL_PAD;
 
 enum { PT_DISTMULT = 0, PT_DISTMULT16 = 1, PT_TABLE = 2 };
 
@@ -47,61 +46,6 @@ struct PairTopkArgs {
     float* out_s;
     int32_t* out_r;
 };
-
-__device__ __forceinline__ void wave_sync() {                  // LDS written by this wave is visible to this wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool better(float sa, int ra, float sb, int rb) {
-    return sa > sb || (sa == sb && ra < rb);
-}
-
-// index of `key` in the strictly ascending keys [0, n), or -1: every lane calls it with the same arguments and gets the
-// same answer; the 64 lanes probe 64 keys per step
-__device__ int64_t find_key(const int64_t* keys, int64_t n, int64_t key, int lane) {
-    const int64_t big = 0x7fffffffffffffffLL;
-    int64_t lo = 0, hi = n;
-    while (hi - lo > TIPK_WAVE) {
-        const int64_t step = (hi - lo + TIPK_WAVE - 1) / TIPK_WAVE;
-        const int64_t idx = lo + (int64_t)lane * step;
-        const int64_t v = idx < hi ? keys[idx] : big;
-        const int c = __popcll(__ballot(v <= key));              // the probes ascend: the lanes with v <= key are a prefix
-        if (c == 0) return -1;
-        lo += (int64_t)(c - 1) * step;
-        hi = lo + step < hi ? lo + step : hi;
-    }
-    const int64_t idx = lo + lane;
-    const int64_t v = idx < hi ? keys[idx] : big;
-    const unsigned long long m = __ballot(idx < hi && v == key);
-    return m ? lo + (__ffsll((long long)m) - 1) : -1;
-}
-
-// sort the wave's c buffer entries best first and keep k of them (the whole wave, uniform)
-__device__ void flush(float* bs, int* br, int& c, float& thr, int k, int lane) {
-    int p = TIPK_WAVE;
-    while (p < c) p <<= 1;
-    wave_sync();
-    for (int i = c + lane; i < p; i += TIPK_WAVE) { bs[i] = -INFINITY; br[i] = PT_REL_PAD; }
-    wave_sync();
-    for (int size = 2; size <= p; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int x = lane; x < (p >> 1); x += TIPK_WAVE) {
-                const int i = 2 * stride * (x / stride) + (x % stride), j = i + stride;
-                const float si = bs[i], sj = bs[j];
-                const int ri = br[i], rj = br[j];
-                const bool up = (i & size) == 0;
-                if (up ? better(sj, rj, si, ri) : better(si, ri, sj, rj)) {
-                    bs[i] = sj; br[i] = rj; bs[j] = si; br[j] = ri;
-                }
-            }
-            wave_sync();
-        }
-    }
-    c = c < k ? c : k;
-    thr = c == k ? bs[k - 1] : -INFINITY;
-}
 
 // rows [t0, t0 + rows) of rel_w into the LDS image (row stride a.stride floats), the whole workgroup
 __device__ __forceinline__ void stage_rows(const PairTopkArgs& a, float* Ws, int t0, int rows) {
@@ -233,13 +177,13 @@ __global__ void __launch_bounds__(PT_NT) pair_topk_kernel(PairTopkArgs a) {
                         br[pos] = r;
                     }
                     c += __popcll(mask);
-                    if (c >= flush_at) flush(bs, br, c, thr, k, lane);
+                    if (c >= flush_at) flush<false>(bs, br, nullptr, c, thr, k, lane);
                 }
             }
         }
 
         if (p < a.n_pairs) {
-            if (c > 0) flush(bs, br, c, thr, k, lane);
+            if (c > 0) flush<false>(bs, br, nullptr, c, thr, k, lane);
             float* os = a.out_s + p * k;
             int32_t* orl = a.out_r + p * k;
             for (int i = lane; i < k; i += TIPK_WAVE) {
@@ -251,8 +195,7 @@ __global__ void __launch_bounds__(PT_NT) pair_topk_kernel(PairTopkArgs a) {
     }
 }
 
-// LDS row stride of the rel_w image: dim or dim + 4 floats, whichever has stride / 4 odd
-int pt_stride(int dim) { return ((dim >> 2) & 1) ? dim : dim + 4; }
+int pt_stride(int dim) { return wt_stride(dim); }
 
 int64_t pt_fixed_bytes(int dim, bool table) {
     return (table ? 0 : (int64_t)PT_NW * dim * 4) + (int64_t)PT_NW * PT_CAP * 8 + (int64_t)PT_NW * (PT_WIN / 32) * 4;
@@ -267,13 +210,7 @@ int pt_stream_tile(int dim) {
     return rows < TIPK_WAVE ? TIPK_WAVE : rows;
 }
 
-int pt_cu_count() {
-    int dev = 0, n_cu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        n_cu = prop.multiProcessorCount;
-    return n_cu;
-}
+int pt_cu_count() { return wt_cu_count(); }
 
 int pt_check_lists(int64_t n_nodes, int64_t n_rel, const int32_t* pair_u, const int32_t* pair_v, int64_t n_pairs,
                    const int64_t* keys, const int64_t* kptr, const int32_t* krel, int64_t n_known, int k,

@@ -33,6 +33,7 @@ EPS = 1e-13                    # src/layers.py:15
 ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
+RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP']
@@ -816,6 +817,52 @@ class MultiInnerProductDecoder(nn.Module):
             w = w[relations]
         return ops.distmult_pair_topk(z.detach(), w, pairs, k, known)
 
+    def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
+        """Regimen top-k (extension, `tipk_distmult_regimen_topk`): the k best relations of every drug list of the CSR pair
+        (reg_drugs, reg_ptr) by the aggregate of its pairs' LOGITS -> (score [G, k], relation int32 [G, k], pair_i, pair_j
+        int32 [G, k]: list positions of the driving pair); no autograd.  known and relations as `top_relations`."""
+        w = self.weight.detach()
+        if relations is not None:
+            w = w[relations]
+        return ops.distmult_regimen_topk(z.detach(), w, reg_drugs, reg_ptr, k, aggregate, known)
+
+
+def normalize_regimens(regimens, n_drug, max_drugs):
+    """Host normalisation of `TIP.regimen_side_effects`: a list of lists of drug ids, or a (drugs, ptr) pair of int tensors
+    (regimen g = drugs[ptr[g]:ptr[g + 1]]) -> (drugs int32, ptr int64) on the host with every regimen sorted ascending and
+    de-duplicated.  ValueError for an id outside [0, n_drug), a regimen of more than max_drugs distinct drugs, or lists
+    that are not what the above says."""
+    if isinstance(regimens, tuple) and len(regimens) == 2 and all(torch.is_tensor(t) for t in regimens):
+        drugs, ptr = (t.detach().to('cpu') for t in regimens)
+        if drugs.dim() != 1 or ptr.dim() != 1 or ptr.numel() < 1 or drugs.dtype.is_floating_point or ptr.dtype.is_floating_point:
+            raise ValueError('regimens: int tensors (drugs [n_entries], ptr [G + 1]) expected, got %s %s and %s %s'
+                             % (drugs.dtype, tuple(drugs.shape), ptr.dtype, tuple(ptr.shape)))
+        ptr = ptr.to(torch.int64)
+        size = ptr[1:] - ptr[:-1]
+        if int(ptr[0]) != 0 or int(ptr[-1]) != drugs.numel() or bool((size < 0).any()):
+            raise ValueError('regimens: ptr must ascend from 0 to the number of entries (%d)' % drugs.numel())
+        drugs = drugs.to(torch.int64)
+    else:
+        try:
+            lists = [[int(x) for x in g] for g in regimens]
+        except (TypeError, ValueError):
+            raise ValueError('regimens: a list of lists of drug ids, or a (drugs, ptr) tensor pair expected') from None
+        size = torch.tensor([len(g) for g in lists], dtype=torch.int64)
+        drugs = torch.tensor([x for g in lists for x in g], dtype=torch.int64)
+    if drugs.numel():
+        lo, hi = int(drugs.min()), int(drugs.max())
+        if lo < 0 or hi >= n_drug:
+            raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, n_drug))
+    owner = torch.repeat_interleave(torch.arange(size.numel()), size)
+    uniq = torch.unique(owner * max(1, int(n_drug)) + drugs)            # sorted by (regimen, id), duplicates gone
+    owner = torch.div(uniq, max(1, int(n_drug)), rounding_mode='floor')
+    size = torch.bincount(owner, minlength=size.numel())
+    if size.numel() and int(size.max()) > max_drugs:
+        raise ValueError('a regimen of %d distinct drugs: at most %d are ranked' % (int(size.max()), max_drugs))
+    ptr = torch.zeros(size.numel() + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(size, 0)
+    return (uniq % max(1, int(n_drug))).to(torch.int32), ptr
+
 
 def screen_queries(num_et, relations=None, drugs=None):
     """int32 [Q, 2] (relation, drug | -1) on the host, in the order `MultiInnerProductDecoder.screen` documents."""
@@ -903,6 +950,17 @@ class NNDecoder(nn.Module):
             s1 = ops.matmul(p, w1.t())
             s2 = ops.matmul(q, w2.t())
         return ops.pair_table_pair_topk(s1, s2, pairs, k, known)
+
+    def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
+        """Regimen top-k (extension, `tipk_pair_table_regimen_topk`) on the two tables `forward` forms; arguments and result
+        as `MultiInnerProductDecoder.top_regimen_relations`.  The earlier list position is the decoder's first argument."""
+        with torch.no_grad():
+            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
+            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
+            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
+            s1 = ops.matmul(p, w1.t())
+            s2 = ops.matmul(q, w2.t())
+        return ops.pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate, known)
 
     def objective(self, z, pos_index, neg_index, edge_type):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps) (src/layers.py:335-340 with this decoder as
@@ -1113,16 +1171,7 @@ class TIP(nn.Module):
         rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
         if rel is not None and known is not None:
             # the lists hold global ids: keep the candidates' entries and renumber them to positions in `relations`
-            keys, kptr, krel = known
-            pos = torch.full((d.n_dd_et,), -1, dtype=torch.int64, device=dev)
-            pos[rel] = torch.arange(rel.numel(), device=dev)
-            owner = torch.repeat_interleave(torch.arange(keys.numel(), device=dev), kptr[1:] - kptr[:-1])
-            new = pos[krel.long()]
-            keep = new >= 0
-            order = torch.sort(owner[keep] * max(1, rel.numel()) + new[keep]).indices
-            kptr2 = torch.zeros_like(kptr)
-            kptr2[1:] = torch.cumsum(torch.bincount(owner[keep], minlength=keys.numel()), 0)
-            known = (keys, kptr2, new[keep][order].to(torch.int32))
+            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
         with torch.no_grad():
             logit, idx = self.decoder.top_relations(self.embeddings, pairs, k, known, rel)
             score = torch.sigmoid(logit) if sigmoid else logit
@@ -1130,6 +1179,50 @@ class TIP(nn.Module):
             if rel is not None:
                 idx = torch.where(idx >= 0, rel[idx.clamp(min=0)], idx)
         return SideEffects(score, idx)
+
+    def regimen_side_effects(self, regimens, k=10, aggregate='noisy_or', exclude=None, relations=None, probability=True):
+        """Serving (extension): the k side effects the model expects most from every drug REGIMEN (a medication list), and the
+        two drugs of the list that drive each (`decoder.top_regimen_relations`: one `tipk_distmult_regimen_topk` /
+        `tipk_pair_table_regimen_topk` launch on `self.embeddings`, under no_grad; both decoder kinds).
+        regimens: a list of lists of drug ids, or a (drugs, ptr) pair of int tensors (CSR).  Every regimen is sorted
+        ascending and de-duplicated on the host (`normalize_regimens`), so u < v always; a regimen of 0 or 1 drugs gives a
+        padded row.  aggregate: 'noisy_or' ranks a side effect by sum softplus(logit) over the regimen's pairs, i.e. by the
+        probability that at least one pair causes it; 'max' by its largest pair logit.  exclude / relations: as
+        `side_effects` -- a recorded (pair, side effect) does not contribute.  probability = True maps the score after the
+        kernel: sigmoid(A) for 'max', -expm1(-A) for 'noisy_or' (padding: score 0, relation -1, u = v = -1).
+        -> RegimenSideEffects(score [G, k], relation int64 [G, k], u int64 [G, k], v int64 [G, k]) on the model's device."""
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
+                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
+        if exclude not in ('train', 'all', None):
+            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        if aggregate not in ops.REGIMEN_AGGREGATES:
+            raise ValueError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+        d = self.data
+        drugs, ptr = normalize_regimens(regimens, d.n_drug, ops.regimen_max_drugs())
+        dev = self.embeddings.device
+        both = torch.cat([ptr, drugs.to(torch.int64)]).to(dev)          # one upload
+        ptr_d, drugs_d = both[:ptr.numel()], both[ptr.numel():]
+        known = None
+        if exclude is not None:
+            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
+            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
+        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
+        if rel is not None and known is not None:
+            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        with torch.no_grad():
+            score, idx, pi, pj = self.decoder.top_regimen_relations(self.embeddings, drugs_d, ptr_d, k, aggregate, known, rel)
+            if probability:
+                score = torch.sigmoid(score) if aggregate == 'max' \
+                    else torch.where(idx >= 0, -torch.expm1(-score), torch.zeros_like(score))   # (padding: -expm1(inf))
+            idx, have = idx.to(torch.int64), idx >= 0
+            if rel is not None:
+                idx = torch.where(have, rel[idx.clamp(min=0)], idx)
+            lookup = drugs_d if drugs_d.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+            first, none = ptr_d[:-1, None], torch.full_like(idx, -1)
+            u = torch.where(have, lookup[(first + pi).clamp(min=0, max=lookup.numel() - 1)], none)
+            v = torch.where(have, lookup[(first + pj).clamp(min=0, max=lookup.numel() - 1)], none)
+        return RegimenSideEffects(score, idx, u, v)
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

@@ -1123,13 +1123,9 @@ def known_relations_by_pair(edge_index, range_list, n_nodes, extra=None):
     return hit
 
 
-def _pair_topk_lists(pairs, known, dev):
-    """(pair_u, pair_v int32 [P], keys, ptr, rel, n_keys) of the pair top-k entries, all on `dev`."""
-    pairs = torch.as_tensor(pairs)
-    require_device(pairs)
-    if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype.is_floating_point:
-        raise _lib.TipkError('pairs: an int tensor [2, P] expected, got %s %s' % (pairs.dtype, tuple(pairs.shape)))
-    pu, pv = pairs[0].to(torch.int32).contiguous(), pairs[1].to(torch.int32).contiguous()
+def _known_lists(known):
+    """(keys, ptr, rel, n_keys) of a pair-major known list for the C entries: device tensors of the entries' types, or
+    (None, None, None, 0) when there is nothing to drop."""
     keys = kptr = krel = None
     n_keys = 0
     if known is not None:
@@ -1143,6 +1139,17 @@ def _pair_topk_lists(pairs, known, dev):
         if n_keys == 0 or krel.numel() == 0:                             # nothing to drop (empty tensors have no address)
             keys = kptr = krel = None
             n_keys = 0
+    return keys, kptr, krel, n_keys
+
+
+def _pair_topk_lists(pairs, known, dev):
+    """(pair_u, pair_v int32 [P], keys, ptr, rel, n_keys) of the pair top-k entries, all on `dev`."""
+    pairs = torch.as_tensor(pairs)
+    require_device(pairs)
+    if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype.is_floating_point:
+        raise _lib.TipkError('pairs: an int tensor [2, P] expected, got %s %s' % (pairs.dtype, tuple(pairs.shape)))
+    pu, pv = pairs[0].to(torch.int32).contiguous(), pairs[1].to(torch.int32).contiguous()
+    keys, kptr, krel, n_keys = _known_lists(known)
     return pu, pv, keys, kptr, krel, n_keys
 
 
@@ -1189,6 +1196,99 @@ def pair_table_pair_topk(s1, s2, pairs, k, known=None):
                                           ptr(kptr), ptr(krel), n_keys, k, ptr(out_s), ptr(out_r), stream_ptr(dev)),
           'tipk_pair_table_pair_topk')
     return out_s, out_r
+
+
+def restrict_known_relations(known, relations, n_rel):
+    """The pair-major lists `known` (global relation ids in [0, n_rel)) cut down to the candidate ids `relations` (int64
+    tensor on the lists' device, distinct) and renumbered to POSITIONS in `relations`: same keys, a pair's block keeps the
+    candidates' entries only, ascending by position.  What the top-k entries need when they rank a subset of relations."""
+    keys, kptr, krel = known
+    dev = keys.device
+    pos = torch.full((int(n_rel),), -1, dtype=torch.int64, device=dev)
+    pos[relations] = torch.arange(relations.numel(), device=dev)
+    owner = torch.repeat_interleave(torch.arange(keys.numel(), device=dev), kptr[1:] - kptr[:-1])
+    new = pos[krel.long()]
+    keep = new >= 0
+    order = torch.sort(owner[keep] * max(1, relations.numel()) + new[keep]).indices
+    kptr2 = torch.zeros_like(kptr)
+    kptr2[1:] = torch.cumsum(torch.bincount(owner[keep], minlength=keys.numel()), 0)
+    return keys, kptr2, new[keep][order].to(torch.int32)
+
+
+REGIMEN_AGGREGATES = {'max': 0, 'noisy_or': 1}                          # TIPK_REGIMEN_MAX, TIPK_REGIMEN_NOISY_OR
+
+
+def regimen_max_drugs():
+    """The longest regimen the regimen top-k entries rank (include/tipk.h section 4e)."""
+    return int(lib().tipk_regimen_max_drugs())
+
+
+def _regimen_args(reg_drugs, reg_ptr, k, aggregate, known, dev):
+    if aggregate not in REGIMEN_AGGREGATES:
+        raise _lib.TipkError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+    reg_drugs, reg_ptr = torch.as_tensor(reg_drugs), torch.as_tensor(reg_ptr)
+    require_device(reg_drugs, reg_ptr)
+    if reg_drugs.dim() != 1 or reg_ptr.dim() != 1 or reg_ptr.numel() < 1 or reg_drugs.dtype.is_floating_point \
+            or reg_ptr.dtype.is_floating_point:
+        raise _lib.TipkError('regimens: int tensors reg_drugs [n_entries] and reg_ptr [n_regimens + 1] expected, got %s %s '
+                             'and %s %s' % (reg_drugs.dtype, tuple(reg_drugs.shape), reg_ptr.dtype, tuple(reg_ptr.shape)))
+    drugs, rptr = reg_drugs.to(torch.int32).contiguous(), reg_ptr.to(torch.int64).contiguous()
+    if drugs.numel() == 0:                                               # an empty tensor has no address
+        drugs = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_g, k = rptr.numel() - 1, int(k)
+    out_s = torch.empty((n_g, max(k, 0)), dtype=torch.float32, device=dev)
+    out_r = torch.empty((n_g, max(k, 0)), dtype=torch.int32, device=dev)
+    out_p = torch.empty((n_g, max(k, 0)), dtype=torch.int32, device=dev)
+    return drugs, rptr, n_g, k, REGIMEN_AGGREGATES[aggregate], _known_lists(known), out_s, out_r, out_p
+
+
+def _regimen_result(out_s, out_r, out_p):
+    have = out_p >= 0
+    return out_s, out_r, torch.where(have, out_p & 0xffff, out_p), torch.where(have, out_p >> 16, out_p)
+
+
+def distmult_regimen_topk(z, rel_w, reg_drugs, reg_ptr, k, aggregate='max', known=None):
+    """The k best relations of every drug list by the DistMult logits of its pairs, aggregated (include/tipk.h section 4e).
+
+    reg_drugs int [n_entries], reg_ptr int [G + 1] on the device: regimen g is reg_drugs[reg_ptr[g]:reg_ptr[g + 1]], its
+    pairs are the position pairs i < j.  aggregate: 'max' (the largest logit) or 'noisy_or' (sum of softplus(logit) =
+    -log(1 - P)).  known: None or the pair-major lists of `known_relations_by_pair` on the device: a known triple
+    contributes nothing.  -> (score float32 [G, k], relation int32 [G, k], pair_i int32 [G, k], pair_j int32 [G, k]):
+    descending score then ascending relation id, (pair_i, pair_j) the list positions of the pair with the largest logit;
+    (-inf, -1, -1, -1) pads a row with fewer than k candidates.  Does not synchronise."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('distmult_regimen_topk: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (tuple(z.shape), tuple(rel_w.shape)))
+    dev = z.device
+    drugs, rptr, n_g, k, agg, (keys, kptr, krel, n_keys), out_s, out_r, out_p = _regimen_args(reg_drugs, reg_ptr, k,
+                                                                                              aggregate, known, dev)
+    n, dim, n_rel = z.shape[0], z.shape[1], rel_w.shape[0]
+    check(lib().tipk_distmult_regimen_topk(ptr(z), n, dim, ptr(rel_w), n_rel, ptr(drugs), ptr(rptr), n_g, ptr(keys),
+                                           ptr(kptr), ptr(krel), n_keys, agg, k, ptr(out_s), ptr(out_r), ptr(out_p), None,
+                                           stream_ptr(dev)), 'tipk_distmult_regimen_topk')
+    return _regimen_result(out_s, out_r, out_p)
+
+
+def pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate='max', known=None):
+    """`distmult_regimen_topk` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for
+    both): the logit of the position pair i < j under r is s1[d_i, r] + s2[d_j, r]."""
+    s1, s2 = _f32c(s1), _f32c(s2)
+    require_device(s1, s2)
+    if s1.dim() != 2 or s1.shape != s2.shape:
+        raise _lib.TipkError('pair_table_regimen_topk: two tables [n, n_rel] expected, got %s and %s'
+                             % (tuple(s1.shape), tuple(s2.shape)))
+    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1] or s1.stride(1) != 1 or s2.stride(1) != 1:
+        s1, s2 = s1.contiguous(), s2.contiguous()
+    dev = s1.device
+    drugs, rptr, n_g, k, agg, (keys, kptr, krel, n_keys), out_s, out_r, out_p = _regimen_args(reg_drugs, reg_ptr, k,
+                                                                                              aggregate, known, dev)
+    n, n_rel = s1.shape[0], s1.shape[1]
+    check(lib().tipk_pair_table_regimen_topk(ptr(s1), ptr(s2), s1.stride(0), n, n_rel, ptr(drugs), ptr(rptr), n_g,
+                                             ptr(keys), ptr(kptr), ptr(krel), n_keys, agg, k, ptr(out_s), ptr(out_r),
+                                             ptr(out_p), stream_ptr(dev)), 'tipk_pair_table_regimen_topk')
+    return _regimen_result(out_s, out_r, out_p)
 
 
 _DET_WS = {}
