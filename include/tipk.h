@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 27
+#define TIPK_ABI_VERSION 28
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -57,6 +57,8 @@ const char* tipk_build_id(void);
  *                            (section 4d; both routes return the same bits)
  *      "regimen_global"      1 = tipk_distmult_regimen_topk reads rel_w rows from global memory even where the LDS image
  *                            fits (section 4e; both routes return the same bits)
+ *      "pair_rank_stream"    1 = tipk_distmult_pair_rank reads rel_w rows from global memory even where the LDS image fits
+ *                            (section 4f; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -885,6 +887,51 @@ int     tipk_pair_table_regimen_topk(const float* s1, const float* s2, int64_t l
                                      int64_t n_known_pairs /* nullable together */,
                                      int aggregate, int k, float* out_score, int32_t* out_rel, int32_t* out_pair,
                                      tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4f. Pair rank: the filtered rank of given relations (held-out side effects) among all relations of their pair, on the
+ *     logit (evaluation of what 4d serves: filtered MRR / Hits@k; no reference call site).
+ *
+ *   Input, pair-major, DEVICE: pair_u / pair_v int32 [n_pairs]; tgt_ptr int64 [n_pairs + 1], tgt_rel int32 [n_tgt]: pair p
+ *   owns the targets tgt_rel[tgt_ptr[p] : tgt_ptr[p+1]].  Targets may come in any order, may repeat, and a pair may have
+ *   none.  n_tgt is the length of tgt_rel (= tgt_ptr[n_pairs]); positions outside [0, n_tgt) are neither read nor written.
+ *   Logits: bit for bit those of 4d.  DistMult: h_k = z[u,k] * z[v,k] rounded, then acc = fmaf(h_k, w[r,k], acc) for k
+ *   ascending from 0; (u, v) and (v, u) give identical bits.  Table variant: the single fp32 add s1[u,r] + s2[v,r]; NOT
+ *   symmetric in (u, v).
+ *   Candidates of a target t of pair (u, v): every relation in [0, n_rel) except those listed for the pair's UNORDERED key
+ *   in the pair-major known lists of 4d (nullable together).  The target itself is never dropped, listed or not.
+ *   Rank (1-based): rank = 1 + #{candidates c != t : logit[c] > logit[t] or (logit[c] == logit[t] and c < t)} -- the total
+ *   order of 4d, so rank - 1 is the position the pair top-k gives the same relation under the same filter (with t taken
+ *   off the known list).  A candidate whose logit is NaN beats nothing.
+ *   Output per target (device): out_rank int32 [n_tgt]; out_logit fp32 [n_tgt] (nullable) = the target's logit.
+ *   Not ranked -- rank 0, logit NaN, nothing read out of bounds: a target whose logit is NaN, a target outside [0, n_rel),
+ *   a pair with an index outside [0, n_nodes).
+ *   Routes (DistMult): rel_w is staged in LDS once per workgroup when it fits (tipk_distmult_pair_rank_lds_route: 1 097 x 16
+ *   does); otherwise, or under option "pair_rank_stream", every lane reads its rows from global memory; same bits.
+ *   Supported: as 4d without k -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; rel_w 16-byte aligned),
+ *   1 <= n_rel <= 65 536; any number of targets per pair.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes or n_rel < 1, ld < n_rel,
+ *   a NULL required pointer (the lists, the tables, out_rank; with n_pairs > 0 and n_tgt > 0), known arrays given only in
+ *   part; then TIPK_EUNSUPPORTED outside the supported range; n_pairs == 0 or n_tgt == 0 is TIPK_OK with no launch; TIPK_OK
+ *   implies correct numbers.
+ *   No workspace.  Nothing lives in host memory: these entries do NOT synchronise, may be captured into a hipGraph and are
+ *   BITWISE repeatable (integer counts; no atomics on global memory).
+ */
+int     tipk_distmult_pair_rank_supported(int64_t n_nodes, int dim, int64_t n_rel);
+int     tipk_distmult_pair_rank_lds_route(int dim, int64_t n_rel);   /* 1 = rel_w is staged in LDS once (options apply) */
+int     tipk_distmult_pair_rank(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                const int32_t* pair_u, const int32_t* pair_v /* device */, int64_t n_pairs,
+                                const int64_t* tgt_ptr, const int32_t* tgt_rel /* device */, int64_t n_tgt,
+                                const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                int64_t n_known_pairs /* nullable together */,
+                                int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
+int     tipk_pair_table_pair_rank_supported(int64_t n_nodes, int64_t n_rel);
+int     tipk_pair_table_pair_rank(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                  const int32_t* pair_u, const int32_t* pair_v /* device */, int64_t n_pairs,
+                                  const int64_t* tgt_ptr, const int32_t* tgt_rel /* device */, int64_t n_tgt,
+                                  const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                  int64_t n_known_pairs /* nullable together */,
+                                  int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

@@ -1,4 +1,5 @@
-// What the wave-per-row top-k kernels share (tipk_pair_topk.hip, tipk_regimen_topk.hip; include/tipk.h sections 4d, 4e):
+// What the wave-per-row kernels share (tipk_pair_topk.hip, tipk_regimen_topk.hip, tipk_pair_rank.hip; include/tipk.h
+// sections 4d, 4e, 4f):
 // the wavefront-local LDS fence, the total order, the 64-ary key search, the bitonic cut of a wave's candidate buffer and
 // the bank-spreading row stride of the rel_w image.
 #pragma once

@@ -25,7 +25,7 @@ from .data import Data, build_data_dict
 from .neg_sampling import typed_negative_sampling
 from .plan import (build_pair_bwd_plan, build_dest_plan, build_row_stream_plan, build_row_stream_plan_s, build_gather_plan, build_gather_plan_segmented, build_rel_plan, build_stream_plan, build_stream_plan_rows, build_csr_plan, group_slots_for,
                    relations_per_segment, DEFAULT_CHUNK)
-from .utils import process_edges, auprc_auroc_ap_by_range
+from .utils import process_edges, auprc_auroc_ap_by_range, rank_report
 
 EPS = 1e-13                    # src/layers.py:15
 
@@ -34,6 +34,7 @@ ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
+RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP']
@@ -817,6 +818,16 @@ class MultiInnerProductDecoder(nn.Module):
             w = w[relations]
         return ops.distmult_pair_topk(z.detach(), w, pairs, k, known)
 
+    def relation_ranks(self, z, pairs, tgt_ptr, tgt_rel, known=None, relations=None):
+        """Pair rank (extension, `tipk_distmult_pair_rank`): the rank of every target relation among the relations of its
+        pair by LOGIT -> (rank int32 [T], logit [T]), rank 0 = not ranked; no autograd.  pairs [2, P], tgt_ptr [P + 1], tgt_rel
+        [T]: `ops.targets_by_pair`.  known and relations as `top_relations`: with a candidate subset, tgt_rel and the known
+        lists (`ops.restrict_known_relations`) hold positions in `relations`."""
+        w = self.weight.detach()
+        if relations is not None:
+            w = w[relations]
+        return ops.distmult_pair_rank(z.detach(), w, pairs, tgt_ptr, tgt_rel, known)
+
     def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
         """Regimen top-k (extension, `tipk_distmult_regimen_topk`): the k best relations of every drug list of the CSR pair
         (reg_drugs, reg_ptr) by the aggregate of its pairs' LOGITS -> (score [G, k], relation int32 [G, k], pair_i, pair_j
@@ -950,6 +961,17 @@ class NNDecoder(nn.Module):
             s1 = ops.matmul(p, w1.t())
             s2 = ops.matmul(q, w2.t())
         return ops.pair_table_pair_topk(s1, s2, pairs, k, known)
+
+    def relation_ranks(self, z, pairs, tgt_ptr, tgt_rel, known=None, relations=None):
+        """Pair rank (extension, `tipk_pair_table_pair_rank`) on the two tables `forward` forms; arguments and result as
+        `MultiInnerProductDecoder.relation_ranks`.  The pair's first drug is the decoder's first argument."""
+        with torch.no_grad():
+            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
+            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
+            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
+            s1 = ops.matmul(p, w1.t())
+            s2 = ops.matmul(q, w2.t())
+        return ops.pair_table_pair_rank(s1, s2, pairs, tgt_ptr, tgt_rel, known)
 
     def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
         """Regimen top-k (extension, `tipk_pair_table_regimen_topk`) on the two tables `forward` forms; arguments and result
@@ -1223,6 +1245,62 @@ class TIP(nn.Module):
             u = torch.where(have, lookup[(first + pi).clamp(min=0, max=lookup.numel() - 1)], none)
             v = torch.where(have, lookup[(first + pj).clamp(min=0, max=lookup.numel() - 1)], none)
         return RegimenSideEffects(score, idx, u, v)
+
+    def rank_side_effects(self, triples=None, filter='all', ks=(1, 3, 10), relations=None):
+        """Evaluation of what `side_effects` serves (extension): where each given (drug, drug, side effect) triple lands
+        among the side effects not recorded for its pair, and filtered MRR / Hits@k over the triples
+        (`decoder.relation_ranks`: one `tipk_distmult_pair_rank` / `tipk_pair_table_pair_rank` launch on `self.embeddings`,
+        under no_grad; both decoder kinds).
+        triples: None = the held-out set (data.dd_test_idx, data.dd_test_et), else (edge_index int [2, T], edge_type int
+        [T]); a triple is ranked for its pair as given, (u, v) and (v, u) apart.  filter: 'all' drops the pair's other train
+        and test side effects (the standard filtered setting), 'train' only its training ones -- what
+        `side_effects(exclude='train')` shows: other held-out side effects compete -- and None nothing (the raw rank); a
+        recorded side effect is dropped in either pair direction, the triple's own never.  relations: candidate side-effect
+        ids (None = all); a triple whose side effect is not among them is not ranked.  Ranks are 1-based on the logit, ties
+        by ascending position in `relations`: rank - 1 is the triple's position in `side_effects` under the same filter.
+        -> RankReport(rank int64 [T] (0 = not ranked), logit [T] (NaN there), mrr, hits {k: share of ranks <= k},
+        per_relation {'count' [R], 'mrr' [R], 'hits' [len(ks), R]}, macro_mrr, unranked): `utils.rank_report` of the ranks;
+        the tensors are on the model's device, in the triples' order."""
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
+                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
+        if filter not in ('train', 'all', None):
+            raise ValueError("filter must be 'train', 'all' or None, not %r" % (filter,))
+        d = self.data
+        dev = self.embeddings.device
+        idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
+        idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
+        if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
+                or idx.dtype.is_floating_point or et.dtype.is_floating_point:
+            raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
+                             % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
+        if et.numel():
+            lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
+            if lo < 0 or hi >= d.n_drug:
+                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
+            if rlo < 0 or rhi >= d.n_dd_et:
+                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
+        known = None
+        if filter is not None:
+            extra = (d.dd_test_idx, d.dd_test_range) if filter == 'all' else None
+            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
+        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
+        et = et.to(torch.int64)
+        tgt = et
+        if rel is not None:
+            pos = torch.full((d.n_dd_et,), -1, dtype=torch.int64, device=dev)
+            pos[rel] = torch.arange(rel.numel(), device=dev)
+            tgt = pos[et]                                                # -1: not a candidate, not ranked
+            if known is not None:
+                known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        with torch.no_grad():
+            pairs, tgt_ptr, tgt_rel, order = ops.targets_by_pair(idx, tgt, d.n_drug)
+            r, s = self.decoder.relation_ranks(self.embeddings, pairs, tgt_ptr, tgt_rel, known, rel)
+            rank = torch.empty_like(r, dtype=torch.int64)
+            rank[order] = r.to(torch.int64)
+            logit = torch.empty_like(s)
+            logit[order] = s
+        return RankReport(rank, logit, **rank_report(rank, et, d.n_dd_et, ks))
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

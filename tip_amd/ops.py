@@ -1215,7 +1215,86 @@ def restrict_known_relations(known, relations, n_rel):
     return keys, kptr2, new[keep][order].to(torch.int32)
 
 
-REGIMEN_AGGREGATES = {'max': 0, 'noisy_or': 1}                          # TIPK_REGIMEN_MAX, TIPK_REGIMEN_NOISY_OR
+def targets_by_pair(edge_index, edge_type, n_nodes):
+    """Triples grouped by their ORDERED pair (u, v) -- the table decoder is not symmetric -- for the pair rank entries
+    (include/tipk.h section 4f) -> (pairs int64 [2, P], tgt_ptr int64 [P + 1], tgt_rel int32 [T], order int64 [T]): pair p
+    owns tgt_rel[tgt_ptr[p]:tgt_ptr[p + 1]], pairs ascend by u * n_nodes + v, a pair's targets keep the caller's order
+    (repeats stay), and order[i] is the caller's position of grouped triple i: `out[order] = result` scatters a result
+    back.  Torch ops on edge_index's device (CPU tensors work too)."""
+    edge_index, edge_type = torch.as_tensor(edge_index), torch.as_tensor(edge_type)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_type.numel() != edge_index.shape[1] \
+            or edge_index.dtype.is_floating_point or edge_type.dtype.is_floating_point:
+        raise _lib.TipkError('triples: int tensors edge_index [2, T] and edge_type [T] expected, got %s %s and %s %s'
+                             % (edge_index.dtype, tuple(edge_index.shape), edge_type.dtype, tuple(edge_type.shape)))
+    n = int(n_nodes)
+    key = edge_index[0].to(torch.int64) * n + edge_index[1].to(torch.int64)
+    order = torch.sort(key, stable=True).indices
+    keys, counts = torch.unique_consecutive(key[order], return_counts=True)
+    tgt_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=key.device)
+    tgt_ptr[1:] = torch.cumsum(counts, 0)
+    pairs = torch.stack([torch.div(keys, n, rounding_mode='floor'), keys % n])
+    return pairs, tgt_ptr, edge_type.to(key.device)[order].to(torch.int32).contiguous(), order
+
+
+def _pair_rank_lists(pairs, tgt_ptr, tgt_rel, known, dev):
+    """(pair_u, pair_v, tgt_ptr, tgt_rel, n_tgt, known lists, out_rank, out_logit) of the pair rank entries, all on `dev`."""
+    pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
+    tgt_ptr, tgt_rel = torch.as_tensor(tgt_ptr), torch.as_tensor(tgt_rel)
+    require_device(tgt_ptr, tgt_rel)
+    if tgt_ptr.dim() != 1 or tgt_rel.dim() != 1 or tgt_ptr.numel() != pu.numel() + 1 or tgt_ptr.dtype.is_floating_point \
+            or tgt_rel.dtype.is_floating_point:
+        raise _lib.TipkError('targets: int tensors tgt_ptr [%d] and tgt_rel [T] expected, got %s %s and %s %s'
+                             % (pu.numel() + 1, tgt_ptr.dtype, tuple(tgt_ptr.shape), tgt_rel.dtype, tuple(tgt_rel.shape)))
+    tptr, trel = tgt_ptr.to(torch.int64).contiguous(), tgt_rel.to(torch.int32).contiguous()
+    n_tgt = trel.numel()
+    out_rank = torch.zeros((n_tgt,), dtype=torch.int32, device=dev)       # a target no pair owns stays (0, NaN)
+    out_logit = torch.full((n_tgt,), float('nan'), dtype=torch.float32, device=dev)
+    return pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit
+
+
+def distmult_pair_rank(z, rel_w, pairs, tgt_ptr, tgt_rel, known=None):
+    """The filtered rank of given relations among all relations of their pair by DistMult logit (include/tipk.h section 4f).
+
+    pairs: int tensor [2, P]; tgt_ptr int [P + 1], tgt_rel int [T]: pair p owns the targets tgt_rel[tgt_ptr[p]:tgt_ptr[p+1]]
+    (`targets_by_pair`); known: None or the pair-major lists of `known_relations_by_pair`; all on the device.
+    -> (rank int32 [T], logit float32 [T]): rank = 1 + the number of relations, not listed for the pair, that beat the
+    target (higher logit, or equal logit and lower id); rank - 1 is the target's position in `distmult_pair_topk` under the
+    same filter.  (0, NaN): not ranked -- a NaN logit, a target outside [0, n_rel), a pair index outside [0, n).
+    Does not synchronise."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('distmult_pair_rank: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (tuple(z.shape), tuple(rel_w.shape)))
+    dev = z.device
+    pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit = _pair_rank_lists(pairs, tgt_ptr, tgt_rel,
+                                                                                               known, dev)
+    check(lib().tipk_distmult_pair_rank(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(pu), ptr(pv),
+                                        pu.numel(), ptr(tptr), ptr(trel), n_tgt, ptr(keys), ptr(kptr), ptr(krel), n_keys,
+                                        ptr(out_rank), ptr(out_logit), stream_ptr(dev)), 'tipk_distmult_pair_rank')
+    return out_rank, out_logit
+
+
+def pair_table_pair_rank(s1, s2, pairs, tgt_ptr, tgt_rel, known=None):
+    """`distmult_pair_rank` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for both):
+    the logit of (u, v, r) is s1[u, r] + s2[v, r] (not symmetric); `known` drops a relation in either pair direction."""
+    s1, s2 = _f32c(s1), _f32c(s2)
+    require_device(s1, s2)
+    if s1.dim() != 2 or s1.shape != s2.shape:
+        raise _lib.TipkError('pair_table_pair_rank: two tables [n, n_rel] expected, got %s and %s'
+                             % (tuple(s1.shape), tuple(s2.shape)))
+    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1] or s1.stride(1) != 1 or s2.stride(1) != 1:
+        s1, s2 = s1.contiguous(), s2.contiguous()
+    dev = s1.device
+    pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit = _pair_rank_lists(pairs, tgt_ptr, tgt_rel,
+                                                                                               known, dev)
+    check(lib().tipk_pair_table_pair_rank(ptr(s1), ptr(s2), s1.stride(0), s1.shape[0], s1.shape[1], ptr(pu), ptr(pv),
+                                          pu.numel(), ptr(tptr), ptr(trel), n_tgt, ptr(keys), ptr(kptr), ptr(krel), n_keys,
+                                          ptr(out_rank), ptr(out_logit), stream_ptr(dev)), 'tipk_pair_table_pair_rank')
+    return out_rank, out_logit
+
+
+REGIMEN_AGGREGATES = {'max': 0, 'noisy_or': 1}                        # TIPK_REGIMEN_MAX, TIPK_REGIMEN_NOISY_OR
 
 
 def regimen_max_drugs():

@@ -155,3 +155,35 @@ def auprc_auroc_ap_by_range(pos_score, neg_score, range_list):
         s = np.r_[pos[a:b], neg[a:b]]
         rec[:, i] = auprc_auroc_ap(y, s)
     return rec
+
+
+def rank_report(rank, rel, n_rel, ks=(1, 3, 10)):
+    """Filtered-rank metrics from the ranks of `TIP.rank_side_effects` (device-agnostic: fp64, bincount, scatter_add).
+
+    rank: int tensor [T], 1-based, 0 = not ranked; rel: int tensor [T], each triple's relation in [0, n_rel).
+    -> dict: 'mrr' and 'hits' {k: share of ranks <= k}: MICRO averages over the ranked triples (NaN without any);
+    'per_relation' {'count' int64 [n_rel], 'mrr' float64 [n_rel], 'hits' float64 [len(ks), n_rel]} over each relation's
+    ranked triples, NaN for a relation without one; 'macro_mrr': the mean of per-relation mrr over the relations with
+    count > 0; 'unranked': the number of triples with rank 0, which enter no mean."""
+    rank = torch.as_tensor(rank).to(torch.int64).reshape(-1)
+    rel = torch.as_tensor(rel).to(device=rank.device, dtype=torch.int64).reshape(-1)
+    ks = tuple(int(k) for k in ks)
+    n_rel = int(n_rel)
+    ok = rank > 0
+    r, e = rank[ok], rel[ok]
+    count = torch.bincount(e, minlength=n_rel)
+    rr = 1.0 / r.to(torch.float64)
+    rr_sum = torch.zeros(n_rel, dtype=torch.float64, device=rank.device).scatter_add_(0, e, rr)
+    hit = torch.stack([(r <= k).to(torch.float64) for k in ks]) if ks else rr.new_zeros((0, r.numel()))
+    hit_sum = torch.zeros((len(ks), n_rel), dtype=torch.float64, device=rank.device)
+    hit_sum.scatter_add_(1, e[None, :].expand(len(ks), -1), hit)
+    nan = float('nan')
+    have = count > 0
+    denom = count.to(torch.float64).masked_fill(~have, nan)
+    per_mrr = rr_sum / denom
+    n_ok = int(r.numel())
+    return {'mrr': float(rr.sum()) / n_ok if n_ok else nan,
+            'hits': {k: (float(hit[i].sum()) / n_ok if n_ok else nan) for i, k in enumerate(ks)},
+            'per_relation': {'count': count, 'mrr': per_mrr, 'hits': hit_sum / denom},
+            'macro_mrr': float(per_mrr[have].mean()) if bool(have.any()) else nan,
+            'unranked': int(rank.numel()) - n_ok}
