@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 28
+#define TIPK_ABI_VERSION 29
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -59,6 +59,8 @@ const char* tipk_build_id(void);
  *                            fits (section 4e; both routes return the same bits)
  *      "pair_rank_stream"    1 = tipk_distmult_pair_rank reads rel_w rows from global memory even where the LDS image fits
  *                            (section 4f; both routes return the same bits)
+ *      "partner_rank_global" 1 = tipk_distmult_partner_rank reads z rows from global memory even where the LDS image fits
+ *                            (section 4g; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -932,6 +934,57 @@ int     tipk_pair_table_pair_rank(const float* s1, const float* s2, int64_t ld, 
                                   const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
                                   int64_t n_known_pairs /* nullable together */,
                                   int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4g. Partner rank: the filtered rank of given partners (held-out drugs) among all drugs, per (relation, drug) query, on the
+ *     logit (evaluation of what the drug queries of 4c serve: entity-ranking filtered MRR / Hits@k; no reference call site).
+ *
+ *   Input, query-major, DEVICE: q_rel / q_drug int32 [n_q]; tgt_ptr int64 [n_q + 1], tgt_node int32 [n_tgt]: query
+ *   q = (r, u) owns the target partners tgt_node[tgt_ptr[q] : tgt_ptr[q+1]].  Targets may come in any order, may repeat, and
+ *   a query may have none.  n_tgt is the length of tgt_node (= tgt_ptr[n_q]); tgt_ptr is clamped to it: positions outside
+ *   [0, n_tgt) are neither read nor written.
+ *   Logits: bit for bit those of a 4c drug query.  DistMult: a_k = z[u,k] * w[r,k] rounded once, then
+ *   acc = fmaf(a_k, z[c,k], acc) for k ascending from 0.  This is NOT symmetric in (u, c): the queried drug is the one
+ *   multiplied with w first, and (r, u) ranking c may differ in the last bit from (r, c) ranking u.  Table variant
+ *   (tipk_pair_table_partner_rank; the NN decoder of 4b): the RELATION-major tables s1t, s2t [n_rel x ld], ld >= n_nodes,
+ *   as NNDecoder.objective forms them for tipk_pair_table_loss; the logit is the single fp32 add s1t[r,u] + s2t[r,c]; a
+ *   query's candidates are one coalesced row.
+ *   Candidates of a target t of query (r, u): every drug c in [0, n_nodes) with c != u, except those with u*n+c OR c*n+u a
+ *   key of relation r in the relation-major lists of 4c (known_keys sorted inside each relation, known_ptr [n_rel + 1];
+ *   nullable together; lists that hold one direction only are handled).  The target itself is never dropped, listed or not.
+ *   Rank (1-based): rank = 1 + #{candidates c != t : logit[c] > logit[t] or (logit[c] == logit[t] and c < t)} -- the total
+ *   order of 4c for a fixed u (key u*n+v ascending), so rank - 1 is the position a 4c drug query (r, u) gives (u, t) under
+ *   the same filter (with t taken off the known list).  A candidate whose logit is NaN beats nothing.
+ *   Output per target (device): out_rank int32 [n_tgt]; out_logit fp32 [n_tgt] (nullable) = the target's logit.
+ *   Not ranked -- rank 0, logit NaN, nothing read out of bounds: r outside [0, n_rel), u or t outside [0, n_nodes), t == u
+ *   (the screen has no self pairs), a target whose logit is NaN.
+ *   Routes (DistMult): z is staged in LDS once per workgroup when it fits beside the wavefronts' state
+ *   (tipk_distmult_partner_rank_lds_route: 645 x 16 does); otherwise, or under option "partner_rank_global", every lane reads
+ *   its rows from global memory; same bits.
+ *   Filter scheme: the keys [u*n, (u+1)*n) of relation r (two searches) are merged into a bitmap of the wavefront; the
+ *   reverse keys c*n+u are searched per candidate, only for a candidate that beats the weakest target at hand.
+ *   Supported: as 4c/4d -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; z 16-byte aligned),
+ *   1 <= n_rel <= 65 536; any number of targets per query.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes or n_rel < 1,
+ *   ld < n_nodes, a NULL required pointer (the lists, the tables, out_rank; with n_q > 0 and n_tgt > 0), keys without
+ *   offsets or the reverse; then TIPK_EUNSUPPORTED outside the supported range; n_q == 0 or n_tgt == 0 is TIPK_OK with no
+ *   launch; TIPK_OK implies correct numbers.
+ *   No workspace.  Nothing lives in host memory: these entries do NOT synchronise, may be captured into a hipGraph and are
+ *   BITWISE repeatable (integer counts; no atomics on global memory).
+ */
+int     tipk_distmult_partner_rank_supported(int64_t n_nodes, int dim, int64_t n_rel);
+int     tipk_distmult_partner_rank_lds_route(int64_t n_nodes, int dim);   /* 1 = z is staged in LDS once (options apply) */
+int     tipk_distmult_partner_rank(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                   const int32_t* q_rel, const int32_t* q_drug /* device */, int64_t n_q,
+                                   const int64_t* tgt_ptr, const int32_t* tgt_node /* device */, int64_t n_tgt,
+                                   const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                                   int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
+int     tipk_pair_table_partner_rank_supported(int64_t n_nodes, int64_t n_rel);
+int     tipk_pair_table_partner_rank(const float* s1t, const float* s2t, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                     const int32_t* q_rel, const int32_t* q_drug /* device */, int64_t n_q,
+                                     const int64_t* tgt_ptr, const int32_t* tgt_node /* device */, int64_t n_tgt,
+                                     const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                                     int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

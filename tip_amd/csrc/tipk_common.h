@@ -36,7 +36,8 @@ enum {
     TIPK_OPT_PAIR_TOPK_STREAM = 9,    // tipk_distmult_pair_topk: rel_w streamed through LDS in tiles even where all of it fits
     TIPK_OPT_REGIMEN_GLOBAL = 10,     // tipk_distmult_regimen_topk: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_PAIR_RANK_STREAM = 11,   // tipk_distmult_pair_rank: rel_w rows read from global memory even where the LDS image fits
-    TIPK_OPT_COUNT = 12
+    TIPK_OPT_PARTNER_RANK_GLOBAL = 12, // tipk_distmult_partner_rank: z rows read from global memory even where the LDS image fits
+    TIPK_OPT_COUNT = 13
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

@@ -1,5 +1,5 @@
-// What the wave-per-row kernels share (tipk_pair_topk.hip, tipk_regimen_topk.hip, tipk_pair_rank.hip; include/tipk.h
-// sections 4d, 4e, 4f):
+// What the wave-per-row kernels share (tipk_pair_topk.hip, tipk_regimen_topk.hip, tipk_pair_rank.hip, tipk_partner_rank.hip;
+// include/tipk.h sections 4d, 4e, 4f, 4g):
 // the wavefront-local LDS fence, the total order, the 64-ary key search, the bitonic cut of a wave's candidate buffer and
 // the bank-spreading row stride of the rel_w image.
 #pragma once

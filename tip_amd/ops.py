@@ -1294,6 +1294,95 @@ def pair_table_pair_rank(s1, s2, pairs, tgt_ptr, tgt_rel, known=None):
     return out_rank, out_logit
 
 
+def targets_by_query(edge_index, edge_type, n_nodes):
+    """Triples (u, v, r) grouped by the (relation, drug) query (r, u) that ranks v -- for the partner rank entries
+    (include/tipk.h section 4g) -> (q_rel int32 [Q], q_drug int32 [Q], tgt_ptr int64 [Q + 1], tgt_node int32 [T], order
+    int64 [T]): query q owns tgt_node[tgt_ptr[q]:tgt_ptr[q + 1]], the queries ascend by r * n_nodes + u, a query's targets
+    keep the caller's order (repeats stay), and order[i] is the caller's position of grouped triple i:
+    `out[order] = result` scatters a result back.  Torch ops on edge_index's device (CPU tensors work too)."""
+    edge_index, edge_type = torch.as_tensor(edge_index), torch.as_tensor(edge_type)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_type.numel() != edge_index.shape[1] \
+            or edge_index.dtype.is_floating_point or edge_type.dtype.is_floating_point:
+        raise _lib.TipkError('triples: int tensors edge_index [2, T] and edge_type [T] expected, got %s %s and %s %s'
+                             % (edge_index.dtype, tuple(edge_index.shape), edge_type.dtype, tuple(edge_type.shape)))
+    n = int(n_nodes)
+    key = edge_type.to(device=edge_index.device, dtype=torch.int64) * n + edge_index[0].to(torch.int64)
+    order = torch.sort(key, stable=True).indices
+    keys, counts = torch.unique_consecutive(key[order], return_counts=True)
+    tgt_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=key.device)
+    tgt_ptr[1:] = torch.cumsum(counts, 0)
+    q_rel = torch.div(keys, n, rounding_mode='floor').to(torch.int32)
+    return q_rel, (keys % n).to(torch.int32), tgt_ptr, edge_index[1][order].to(torch.int32).contiguous(), order
+
+
+def _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known, dev):
+    """(q_rel, q_drug, tgt_ptr, tgt_node, n_tgt, keys, ptr, out_rank, out_logit) of the partner rank entries, all on `dev`."""
+    q_rel, q_drug, tgt_ptr, tgt_node = (torch.as_tensor(t) for t in (q_rel, q_drug, tgt_ptr, tgt_node))
+    require_device(q_rel, q_drug, tgt_ptr, tgt_node)
+    if any(t.dim() != 1 or t.dtype.is_floating_point for t in (q_rel, q_drug, tgt_ptr, tgt_node)) \
+            or q_drug.numel() != q_rel.numel() or tgt_ptr.numel() != q_rel.numel() + 1:
+        raise _lib.TipkError('queries: int tensors q_rel [Q], q_drug [Q], tgt_ptr [Q + 1] and tgt_node [T] expected, got %s, %s, '
+                             '%s and %s' % tuple((t.dtype, tuple(t.shape)) for t in (q_rel, q_drug, tgt_ptr, tgt_node)))
+    keys = kptr = None
+    if known is not None:
+        keys, kptr = known
+        require_device(keys, kptr)
+        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+        if keys.numel() == 0:                                            # nothing to drop (empty tensors have no address)
+            keys = kptr = None
+    qr, qd = q_rel.to(torch.int32).contiguous(), q_drug.to(torch.int32).contiguous()
+    tptr, tnode = tgt_ptr.to(torch.int64).contiguous(), tgt_node.to(torch.int32).contiguous()
+    n_tgt = tnode.numel()
+    out_rank = torch.zeros((n_tgt,), dtype=torch.int32, device=dev)       # a target no query owns stays (0, NaN)
+    out_logit = torch.full((n_tgt,), float('nan'), dtype=torch.float32, device=dev)
+    return qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit
+
+
+def distmult_partner_rank(z, rel_w, q_rel, q_drug, tgt_ptr, tgt_node, known=None):
+    """The filtered rank of given partners among all drugs, per (relation, drug) query, by DistMult logit (include/tipk.h
+    section 4g).
+
+    q_rel, q_drug: int tensors [Q]; tgt_ptr int [Q + 1], tgt_node int [T]: query q = (r, u) owns the target partners
+    tgt_node[tgt_ptr[q]:tgt_ptr[q+1]] (`targets_by_query`); known: None or (keys int64 u*n+v sorted inside each relation, ptr
+    int64 [n_rel + 1]), the relation-major lists `distmult_screen` takes; all on the device.
+    -> (rank int32 [T], logit float32 [T]): rank = 1 + the number of drugs c != u, with neither u*n+c nor c*n+u listed for
+    r, that beat the target (higher logit, or equal logit and lower id); rank - 1 is the target's position in the drug query
+    (r, u) of `distmult_screen` under the same filter.  The logit multiplies z[u] with rel_w[r] first: it is the screen's,
+    not symmetric in (u, target) to the last bit.  (0, NaN): not ranked -- r outside [0, n_rel), u or the target outside
+    [0, n), target == u, a NaN logit.  Does not synchronise."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('distmult_partner_rank: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (tuple(z.shape), tuple(rel_w.shape)))
+    dev = z.device
+    qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit = _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known,
+                                                                                      dev)
+    check(lib().tipk_distmult_partner_rank(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(qr), ptr(qd),
+                                           qr.numel(), ptr(tptr), ptr(tnode), n_tgt, ptr(keys), ptr(kptr), ptr(out_rank),
+                                           ptr(out_logit), stream_ptr(dev)), 'tipk_distmult_partner_rank')
+    return out_rank, out_logit
+
+
+def pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known=None):
+    """`distmult_partner_rank` for the NN decoder's RELATION-major tables s1t, s2t [n_rel, n] (row stride free, the same for
+    both), as `NNDecoder.objective` forms them: the logit of target c of query (r, u) is s1t[r, u] + s2t[r, c]."""
+    s1t, s2t = _f32c(s1t), _f32c(s2t)
+    require_device(s1t, s2t)
+    if s1t.dim() != 2 or s1t.shape != s2t.shape:
+        raise _lib.TipkError('pair_table_partner_rank: two tables [n_rel, n] expected, got %s and %s'
+                             % (tuple(s1t.shape), tuple(s2t.shape)))
+    if s1t.stride(0) != s2t.stride(0) or s1t.stride(0) < s1t.shape[1] or s1t.stride(1) != 1 or s2t.stride(1) != 1:
+        s1t, s2t = s1t.contiguous(), s2t.contiguous()
+    dev = s1t.device
+    qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit = _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known,
+                                                                                      dev)
+    check(lib().tipk_pair_table_partner_rank(ptr(s1t), ptr(s2t), s1t.stride(0), s1t.shape[1], s1t.shape[0], ptr(qr), ptr(qd),
+                                             qr.numel(), ptr(tptr), ptr(tnode), n_tgt, ptr(keys), ptr(kptr), ptr(out_rank),
+                                             ptr(out_logit), stream_ptr(dev)), 'tipk_pair_table_partner_rank')
+    return out_rank, out_logit
+
+
 REGIMEN_AGGREGATES = {'max': 0, 'noisy_or': 1}                        # TIPK_REGIMEN_MAX, TIPK_REGIMEN_NOISY_OR
 
 
