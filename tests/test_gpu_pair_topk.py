@@ -79,6 +79,34 @@ def test_table_small_shapes(n_rel):
                  seed=n_rel, symmetric=False)
 
 
+def test_column_sliced_tables_equal_contiguous_copies():
+    """Tables with column stride 2 (`big[:, ::2]`; the row stride 140 >= 70 looks fine) must be read as their contiguous
+    copies are, bit for bit, by all four table faces: the entries know a row stride only.  70 relations: lane windows of
+    64 + 6.  The partner rank takes relation-major tables, so its views are [70, 9]."""
+    def bits(out):
+        return [t.view(torch.int32) if t.is_floating_point() else t for t in out]
+
+    def same(face, t1, t2, *lists):
+        assert t1.stride(1) == 2 and t2.stride(1) == 2
+        got, want = face(t1, t2, *lists), face(t1.contiguous(), t2.contiguous(), *lists)
+        assert all(torch.equal(a, b) for a, b in zip(bits(got), bits(want))), face.__name__
+
+    g = torch.Generator().manual_seed(970)
+    n, n_rel, k = 9, 70, 3
+    s1, s2 = (torch.randn(n, 2 * n_rel, generator=g).to(DEV)[:, ::2] for _ in range(2))
+    s1t, s2t = (torch.randn(n_rel, 2 * n, generator=g).to(DEV)[:, ::2] for _ in range(2))
+    assert tuple(s1.shape) == (n, n_rel) and tuple(s1t.shape) == (n_rel, n)
+    pairs = torch.tensor([[0, 1, 8, 3, 4], [5, 0, 2, 7, 6]], device=DEV)
+    one_each = torch.arange(6, device=DEV)                                # a target per pair / query
+    tgt_rel = torch.tensor([0, 63, 64, 69, 17], device=DEV)
+    same(ops.pair_table_pair_topk, s1, s2, pairs, k)
+    same(ops.pair_table_pair_rank, s1, s2, pairs, one_each, tgt_rel)
+    reg_drugs = torch.tensor([0, 1, 2, 3, 4, 5, 6, 7, 8, 1, 3, 2, 8], device=DEV)
+    reg_ptr = torch.tensor([0, 3, 5, 9, 11, 13], device=DEV)
+    same(ops.pair_table_regimen_topk, s1, s2, reg_drugs, reg_ptr, k)
+    same(ops.pair_table_partner_rank, s1t, s2t, tgt_rel, pairs[0], one_each, pairs[1])
+
+
 def test_ties_resolve_by_relation_id():
     """rel_w has 13 distinct rows repeated 10 times (table: 13 distinct columns): every logit occurs 10 times, and equal
     logits must come out in ascending relation id -- rule 3 of the acceptance rule is exact about that."""

@@ -1,14 +1,15 @@
 // Pair rank: the filtered rank of given relations (held-out side effects) among all relations of their pair
 // (include/tipk.h section 4f).
 //
-// One launch of persistent workgroups (16 wavefronts); a workgroup takes blocks of 16 pairs, ONE WAVEFRONT PER PAIR, as the
-// pair top-k (tipk_pair_topk.hip) does; the logits, the known bitmap and the total order are that kernel's.
+// One launch of persistent workgroups (16 wavefronts); a workgroup takes blocks of 16 pairs, ONE WAVEFRONT PER PAIR.  The
+// logits, the known bitmap, the counting step and the total order are the shared pieces of tipk_wave_topk.h, so rank - 1
+// is the position the pair top-k gives; this file holds the pair / chunk / window loop.
 // Targets.  The wave holds the pair's targets in chunks of 64, one per lane, and computes their logits first, with the
 //   same fma chain every candidate gets (a target is a candidate of the other targets).
 // Scoring.  DistMult: the wave leaves h = z[u] * z[v] (rounded once) in its LDS row; lane l scores relations l, l + 64, ...
-//   as acc = fmaf(h[k], w[r][k], acc), k ascending.  LDS route: the rows come from an LDS image of rel_w staged once per
-//   workgroup (row stride S with S / 4 odd, as in 4d).  Global route (the image does not fit, or option
-//   "pair_rank_stream"): each lane reads its rows from global memory.  Same arithmetic in the same order: same bits.
+//   with the shared fma chain.  LDS route: the rows come from an LDS image of rel_w staged once per workgroup.  Global
+//   route (the image does not fit, or option "pair_rank_stream"): each lane reads its rows from global memory.  Same
+//   arithmetic in the same order: same bits.
 //   Table variant: lane l adds s1[u][r] + s2[v][r] from the two (coalesced) table rows.
 //   A relation is scored once per chunk of 64 targets, i.e. once per pair unless the pair has more than 64 targets.
 // Known filter.  One 64-ary search per pair finds the pair's block of known_rel; the block is merged into a 2 048-bit LDS
@@ -21,16 +22,6 @@
 #include "tipk_wave_topk.h"
 
 namespace {
-
-constexpr int PR_NT = 1024;                 // threads per workgroup
-constexpr int PR_NW = PR_NT / TIPK_WAVE;    // pairs per block (one per wavefront)
-constexpr int PR_DIM_MAX = 256;
-constexpr int64_t PR_NMAX = 46340;
-constexpr int64_t PR_RMAX = 65536;
-constexpr int PR_WIN = 2048;                // relations per bitmap window (64 words: lane l clears word l)
-constexpr int PR_LDS_BYTES = 152 * 1024;    // dynamic LDS a workgroup may ask for
-
-enum { PR_DISTMULT = 0, PR_DISTMULT16 = 1, PR_TABLE = 2 };
 
 struct PairRankArgs {
     const float* a;            // z [n x dim]            | s1 [n x ld]
@@ -48,34 +39,8 @@ struct PairRankArgs {
     float* out_logit;          // nullable
 };
 
-// logit of relation r for the wave's pair: wr = row r of rel_w (LDS image or global), hs = the wave's h row
-template <int MODE>
-__device__ __forceinline__ float pr_dot(const float* wr, const float* hs, const float4* hq, int dim) {
-    float s = 0.f;
-    if (MODE == PR_DISTMULT16) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 w4 = *reinterpret_cast<const float4*>(wr + 4 * q);
-            s = fmaf(hq[q].x, w4.x, s);
-            s = fmaf(hq[q].y, w4.y, s);
-            s = fmaf(hq[q].z, w4.z, s);
-            s = fmaf(hq[q].w, w4.w, s);
-        }
-    } else {
-        for (int k0 = 0; k0 < dim; k0 += 4) {
-            const float4 w4 = *reinterpret_cast<const float4*>(wr + k0);
-            const float4 h4 = *reinterpret_cast<const float4*>(hs + k0);
-            s = fmaf(h4.x, w4.x, s);
-            s = fmaf(h4.y, w4.y, s);
-            s = fmaf(h4.z, w4.z, s);
-            s = fmaf(h4.w, w4.w, s);
-        }
-    }
-    return s;
-}
-
 template <int MODE, bool GLOBAL>
-__global__ void __launch_bounds__(PR_NT) pair_rank_kernel(PairRankArgs a) {
+__global__ void __launch_bounds__(WT_NT) pair_rank_kernel(PairRankArgs a) {
     extern __shared__ __align__(16) unsigned char pr_smem[];
     const int t = threadIdx.x, lane = tipk_lane();
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -85,44 +50,33 @@ __global__ void __launch_bounds__(PR_NT) pair_rank_kernel(PairRankArgs a) {
 
     // LDS: [rel_w image] [h rows] | bitmaps
     float* Ws = reinterpret_cast<float*>(pr_smem);
-    float* hs_all = Ws + ((MODE == PR_TABLE || GLOBAL) ? 0 : R * a.stride);
-    uint32_t* km_all = reinterpret_cast<uint32_t*>(hs_all + (MODE == PR_TABLE ? 0 : PR_NW * dim));
+    float* hs_all = Ws + ((MODE == WT_TABLE || GLOBAL) ? 0 : R * a.stride);
+    uint32_t* km_all = reinterpret_cast<uint32_t*>(hs_all + (MODE == WT_TABLE ? 0 : WT_NW * dim));
     float* hs = hs_all + wave * dim;
-    uint32_t* km = km_all + wave * (PR_WIN / 32);
+    uint32_t* km = km_all + wave * (WT_WIN / 32);
     const float* W = GLOBAL ? a.b : Ws;
 
-    if (MODE != PR_TABLE && !GLOBAL) {
-        const int q4 = dim >> 2;
-        for (int idx = t; idx < R * q4; idx += PR_NT) {
-            const int row = idx / q4, q = idx - row * q4;
-            tipk_st4(Ws + row * a.stride + 4 * q, tipk_ld4(a.b + (int64_t)row * dim + 4 * q));
-        }
+    if (MODE != WT_TABLE && !GLOBAL) {
+        wt_stage_rows<WT_NT>(Ws, a.b, 0, R, dim, a.stride);
         __syncthreads();
     }
 
-    const int64_t n_blocks = (a.n_pairs + PR_NW - 1) / PR_NW;
+    const int64_t n_blocks = (a.n_pairs + WT_NW - 1) / WT_NW;
     for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const int64_t p = blk * PR_NW + wave;
+        const int64_t p = blk * WT_NW + wave;
         if (p >= a.n_pairs) continue;                                  // uniform in the wave; the waves never meet again
-        int64_t tb = a.tptr[p], te = a.tptr[p + 1];
-        tb = tb < 0 ? 0 : tb;                                          // device lists cannot be validated on the host:
-        te = te > a.n_tgt ? a.n_tgt : te;                              // nothing outside [0, n_tgt) is read or written
-        if (tb >= te) continue;
+        int64_t tb, te;
+        if (!wt_target_range(a.tptr, p, a.n_tgt, tb, te)) continue;
         const int u = a.pu[p], v = a.pv[p];
         const bool act = u >= 0 && u < a.n && v >= 0 && v < a.n;
         int64_t kbeg = 0, kend = 0;
-        float4 hq[MODE == PR_DISTMULT16 ? 4 : 1];
+        float4 hq[MODE == WT_DISTMULT16 ? 4 : 1];
         if (act) {
-            if (MODE != PR_TABLE) {
-                const float* zu = a.a + (int64_t)u * dim;
-                const float* zv = a.a + (int64_t)v * dim;
+            if (MODE != WT_TABLE) {
                 wave_sync();                                           // the previous pair's reads of the row are done
-                for (int kk = lane; kk < dim; kk += TIPK_WAVE) hs[kk] = zu[kk] * zv[kk];
+                wt_write_row(hs, a.a + (int64_t)u * dim, a.a + (int64_t)v * dim, dim, lane);
                 wave_sync();
-                if (MODE == PR_DISTMULT16) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) hq[q] = *reinterpret_cast<const float4*>(hs + 4 * q);
-                }
+                wt_row16<MODE>(hq, hs);
             }
             if (a.kkeys) {
                 const int lo = u < v ? u : v, hi = u < v ? v : u;
@@ -138,85 +92,49 @@ __global__ void __launch_bounds__(PR_NT) pair_rank_kernel(PairRankArgs a) {
             const bool tok = act && tr >= 0 && tr < R;
             float ts = NAN;
             if (tok) {
-                if (MODE == PR_TABLE) ts = a.a[(int64_t)u * a.ld + tr] + a.b[(int64_t)v * a.ld + tr];
-                else ts = pr_dot<MODE>(W + (int64_t)tr * wstride, hs, hq, dim);
+                if (MODE == WT_TABLE) ts = a.a[(int64_t)u * a.ld + tr] + a.b[(int64_t)v * a.ld + tr];
+                else ts = wt_dot<MODE>(W + (int64_t)tr * wstride, hs, hq, dim);
             }
             int cnt = 0;
             if (act) {
                 int64_t kc = kbeg;
-                for (int c0 = 0; c0 < R; c0 += PR_WIN) {
-                    const int c1 = c0 + PR_WIN < R ? c0 + PR_WIN : R;
+                for (int c0 = 0; c0 < R; c0 += WT_WIN) {
+                    const int c1 = c0 + WT_WIN < R ? c0 + WT_WIN : R;
                     if (filt) {
                         // the known relations of [c0, c1) as bits; the cursor kc passes every id below c1
                         wave_sync();                                   // the previous window's bits have been read
-                        km[lane] = 0u;
-                        wave_sync();
-                        for (;;) {
-                            const int64_t idx = kc + lane;
-                            const int x = idx < kend ? a.krel[idx] : WT_REL_PAD;
-                            const bool below = x < c1;
-                            if (below && x >= c0) atomicOr(&km[(x - c0) >> 5], 1u << ((x - c0) & 31));
-                            const int nb = __popcll(__ballot(below));
-                            kc += nb;
-                            if (nb < TIPK_WAVE) break;
-                        }
+                        wt_merge_window<WT_WIN / 32>(km, kc, kend, c0, c1, lane, [&](int64_t idx) { return a.krel[idx]; });
                         wave_sync();
                     }
                     for (int g0 = c0; g0 < c1; g0 += TIPK_WAVE) {
                         const int r = g0 + lane;
                         bool cand = r < c1;
-                        if (cand && filt) {
-                            const int bit = r - c0;
-                            cand = !((km[bit >> 5] >> (bit & 31)) & 1u);
-                        }
+                        if (cand && filt) cand = !wt_bit(km, r - c0);
                         float s = NAN;                                 // NaN beats nothing
                         if (cand) {
-                            if (MODE == PR_TABLE) s = a.a[(int64_t)u * a.ld + r] + a.b[(int64_t)v * a.ld + r];
-                            else s = pr_dot<MODE>(W + (int64_t)r * wstride, hs, hq, dim);
+                            if (MODE == WT_TABLE) s = a.a[(int64_t)u * a.ld + r] + a.b[(int64_t)v * a.ld + r];
+                            else s = wt_dot<MODE>(W + (int64_t)r * wstride, hs, hq, dim);
                         }
-                        for (int j = 0; j < nt; ++j) {
-                            const float sj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ts), j));
-                            const int rj = __builtin_amdgcn_readlane(tr, j);
-                            const int beat = __popcll(__ballot(better(s, r, sj, rj)));
-                            cnt += lane == j ? beat : 0;
-                        }
+                        wt_count_beaten(cnt, s, r, ts, tr, nt, lane);
                     }
                 }
             }
-            if (lane < nt) {
-                const bool ranked = tok && ts == ts;
-                a.out_rank[ch + lane] = ranked ? 1 + cnt : 0;
-                if (a.out_logit) a.out_logit[ch + lane] = ranked ? ts : NAN;
-            }
+            wt_write_rank(a.out_rank, a.out_logit, ch, nt, tok, cnt, ts, lane);
         }
     }
 }
 
 int64_t pr_fixed_bytes(int dim, bool table) {
-    return (table ? 0 : (int64_t)PR_NW * dim * 4) + (int64_t)PR_NW * (PR_WIN / 32) * 4;
-}
-
-bool pr_fits_lds(int dim, int64_t n_rel) {
-    return n_rel * wt_stride(dim) * 4 + pr_fixed_bytes(dim, false) <= PR_LDS_BYTES;
+    return (table ? 0 : (int64_t)WT_NW * dim * 4) + (int64_t)WT_NW * (WT_WIN / 32) * 4;
 }
 
 int pr_check_lists(int64_t n_nodes, int64_t n_rel, const int32_t* pair_u, const int32_t* pair_v, int64_t n_pairs,
                    const int64_t* tgt_ptr, const int32_t* tgt_rel, int64_t n_tgt, const int64_t* keys, const int64_t* kptr,
                    const int32_t* krel, int64_t n_known, const int32_t* out_rank) {
     if (n_pairs < 0 || n_tgt < 0 || n_nodes < 1 || n_rel < 1 || n_known < 0) return TIPK_EINVAL;
-    const int given = (keys != nullptr) + (kptr != nullptr) + (krel != nullptr);
-    if (given != 0 && given != 3) return TIPK_EINVAL;
+    if (!wt_known_ok(keys, kptr, krel)) return TIPK_EINVAL;
     if (n_pairs > 0 && n_tgt > 0 && (!pair_u || !pair_v || !tgt_ptr || !tgt_rel || !out_rank)) return TIPK_EINVAL;
     return TIPK_OK;
-}
-
-template <int MODE, bool GLOBAL>
-int pr_launch(const PairRankArgs& a, int grid, size_t lds, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute((const void*)pair_rank_kernel<MODE, GLOBAL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return tipk_hip_status(e);
-    hipLaunchKernelGGL((pair_rank_kernel<MODE, GLOBAL>), dim3((unsigned)grid), dim3(PR_NT), lds, st, a);
-    TIPK_RETURN_LAUNCH();
 }
 
 void pr_fill_lists(PairRankArgs& a, const int32_t* pair_u, const int32_t* pair_v, int64_t n_pairs, const int64_t* tgt_ptr,
@@ -231,12 +149,11 @@ void pr_fill_lists(PairRankArgs& a, const int32_t* pair_u, const int32_t* pair_v
 }  // namespace
 
 extern "C" int tipk_distmult_pair_rank_supported(int64_t n_nodes, int dim, int64_t n_rel) {
-    return n_nodes >= 1 && n_nodes <= PR_NMAX && dim >= 4 && dim <= PR_DIM_MAX && dim % 4 == 0 && n_rel >= 1 &&
-           n_rel <= PR_RMAX;
+    return wt_distmult_shape(n_nodes, dim, n_rel);
 }
 
 extern "C" int tipk_distmult_pair_rank_lds_route(int dim, int64_t n_rel) {
-    return dim >= 4 && dim <= PR_DIM_MAX && dim % 4 == 0 && n_rel >= 1 && n_rel <= PR_RMAX && pr_fits_lds(dim, n_rel) &&
+    return wt_distmult_shape(1, dim, n_rel) && wt_fits_lds(n_rel, dim, pr_fixed_bytes(dim, false)) &&
            !tipk_option(TIPK_OPT_PAIR_RANK_STREAM);
 }
 
@@ -261,17 +178,17 @@ extern "C" int tipk_distmult_pair_rank(const float* z, int64_t n_nodes, int dim,
     a.n = (int)n_nodes; a.dim = dim; a.n_rel = (int)n_rel; a.stride = wt_stride(dim);
     const bool lds_route = tipk_distmult_pair_rank_lds_route(dim, n_rel) != 0;
     const size_t lds = (lds_route ? (size_t)n_rel * a.stride * 4 : 0) + (size_t)pr_fixed_bytes(dim, false);
-    const int64_t n_blocks = (n_pairs + PR_NW - 1) / PR_NW;
-    const int64_t most = wt_cu_count();                                // one workgroup per CU: the image fills its LDS
-    const int grid = (int)(n_blocks < most ? n_blocks : most);
+    const int grid = wt_grid(n_pairs, 1);                              // one workgroup per CU: the image fills its LDS
     hipStream_t st = (hipStream_t)stream;
     if (lds_route)
-        return dim == 16 ? pr_launch<PR_DISTMULT16, false>(a, grid, lds, st) : pr_launch<PR_DISTMULT, false>(a, grid, lds, st);
-    return dim == 16 ? pr_launch<PR_DISTMULT16, true>(a, grid, lds, st) : pr_launch<PR_DISTMULT, true>(a, grid, lds, st);
+        return dim == 16 ? wt_launch<pair_rank_kernel<WT_DISTMULT16, false>>(a, grid, lds, st)
+                         : wt_launch<pair_rank_kernel<WT_DISTMULT, false>>(a, grid, lds, st);
+    return dim == 16 ? wt_launch<pair_rank_kernel<WT_DISTMULT16, true>>(a, grid, lds, st)
+                     : wt_launch<pair_rank_kernel<WT_DISTMULT, true>>(a, grid, lds, st);
 }
 
 extern "C" int tipk_pair_table_pair_rank_supported(int64_t n_nodes, int64_t n_rel) {
-    return n_nodes >= 1 && n_nodes <= PR_NMAX && n_rel >= 1 && n_rel <= PR_RMAX;
+    return wt_table_shape(n_nodes, n_rel);
 }
 
 extern "C" int tipk_pair_table_pair_rank(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
@@ -292,8 +209,6 @@ extern "C" int tipk_pair_table_pair_rank(const float* s1, const float* s2, int64
                   n_known_pairs, out_rank, out_logit);
     a.a = s1; a.b = s2; a.ld = ld;
     a.n = (int)n_nodes; a.dim = 0; a.n_rel = (int)n_rel; a.stride = 0;
-    const int64_t n_blocks = (n_pairs + PR_NW - 1) / PR_NW;
-    const int64_t most = 2 * (int64_t)wt_cu_count();                   // 4 KB of LDS each: two workgroups share a CU
-    const int grid = (int)(n_blocks < most ? n_blocks : most);
-    return pr_launch<PR_TABLE, false>(a, grid, (size_t)pr_fixed_bytes(0, true), (hipStream_t)stream);
+    const int grid = wt_grid(n_pairs, 2);                              // 4 KB of LDS each: two workgroups share a CU
+    return wt_launch<pair_rank_kernel<WT_TABLE, false>>(a, grid, (size_t)pr_fixed_bytes(0, true), (hipStream_t)stream);
 }

@@ -1142,6 +1142,29 @@ def _known_lists(known):
     return keys, kptr, krel, n_keys
 
 
+def _distmult_operands(z, rel_w, who):
+    """z [n, dim] and rel_w [n_rel, dim] as contiguous fp32 device tensors for the entry `who`."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w)
+    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
+        raise _lib.TipkError('%s: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (who, tuple(z.shape), tuple(rel_w.shape)))
+    return z, rel_w
+
+
+def _table_pair(t1, t2, who, shape='[n, n_rel]'):
+    """Two decoder tables of one shape as fp32 device tensors the table entries of `who` can read.  The entries take ONE row
+    stride and know no column stride: tables whose row strides differ or are shorter than a row, or whose column stride is
+    not 1, are made contiguous."""
+    t1, t2 = _f32c(t1), _f32c(t2)
+    require_device(t1, t2)
+    if t1.dim() != 2 or t1.shape != t2.shape:
+        raise _lib.TipkError('%s: two tables %s expected, got %s and %s' % (who, shape, tuple(t1.shape), tuple(t2.shape)))
+    if t1.stride(0) != t2.stride(0) or t1.stride(0) < t1.shape[1] or t1.stride(1) != 1 or t2.stride(1) != 1:
+        t1, t2 = t1.contiguous(), t2.contiguous()
+    return t1, t2
+
+
 def _pair_topk_lists(pairs, known, dev):
     """(pair_u, pair_v int32 [P], keys, ptr, rel, n_keys) of the pair top-k entries, all on `dev`."""
     pairs = torch.as_tensor(pairs)
@@ -1159,11 +1182,7 @@ def distmult_pair_topk(z, rel_w, pairs, k, known=None):
     pairs: int tensor [2, P] on the device.  known: None or (pair_keys, pair_ptr, rel) on the device, the pair-major lists
     of `known_relations_by_pair`.  -> (logits float32 [P, k], relation int32 [P, k]), descending logit then ascending
     relation id; (-inf, -1) pads a row with fewer than k candidates.  Does not synchronise."""
-    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
-    require_device(z, rel_w)
-    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
-        raise _lib.TipkError('distmult_pair_topk: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
-                             % (tuple(z.shape), tuple(rel_w.shape)))
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_pair_topk')
     dev = z.device
     pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
     n, dim, n_rel, n_p, k = z.shape[0], z.shape[1], rel_w.shape[0], pu.numel(), int(k)
@@ -1180,13 +1199,7 @@ def distmult_pair_topk(z, rel_w, pairs, k, known=None):
 def pair_table_pair_topk(s1, s2, pairs, k, known=None):
     """`distmult_pair_topk` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for both):
     the logit of (u, v, r) is s1[u, r] + s2[v, r] (not symmetric); `known` drops a relation in either pair direction."""
-    s1, s2 = _f32c(s1), _f32c(s2)
-    require_device(s1, s2)
-    if s1.dim() != 2 or s1.shape != s2.shape:
-        raise _lib.TipkError('pair_table_pair_topk: two tables [n, n_rel] expected, got %s and %s'
-                             % (tuple(s1.shape), tuple(s2.shape)))
-    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1]:
-        s1, s2 = s1.contiguous(), s2.contiguous()
+    s1, s2 = _table_pair(s1, s2, 'pair_table_pair_topk')
     dev = s1.device
     pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
     n, n_rel, n_p, k = s1.shape[0], s1.shape[1], pu.numel(), int(k)
@@ -1215,40 +1228,60 @@ def restrict_known_relations(known, relations, n_rel):
     return keys, kptr2, new[keep][order].to(torch.int32)
 
 
+def _triples(edge_index, edge_type):
+    """(edge_index [2, T], edge_type [T]) as int tensors, checked."""
+    edge_index, edge_type = torch.as_tensor(edge_index), torch.as_tensor(edge_type)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_type.numel() != edge_index.shape[1] \
+            or edge_index.dtype.is_floating_point or edge_type.dtype.is_floating_point:
+        raise _lib.TipkError('triples: int tensors edge_index [2, T] and edge_type [T] expected, got %s %s and %s %s'
+                             % (edge_index.dtype, tuple(edge_index.shape), edge_type.dtype, tuple(edge_type.shape)))
+    return edge_index, edge_type
+
+
+def _group_by_key(key):
+    """int64 key [T] -> (keys [G] distinct ascending, ptr int64 [G + 1], order int64 [T]): group g is order[ptr[g]:ptr[g + 1]],
+    the positions whose key is keys[g], in the caller's order (the sort is stable)."""
+    order = torch.sort(key, stable=True).indices
+    keys, counts = torch.unique_consecutive(key[order], return_counts=True)
+    ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=key.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return keys, ptr, order
+
+
 def targets_by_pair(edge_index, edge_type, n_nodes):
     """Triples grouped by their ORDERED pair (u, v) -- the table decoder is not symmetric -- for the pair rank entries
     (include/tipk.h section 4f) -> (pairs int64 [2, P], tgt_ptr int64 [P + 1], tgt_rel int32 [T], order int64 [T]): pair p
     owns tgt_rel[tgt_ptr[p]:tgt_ptr[p + 1]], pairs ascend by u * n_nodes + v, a pair's targets keep the caller's order
     (repeats stay), and order[i] is the caller's position of grouped triple i: `out[order] = result` scatters a result
     back.  Torch ops on edge_index's device (CPU tensors work too)."""
-    edge_index, edge_type = torch.as_tensor(edge_index), torch.as_tensor(edge_type)
-    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_type.numel() != edge_index.shape[1] \
-            or edge_index.dtype.is_floating_point or edge_type.dtype.is_floating_point:
-        raise _lib.TipkError('triples: int tensors edge_index [2, T] and edge_type [T] expected, got %s %s and %s %s'
-                             % (edge_index.dtype, tuple(edge_index.shape), edge_type.dtype, tuple(edge_type.shape)))
+    edge_index, edge_type = _triples(edge_index, edge_type)
     n = int(n_nodes)
     key = edge_index[0].to(torch.int64) * n + edge_index[1].to(torch.int64)
-    order = torch.sort(key, stable=True).indices
-    keys, counts = torch.unique_consecutive(key[order], return_counts=True)
-    tgt_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=key.device)
-    tgt_ptr[1:] = torch.cumsum(counts, 0)
+    keys, tgt_ptr, order = _group_by_key(key)
     pairs = torch.stack([torch.div(keys, n, rounding_mode='floor'), keys % n])
     return pairs, tgt_ptr, edge_type.to(key.device)[order].to(torch.int32).contiguous(), order
+
+
+def _rank_targets(tgt_ptr, tgt, n_rows, dev):
+    """(tgt_ptr int64 [n_rows + 1], tgt int32 [T], T, out_rank, out_logit) of the rank entries, all on `dev`: the target lists
+    checked, the outputs filled with (0, NaN), which a target no row owns keeps."""
+    tgt_ptr, tgt = torch.as_tensor(tgt_ptr), torch.as_tensor(tgt)
+    require_device(tgt_ptr, tgt)
+    if tgt_ptr.dim() != 1 or tgt.dim() != 1 or tgt_ptr.numel() != n_rows + 1 or tgt_ptr.dtype.is_floating_point \
+            or tgt.dtype.is_floating_point:
+        raise _lib.TipkError('targets: int tensors tgt_ptr [%d] and targets [T] expected, got %s %s and %s %s'
+                             % (n_rows + 1, tgt_ptr.dtype, tuple(tgt_ptr.shape), tgt.dtype, tuple(tgt.shape)))
+    tptr, tgt = tgt_ptr.to(torch.int64).contiguous(), tgt.to(torch.int32).contiguous()
+    n_tgt = tgt.numel()
+    out_rank = torch.zeros((n_tgt,), dtype=torch.int32, device=dev)
+    out_logit = torch.full((n_tgt,), float('nan'), dtype=torch.float32, device=dev)
+    return tptr, tgt, n_tgt, out_rank, out_logit
 
 
 def _pair_rank_lists(pairs, tgt_ptr, tgt_rel, known, dev):
     """(pair_u, pair_v, tgt_ptr, tgt_rel, n_tgt, known lists, out_rank, out_logit) of the pair rank entries, all on `dev`."""
     pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
-    tgt_ptr, tgt_rel = torch.as_tensor(tgt_ptr), torch.as_tensor(tgt_rel)
-    require_device(tgt_ptr, tgt_rel)
-    if tgt_ptr.dim() != 1 or tgt_rel.dim() != 1 or tgt_ptr.numel() != pu.numel() + 1 or tgt_ptr.dtype.is_floating_point \
-            or tgt_rel.dtype.is_floating_point:
-        raise _lib.TipkError('targets: int tensors tgt_ptr [%d] and tgt_rel [T] expected, got %s %s and %s %s'
-                             % (pu.numel() + 1, tgt_ptr.dtype, tuple(tgt_ptr.shape), tgt_rel.dtype, tuple(tgt_rel.shape)))
-    tptr, trel = tgt_ptr.to(torch.int64).contiguous(), tgt_rel.to(torch.int32).contiguous()
-    n_tgt = trel.numel()
-    out_rank = torch.zeros((n_tgt,), dtype=torch.int32, device=dev)       # a target no pair owns stays (0, NaN)
-    out_logit = torch.full((n_tgt,), float('nan'), dtype=torch.float32, device=dev)
+    tptr, trel, n_tgt, out_rank, out_logit = _rank_targets(tgt_ptr, tgt_rel, pu.numel(), dev)
     return pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit
 
 
@@ -1261,11 +1294,7 @@ def distmult_pair_rank(z, rel_w, pairs, tgt_ptr, tgt_rel, known=None):
     target (higher logit, or equal logit and lower id); rank - 1 is the target's position in `distmult_pair_topk` under the
     same filter.  (0, NaN): not ranked -- a NaN logit, a target outside [0, n_rel), a pair index outside [0, n).
     Does not synchronise."""
-    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
-    require_device(z, rel_w)
-    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
-        raise _lib.TipkError('distmult_pair_rank: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
-                             % (tuple(z.shape), tuple(rel_w.shape)))
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_pair_rank')
     dev = z.device
     pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit = _pair_rank_lists(pairs, tgt_ptr, tgt_rel,
                                                                                                known, dev)
@@ -1278,13 +1307,7 @@ def distmult_pair_rank(z, rel_w, pairs, tgt_ptr, tgt_rel, known=None):
 def pair_table_pair_rank(s1, s2, pairs, tgt_ptr, tgt_rel, known=None):
     """`distmult_pair_rank` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for both):
     the logit of (u, v, r) is s1[u, r] + s2[v, r] (not symmetric); `known` drops a relation in either pair direction."""
-    s1, s2 = _f32c(s1), _f32c(s2)
-    require_device(s1, s2)
-    if s1.dim() != 2 or s1.shape != s2.shape:
-        raise _lib.TipkError('pair_table_pair_rank: two tables [n, n_rel] expected, got %s and %s'
-                             % (tuple(s1.shape), tuple(s2.shape)))
-    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1] or s1.stride(1) != 1 or s2.stride(1) != 1:
-        s1, s2 = s1.contiguous(), s2.contiguous()
+    s1, s2 = _table_pair(s1, s2, 'pair_table_pair_rank')
     dev = s1.device
     pu, pv, tptr, trel, n_tgt, keys, kptr, krel, n_keys, out_rank, out_logit = _pair_rank_lists(pairs, tgt_ptr, tgt_rel,
                                                                                                known, dev)
@@ -1300,29 +1323,22 @@ def targets_by_query(edge_index, edge_type, n_nodes):
     int64 [T]): query q owns tgt_node[tgt_ptr[q]:tgt_ptr[q + 1]], the queries ascend by r * n_nodes + u, a query's targets
     keep the caller's order (repeats stay), and order[i] is the caller's position of grouped triple i:
     `out[order] = result` scatters a result back.  Torch ops on edge_index's device (CPU tensors work too)."""
-    edge_index, edge_type = torch.as_tensor(edge_index), torch.as_tensor(edge_type)
-    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_type.numel() != edge_index.shape[1] \
-            or edge_index.dtype.is_floating_point or edge_type.dtype.is_floating_point:
-        raise _lib.TipkError('triples: int tensors edge_index [2, T] and edge_type [T] expected, got %s %s and %s %s'
-                             % (edge_index.dtype, tuple(edge_index.shape), edge_type.dtype, tuple(edge_type.shape)))
+    edge_index, edge_type = _triples(edge_index, edge_type)
     n = int(n_nodes)
     key = edge_type.to(device=edge_index.device, dtype=torch.int64) * n + edge_index[0].to(torch.int64)
-    order = torch.sort(key, stable=True).indices
-    keys, counts = torch.unique_consecutive(key[order], return_counts=True)
-    tgt_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=key.device)
-    tgt_ptr[1:] = torch.cumsum(counts, 0)
+    keys, tgt_ptr, order = _group_by_key(key)
     q_rel = torch.div(keys, n, rounding_mode='floor').to(torch.int32)
     return q_rel, (keys % n).to(torch.int32), tgt_ptr, edge_index[1][order].to(torch.int32).contiguous(), order
 
 
 def _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known, dev):
     """(q_rel, q_drug, tgt_ptr, tgt_node, n_tgt, keys, ptr, out_rank, out_logit) of the partner rank entries, all on `dev`."""
-    q_rel, q_drug, tgt_ptr, tgt_node = (torch.as_tensor(t) for t in (q_rel, q_drug, tgt_ptr, tgt_node))
-    require_device(q_rel, q_drug, tgt_ptr, tgt_node)
-    if any(t.dim() != 1 or t.dtype.is_floating_point for t in (q_rel, q_drug, tgt_ptr, tgt_node)) \
-            or q_drug.numel() != q_rel.numel() or tgt_ptr.numel() != q_rel.numel() + 1:
-        raise _lib.TipkError('queries: int tensors q_rel [Q], q_drug [Q], tgt_ptr [Q + 1] and tgt_node [T] expected, got %s, %s, '
-                             '%s and %s' % tuple((t.dtype, tuple(t.shape)) for t in (q_rel, q_drug, tgt_ptr, tgt_node)))
+    q_rel, q_drug = torch.as_tensor(q_rel), torch.as_tensor(q_drug)
+    require_device(q_rel, q_drug)
+    if any(t.dim() != 1 or t.dtype.is_floating_point for t in (q_rel, q_drug)) or q_drug.numel() != q_rel.numel():
+        raise _lib.TipkError('queries: int tensors q_rel [Q] and q_drug [Q] expected, got %s %s and %s %s'
+                             % (q_rel.dtype, tuple(q_rel.shape), q_drug.dtype, tuple(q_drug.shape)))
+    tptr, tnode, n_tgt, out_rank, out_logit = _rank_targets(tgt_ptr, tgt_node, q_rel.numel(), dev)
     keys = kptr = None
     if known is not None:
         keys, kptr = known
@@ -1331,10 +1347,6 @@ def _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known, dev):
         if keys.numel() == 0:                                            # nothing to drop (empty tensors have no address)
             keys = kptr = None
     qr, qd = q_rel.to(torch.int32).contiguous(), q_drug.to(torch.int32).contiguous()
-    tptr, tnode = tgt_ptr.to(torch.int64).contiguous(), tgt_node.to(torch.int32).contiguous()
-    n_tgt = tnode.numel()
-    out_rank = torch.zeros((n_tgt,), dtype=torch.int32, device=dev)       # a target no query owns stays (0, NaN)
-    out_logit = torch.full((n_tgt,), float('nan'), dtype=torch.float32, device=dev)
     return qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit
 
 
@@ -1350,11 +1362,7 @@ def distmult_partner_rank(z, rel_w, q_rel, q_drug, tgt_ptr, tgt_node, known=None
     (r, u) of `distmult_screen` under the same filter.  The logit multiplies z[u] with rel_w[r] first: it is the screen's,
     not symmetric in (u, target) to the last bit.  (0, NaN): not ranked -- r outside [0, n_rel), u or the target outside
     [0, n), target == u, a NaN logit.  Does not synchronise."""
-    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
-    require_device(z, rel_w)
-    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
-        raise _lib.TipkError('distmult_partner_rank: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
-                             % (tuple(z.shape), tuple(rel_w.shape)))
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_partner_rank')
     dev = z.device
     qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit = _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known,
                                                                                       dev)
@@ -1367,13 +1375,7 @@ def distmult_partner_rank(z, rel_w, q_rel, q_drug, tgt_ptr, tgt_node, known=None
 def pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known=None):
     """`distmult_partner_rank` for the NN decoder's RELATION-major tables s1t, s2t [n_rel, n] (row stride free, the same for
     both), as `NNDecoder.objective` forms them: the logit of target c of query (r, u) is s1t[r, u] + s2t[r, c]."""
-    s1t, s2t = _f32c(s1t), _f32c(s2t)
-    require_device(s1t, s2t)
-    if s1t.dim() != 2 or s1t.shape != s2t.shape:
-        raise _lib.TipkError('pair_table_partner_rank: two tables [n_rel, n] expected, got %s and %s'
-                             % (tuple(s1t.shape), tuple(s2t.shape)))
-    if s1t.stride(0) != s2t.stride(0) or s1t.stride(0) < s1t.shape[1] or s1t.stride(1) != 1 or s2t.stride(1) != 1:
-        s1t, s2t = s1t.contiguous(), s2t.contiguous()
+    s1t, s2t = _table_pair(s1t, s2t, 'pair_table_partner_rank', '[n_rel, n]')
     dev = s1t.device
     qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit = _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known,
                                                                                       dev)
@@ -1424,11 +1426,7 @@ def distmult_regimen_topk(z, rel_w, reg_drugs, reg_ptr, k, aggregate='max', know
     contributes nothing.  -> (score float32 [G, k], relation int32 [G, k], pair_i int32 [G, k], pair_j int32 [G, k]):
     descending score then ascending relation id, (pair_i, pair_j) the list positions of the pair with the largest logit;
     (-inf, -1, -1, -1) pads a row with fewer than k candidates.  Does not synchronise."""
-    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
-    require_device(z, rel_w)
-    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
-        raise _lib.TipkError('distmult_regimen_topk: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
-                             % (tuple(z.shape), tuple(rel_w.shape)))
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_regimen_topk')
     dev = z.device
     drugs, rptr, n_g, k, agg, (keys, kptr, krel, n_keys), out_s, out_r, out_p = _regimen_args(reg_drugs, reg_ptr, k,
                                                                                               aggregate, known, dev)
@@ -1442,13 +1440,7 @@ def distmult_regimen_topk(z, rel_w, reg_drugs, reg_ptr, k, aggregate='max', know
 def pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate='max', known=None):
     """`distmult_regimen_topk` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for
     both): the logit of the position pair i < j under r is s1[d_i, r] + s2[d_j, r]."""
-    s1, s2 = _f32c(s1), _f32c(s2)
-    require_device(s1, s2)
-    if s1.dim() != 2 or s1.shape != s2.shape:
-        raise _lib.TipkError('pair_table_regimen_topk: two tables [n, n_rel] expected, got %s and %s'
-                             % (tuple(s1.shape), tuple(s2.shape)))
-    if s1.stride(0) != s2.stride(0) or s1.stride(0) < s1.shape[1] or s1.stride(1) != 1 or s2.stride(1) != 1:
-        s1, s2 = s1.contiguous(), s2.contiguous()
+    s1, s2 = _table_pair(s1, s2, 'pair_table_regimen_topk')
     dev = s1.device
     drugs, rptr, n_g, k, agg, (keys, kptr, krel, n_keys), out_s, out_r, out_p = _regimen_args(reg_drugs, reg_ptr, k,
                                                                                               aggregate, known, dev)
