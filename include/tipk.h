@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TIPK_ABI_VERSION 29
+#define TIPK_ABI_VERSION 30
 
 #define TIPK_OK            0
 #define TIPK_EINVAL      (-1)
@@ -299,6 +299,9 @@ int tipk_stream_gather(const float* table, int64_t ld_table, int64_t n_table, in
  *   GCNConv.lin                                               src/layers.py:392,394      (K1)
  * and their backward products.  Element (i,j) of A[z,q] is a[z*a_sz + q*a_sq + i*a_sm + j*a_sk]
  * (strides in floats, so transposes and the basis-decomposition reshapes need no copies).
+ *
+ * k == 0 is an empty sum: C[z] = relu?(C_in[z]), or zeros without c_in (every slab of a split product: zeros); a and b are
+ * not read and may be NULL.  m == 0, n == 0 or batch == 0: nothing is written.
  */
 typedef struct tipk_gemm_desc {
     int64_t m, n, k;
@@ -314,9 +317,50 @@ typedef struct tipk_gemm_desc {
 
 int tipk_gemm_f32(const tipk_gemm_desc* desc /* host */, tipk_stream_t stream);
 
+/* Which kernel body tipk_gemm_f32 runs for `desc` (grouped != 0: tipk_gemm_f32_group, for `desc` as a member), under the
+ * current "gemm_no_stream" / "gemm_thin_k_narrow" / "gemm_stream_kk" options.  A pure host function -- a, b, c and c_in are
+ * looked at as addresses only (NULL, alignment), nothing is launched -- and THE decision both entry points dispatch on.
+ * Returns the negative status tipk_gemm_f32 would return, else  body | flags:
+ *   body  (code & TIPK_ROUTE_BODY_MASK)
+ *     TIPK_ROUTE_NONE            nothing to compute (m, n or batch == 0)
+ *     TIPK_ROUTE_TILED_128X32    LDS-tiled, 4 x 1 waves of 32 x 32   (n <= 32)
+ *     TIPK_ROUTE_TILED_32X128    LDS-tiled, 1 x 4 waves              (m <= 32 < n)
+ *     TIPK_ROUTE_TILED_64X64     LDS-tiled, 2 x 2 waves
+ *     TIPK_ROUTE_TILED_128X128   LDS-tiled, 2 x 2 waves of 2 x 2 accumulators (m, n >= 512, ksplit == 1; never grouped: 64 x 64)
+ *     TIPK_ROUTE_THIN_K          streaming, k <= 32, dword accesses  (never grouped: tiled)
+ *     TIPK_ROUTE_THIN_K4         streaming, k <= 32, 16-byte accesses (n % 4 == 0, aligned rows; never grouped: tiled)
+ *     TIPK_ROUTE_THIN_M          streaming, m <= 32, long k
+ *     TIPK_ROUTE_KK              streaming, n <= 32, both operands contiguous in k ("gemm_stream_kk" only)
+ *   flags, tiled bodies only
+ *     TIPK_ROUTE_TWO_BUFFERS     two LDS buffers (unset: one -- a K range of a single 32-term tile, and every 128 x 128 product;
+ *                                grouped members always run with two)
+ *     TIPK_ROUTE_A_KFAST         consecutive threads of the A tile loader walk k (a_sk == 1 or a_sm != 1), else rows
+ *     TIPK_ROUTE_B_KFAST         the same for B (b_sk == 1 and b_sn != 1)
+ * The streaming bodies are chosen for products of >= 2^20 elements in m*n, n*k or m*k with kbatch == 1 and k >= 1
+ * (tip_amd/csrc/tipk_gemm.hip: stream_kind).  The narrow thin-k body, thin_m and every tiled body add the terms of one element in
+ * the same order: their results are bit-identical to each other; thin_k4 and kk pair k differently.  Non-finite inputs
+ * included: no body multiplies a term outside its k range (the streaming bodies clear BOTH operands of the lanes past the end
+ * of k), so an infinity in the last row of B gives the infinities of the fp64 product on every route. */
+#define TIPK_ROUTE_NONE 0
+#define TIPK_ROUTE_TILED_128X32 1
+#define TIPK_ROUTE_TILED_32X128 2
+#define TIPK_ROUTE_TILED_64X64 3
+#define TIPK_ROUTE_TILED_128X128 4
+#define TIPK_ROUTE_THIN_K 5
+#define TIPK_ROUTE_THIN_K4 6
+#define TIPK_ROUTE_THIN_M 7
+#define TIPK_ROUTE_KK 8
+#define TIPK_ROUTE_BODY_MASK 15
+#define TIPK_ROUTE_TWO_BUFFERS 16
+#define TIPK_ROUTE_A_KFAST 32
+#define TIPK_ROUTE_B_KFAST 64
+int tipk_gemm_route(const tipk_gemm_desc* desc /* host */, int grouped);
+
 /* Up to TIPK_GROUP_MAX independent products in ONE launch (no ordering between them; outputs must
  * not overlap any input of the group).  Each product is computed exactly as tipk_gemm_f32 would
- * (same tile shape and k order -> bit-identical).  Used where the path needs several small
+ * (same k order -> bit-identical; tipk_gemm_route(desc, 1) names the body: a product tipk_gemm_f32 would stream through the
+ * thin-k bodies runs LDS-tiled here -- the bits of the narrow thin-k body, not of thin_k4 -- and 128 x 128 tiles become
+ * 64 x 64).  Used where the path needs several small
  * products at the same point of the dependent chain: XB and X root going forward
  * (src/layers.py:163-172 and :184), d basis / d root / both halves of dX going back. */
 #define TIPK_GROUP_MAX 6
@@ -656,7 +700,8 @@ int tipk_pd_stage_bwd(const float* g, int64_t ld_g, const float* d_norm, const f
                       const float* row_scale, float* gw, int64_t ld_gw, float* dw2_slabs, float* db2_slabs,
                       tipk_stream_t stream);
 
-/* out[c] = sum_r in[r, c]  (bias gradients of GCNConv).  `scratch` holds >= 256*cols floats. */
+/* out[c] = sum_r in[r, c]  (bias gradients of GCNConv).  `scratch` holds >= 256*cols floats.  rows == 0: out = 0, `in` is
+ * not read and may be NULL. */
 int tipk_col_sum(const float* in, int64_t ld_in, int64_t rows, int64_t cols,
                  float* scratch, float* out, tipk_stream_t stream);
 

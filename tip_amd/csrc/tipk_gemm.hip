@@ -219,8 +219,9 @@ __device__ __forceinline__ void store_tile(const GemmArgs& g, const f32x16& acc,
 //    `global_load v, v_off, s[base]` -- one VGPR per address instead of a 64-bit pair;
 //  * loads are never guarded and never feed a select: out-of-range rows / columns are clamped (their
 //    products land in output rows / columns that are not stored) and out-of-range k is clamped and
-//    its A value is zeroed with a bitwise AND (a `cond ? v : 0` makes the compiler sink the load into
-//    a branch with a vmcnt(0) wait behind every single load);
+//    BOTH its values are zeroed with a bitwise AND (a `cond ? v : 0` makes the compiler sink the load into
+//    a branch with a vmcnt(0) wait behind every single load; clearing A alone would multiply 0 by the
+//    B value of the last valid k again -- NaN in a whole column where that value is infinite);
 //  * the k loop handles both register buffers per iteration (no if/else on the buffer index, which
 //    bounced the accumulator between AGPRs and VGPRs every step);
 //  * a sched_barrier separates "issue the next operands" from "multiply the current ones": left alone
@@ -294,6 +295,9 @@ __device__ __forceinline__ void gemm_thin_k_body(const GemmArgs& g, int64_t bloc
         if (!a_vec) av[kk] = and_mask(ldg(a_z, aoff + kc * a_sk), k < K ? 0xffffffffu : 0u);
         koff[kk] = kc * b_sk;
     }
+    // all ones where register kk holds a k inside K: B is cleared with it at use (recomputed there, not kept in 16 registers)
+    const int klim = WIDE ? K - 16 * kh : K - kh;          // register kk is inside K: kk < klim (wide) / 2 kk < klim
+    auto kmask = [&](int kk) { return (WIDE ? kk : 2 * kk) < klim ? 0xffffffffu : 0u; };
     const int nb = chunk * (32 * THIN_K_NT);
     // WIDE path (the normal case: 16-byte aligned rows, n % 4 == 0): the wave's 128 columns are taken as
     // four INTERLEAVED 32-column tiles -- tile s = columns 4j + s -- so lane j owns four consecutive columns:
@@ -311,10 +315,10 @@ __device__ __forceinline__ void gemm_thin_k_body(const GemmArgs& g, int64_t bloc
         f32x16 a0 = zero16(), a1 = zero16(), a2 = zero16(), a3 = zero16();
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
-            a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], b4[kk].x, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], b4[kk].y, a1, 0, 0, 0);
-            a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], b4[kk].z, a2, 0, 0, 0);
-            a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], b4[kk].w, a3, 0, 0, 0);
+            a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], and_mask(b4[kk].x, kmask(kk)), a0, 0, 0, 0);
+            a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], and_mask(b4[kk].y, kmask(kk)), a1, 0, 0, 0);
+            a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], and_mask(b4[kk].z, kmask(kk)), a2, 0, 0, 0);
+            a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], and_mask(b4[kk].w, kmask(kk)), a3, 0, 0, 0);
         }
         if (col >= N) return;
         float* c_t = c_z + (int64_t)m0 * g.c_sm + nb;       // 64-bit tile origin + 32-bit offsets (outputs > 4 GB)
@@ -351,7 +355,8 @@ __device__ __forceinline__ void gemm_thin_k_body(const GemmArgs& g, int64_t bloc
     for (int j = 0; j < THIN_K_NT; ++j) {
         f32x16 acc = zero16();
 #pragma unroll
-        for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], bt[j][kk], acc, 0, 0, 0);
+        for (int kk = 0; kk < 16; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], and_mask(bt[j][kk], kmask(kk)), acc, 0, 0, 0);
         store_tile32(g, acc, c_z, cin_z, m0, nb + 32 * j, lane);
     }
 }
@@ -389,8 +394,10 @@ __device__ __forceinline__ void gemm_thin_m_body(const GemmArgs& g, int64_t bloc
     __builtin_amdgcn_sched_barrier(0);
 #define TIPK_MMA(A, B, K0)                                                     \
     _Pragma("unroll") for (int kk = 0; kk < 16; ++kk)                          \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[kk], (K0) + 2 * kk + kh < k_hi ? 0xffffffffu : 0u), \
-                                                   B[kk], acc, 0, 0, 0);       \
+    {                                                                          \
+        const u32 mk_ = (K0) + 2 * kk + kh < k_hi ? 0xffffffffu : 0u;          \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[kk], mk_), and_mask(B[kk], mk_), acc, 0, 0, 0); \
+    }                                                                          \
     __builtin_amdgcn_sched_barrier(0);
     f32x16 acc = zero16();
     if (k_lo < k_hi) {
@@ -444,10 +451,10 @@ __device__ __forceinline__ void gemm_kk_body(const GemmArgs& g, int64_t block) {
 #define TIPK_KK_STEP(A, B, K0)                                                 \
     _Pragma("unroll") for (int q = 0; q < 4; ++q) {                            \
         const u32 mk_ = (K0) + 8 * q + 4 * kh < k_hi ? 0xffffffffu : 0u;       \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].x, mk_), B[q].x, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].y, mk_), B[q].y, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].z, mk_), B[q].z, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].w, mk_), B[q].w, acc, 0, 0, 0); \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].x, mk_), and_mask(B[q].x, mk_), acc, 0, 0, 0); \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].y, mk_), and_mask(B[q].y, mk_), acc, 0, 0, 0); \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].z, mk_), and_mask(B[q].z, mk_), acc, 0, 0, 0); \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(A[q].w, mk_), and_mask(B[q].w, mk_), acc, 0, 0, 0); \
     }                                                                          \
     __builtin_amdgcn_sched_barrier(0);
     f32x16 acc = zero16();
@@ -479,7 +486,7 @@ inline bool thin_k_wide_ok(const GemmArgs& g, int64_t batch) {
 
 // which streaming body serves this product (GemmArgs as filled by fill_args, batch = z count)
 inline int stream_kind(const GemmArgs& g, int64_t batch) {
-    if (g.kbatch != 1) return STREAM_NONE;
+    if (g.kbatch != 1 || g.k < 1) return STREAM_NONE;     // (k == 0: the clamps of the bodies below need one valid k)
     const bool big = g.m * g.n >= (1 << 20) || g.n * g.k >= (1 << 20) || g.m * g.k >= (1 << 20);
     if (!big) return STREAM_NONE;
     // 32-bit element offsets inside one operand (positive strides only)
@@ -554,17 +561,13 @@ __global__ __launch_bounds__(256) void gemm_f32_group_kernel(GemmGroupArgs ga) {
 }
 
 template <int WM, int WN, int R = 1>
-int launch(const GemmArgs& g, int64_t batch, hipStream_t st) {
-    constexpr int BM = WM * 32 * R, BN = WN * 32 * R;
-    const int64_t gx = tipk_ceil_div(g.n, BN), gy = tipk_ceil_div(g.m, BM), gz = batch * g.ksplit;
-    if (gx > 0x7fffffffLL || gy > 65535 || gz > 65535) return TIPK_EUNSUPPORTED;
-    dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz), block(256);
-    const bool akf = g.a_sk == 1 || g.a_sm != 1;      // k-contiguous (or generic) -> walk k
-    const bool bkf = g.b_sk == 1 && g.b_sn != 1;      // only when B is truly k-contiguous
-    const bool one_tile = g.kbatch == 1 && g.kchunk <= BK;
+int launch(const GemmArgs& g, const int64_t (&tiles)[3], int route, hipStream_t st) {
+    dim3 grid((unsigned)tiles[0], (unsigned)tiles[1], (unsigned)tiles[2]), block(256);      // as route_of counted and checked them
+    const bool akf = (route & TIPK_ROUTE_A_KFAST) != 0, bkf = (route & TIPK_ROUTE_B_KFAST) != 0;
+    const bool two = (route & TIPK_ROUTE_TWO_BUFFERS) != 0;
 #define TIPK_GEMM_GO(A, B)                                                                              \
     do {                                                                                                \
-        if (one_tile) hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, A, B, 1, R>), grid, block, 0, st, g); \
+        if (!two) hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, A, B, 1, R>), grid, block, 0, st, g);     \
         else hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, A, B, (R > 1 ? 1 : 2), R>), grid, block, 0, st, g); \
     } while (0)
     if (akf && bkf) TIPK_GEMM_GO(true, true);
@@ -740,7 +743,8 @@ __global__ __launch_bounds__(1024) void gemm_wgk_group_kernel(WgkArgs wa) {
         const int step = left < 0 ? 1 : 2;
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(av[kk], step * kk < lim ? m_mask : 0u), bv[kk], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(av[kk], step * kk < lim ? m_mask : 0u),
+                                                       and_mask(bv[kk], step * kk < lim ? 0xffffffffu : 0u), acc, 0, 0, 0);
     };
     const int t_lo = w * g.per, t_hi = t_lo + g.per < g.n_kt ? t_lo + g.per : g.n_kt;
     if (t_lo < t_hi) {
@@ -783,7 +787,7 @@ __global__ __launch_bounds__(1024) void gemm_wgk_group_kernel(WgkArgs wa) {
 static int fill_args(const tipk_gemm_desc* d, GemmArgs& g) {
     if (!d || d->m < 0 || d->n < 0 || d->k < 0 || d->batch < 0 || d->kbatch < 1 || d->ksplit < 1) return TIPK_EINVAL;
     if (d->m == 0 || d->n == 0 || d->batch == 0) return 1;
-    if (!d->a || !d->b || !d->c) return TIPK_EINVAL;
+    if (!d->c || (d->k > 0 && (!d->a || !d->b))) return TIPK_EINVAL;      // k == 0: nothing reads a / b
     if (d->ksplit > 1 && (d->c_in || d->relu)) return TIPK_EINVAL;
     // offsets inside one operand tile are 32-bit byte offsets (strides must be non-negative)
     if (d->a_sm < 0 || d->a_sk < 0 || d->b_sk < 0 || d->b_sn < 0) return TIPK_EINVAL;
@@ -799,16 +803,62 @@ static int fill_args(const tipk_gemm_desc* d, GemmArgs& g) {
     return TIPK_OK;
 }
 
+// THE route decision (include/tipk.h: tipk_gemm_route): which body serves the product, with how many LDS buffers and which
+// operand walks.  Fills g as the body wants it (the streaming bodies find the batch count in kbatch).  Negative: the status
+// tipk_gemm_f32 (grouped: tipk_gemm_f32_group, for this member alone) returns.  tiles: the grid of a tiled body (x, y, z).
+static int route_of(const tipk_gemm_desc* d, int grouped, GemmArgs& g, int64_t (&tiles)[3]) {
+    tiles[0] = tiles[1] = tiles[2] = 0;
+    const int rc = fill_args(d, g);
+    if (rc != TIPK_OK) return rc > 0 ? TIPK_ROUTE_NONE : rc;
+    const int64_t batch = d->batch;
+    int kind = tipk_option(TIPK_OPT_GEMM_NO_STREAM) ? STREAM_NONE : stream_kind(g, batch);
+    // thin-k is never grouped in the path: keeps the grouped kernel's registers down
+    if (grouped && (kind == STREAM_THIN_K || kind == STREAM_THIN_K4)) kind = STREAM_NONE;
+    if (kind != STREAM_NONE) {
+        if (stream_blocks(kind, g, batch) > (grouped ? 0x3fffffffLL : 0x7fffffffLL)) return TIPK_EUNSUPPORTED;
+        g.kbatch = batch;
+        return kind == STREAM_THIN_K ? TIPK_ROUTE_THIN_K : kind == STREAM_THIN_K4 ? TIPK_ROUTE_THIN_K4
+             : kind == STREAM_THIN_M ? TIPK_ROUTE_THIN_M : TIPK_ROUTE_KK;
+    }
+    int body = TIPK_ROUTE_TILED_64X64;
+    if (g.n <= 32) body = TIPK_ROUTE_TILED_128X32;
+    else if (g.m <= 32) body = TIPK_ROUTE_TILED_32X128;
+    else if (!grouped && g.m >= 512 && g.n >= 512 && g.ksplit == 1) body = TIPK_ROUTE_TILED_128X128;
+    const int bm = body == TIPK_ROUTE_TILED_128X32 || body == TIPK_ROUTE_TILED_128X128 ? 128 : (body == TIPK_ROUTE_TILED_32X128 ? 32 : 64);
+    const int bn = body == TIPK_ROUTE_TILED_32X128 || body == TIPK_ROUTE_TILED_128X128 ? 128 : (body == TIPK_ROUTE_TILED_128X32 ? 32 : 64);
+    const int64_t gx = tipk_ceil_div(g.n, bn), gy = tipk_ceil_div(g.m, bm), gz = batch * g.ksplit;
+    if (gx > (grouped ? 0x7fffffLL : 0x7fffffffLL) || gy > 65535 || gz > 65535) return TIPK_EUNSUPPORTED;
+    if (grouped && gx * gy * gz > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
+    tiles[0] = gx; tiles[1] = gy; tiles[2] = gz;
+    const bool akf = g.a_sk == 1 || g.a_sm != 1;      // k-contiguous (or generic) -> walk k
+    const bool bkf = g.b_sk == 1 && g.b_sn != 1;      // only when B is truly k-contiguous
+    // one LDS buffer: a K range of one tile, and the 128 x 128 body (two buffers of it do not fit); grouped members: always two
+    const bool one_tile = g.kbatch == 1 && g.kchunk <= BK;
+    const bool two = grouped || (body != TIPK_ROUTE_TILED_128X128 && !one_tile);
+    return body | (two ? TIPK_ROUTE_TWO_BUFFERS : 0) | (akf ? TIPK_ROUTE_A_KFAST : 0) | (bkf ? TIPK_ROUTE_B_KFAST : 0);
+}
+
+static int stream_kind_of_route(int body) {
+    return body == TIPK_ROUTE_THIN_K ? STREAM_THIN_K : body == TIPK_ROUTE_THIN_K4 ? STREAM_THIN_K4
+         : body == TIPK_ROUTE_THIN_M ? STREAM_THIN_M : body == TIPK_ROUTE_KK ? STREAM_KK : STREAM_NONE;
+}
+
+extern "C" int tipk_gemm_route(const tipk_gemm_desc* d, int grouped) {
+    GemmArgs g;
+    int64_t tiles[3];
+    return route_of(d, grouped != 0, g, tiles);
+}
+
 extern "C" int tipk_gemm_f32(const tipk_gemm_desc* d, tipk_stream_t stream) {
     GemmArgs g;
-    const int rc = fill_args(d, g);
-    if (rc != TIPK_OK) return rc > 0 ? TIPK_OK : rc;
+    int64_t tiles[3];
+    const int route = route_of(d, 0, g, tiles);
+    if (route < 0) return route;
     hipStream_t st = (hipStream_t)stream;
-    const int kind = tipk_option(TIPK_OPT_GEMM_NO_STREAM) ? STREAM_NONE : stream_kind(g, d->batch);
+    const int body = route & TIPK_ROUTE_BODY_MASK;
+    const int kind = stream_kind_of_route(body);
     if (kind != STREAM_NONE) {
         const int64_t blocks = stream_blocks(kind, g, d->batch);
-        if (blocks > 0x7fffffffLL) return TIPK_EUNSUPPORTED;
-        g.kbatch = d->batch;                            // the streaming bodies find the batch count here
         if (kind == STREAM_THIN_K)
             hipLaunchKernelGGL(gemm_stream_kernel<STREAM_THIN_K>, dim3((unsigned)blocks), dim3(256), 0, st, g);
         else if (kind == STREAM_THIN_K4)
@@ -819,10 +869,13 @@ extern "C" int tipk_gemm_f32(const tipk_gemm_desc* d, tipk_stream_t stream) {
             hipLaunchKernelGGL(gemm_stream_kernel<STREAM_KK>, dim3((unsigned)blocks), dim3(256), 0, st, g);
         TIPK_RETURN_LAUNCH();
     }
-    if (d->n <= 32) return launch<4, 1>(g, d->batch, st);
-    if (d->m <= 32) return launch<1, 4>(g, d->batch, st);
-    if (d->m >= 512 && d->n >= 512 && d->ksplit == 1) return launch<2, 2, 2>(g, d->batch, st);   // 128 x 128 tiles
-    return launch<2, 2>(g, d->batch, st);
+    switch (body) {
+    case TIPK_ROUTE_NONE: return TIPK_OK;
+    case TIPK_ROUTE_TILED_128X32: return launch<4, 1>(g, tiles, route, st);
+    case TIPK_ROUTE_TILED_32X128: return launch<1, 4>(g, tiles, route, st);
+    case TIPK_ROUTE_TILED_128X128: return launch<2, 2, 2>(g, tiles, route, st);
+    default: return launch<2, 2>(g, tiles, route, st);
+    }
 }
 
 extern "C" int tipk_gemm_f32_group(const tipk_gemm_desc* descs, int32_t count, tipk_stream_t stream) {
@@ -830,38 +883,29 @@ extern "C" int tipk_gemm_f32_group(const tipk_gemm_desc* descs, int32_t count, t
     GemmGroupArgs ga;
     ga.count = 0;
     int64_t blocks = 0;
-    const bool no_stream = tipk_option(TIPK_OPT_GEMM_NO_STREAM) != 0;
     for (int i = 0; i < count; ++i) {
         GemmArgs& g = ga.g[ga.count];
-        const int rc = fill_args(descs + i, g);
-        if (rc < 0) return rc;
-        if (rc > 0) continue;
-        int kind = no_stream ? STREAM_NONE : stream_kind(g, descs[i].batch);
-        if (kind == STREAM_THIN_K || kind == STREAM_THIN_K4) kind = STREAM_NONE;   // never grouped in the path: keeps the grouped kernel's registers down
+        int64_t tiles[3];
+        const int route = route_of(descs + i, 1, g, tiles);
+        if (route < 0) return route;
+        const int body = route & TIPK_ROUTE_BODY_MASK;
+        if (body == TIPK_ROUTE_NONE) continue;
+        const int kind = stream_kind_of_route(body);
+        int64_t nb;
         if (kind != STREAM_NONE) {
-            const int64_t nb = stream_blocks(kind, g, descs[i].batch);
-            if (nb > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
-            g.kbatch = descs[i].batch;
+            nb = stream_blocks(kind, g, descs[i].batch);
             ga.cfg[ga.count] = 100 + kind;
             ga.gx[ga.count] = 1;
             ga.gy[ga.count] = 1;
-            ga.first_block[ga.count] = (int)blocks;
-            blocks += nb;
-            if (blocks > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
-            ++ga.count;
-            continue;
+        } else {
+            const int shape = body == TIPK_ROUTE_TILED_128X32 ? 0 : (body == TIPK_ROUTE_TILED_32X128 ? 1 : 2);
+            ga.cfg[ga.count] = shape * 4 + ((route & TIPK_ROUTE_A_KFAST) ? 2 : 0) + ((route & TIPK_ROUTE_B_KFAST) ? 1 : 0);
+            ga.gx[ga.count] = (int)tiles[0];
+            ga.gy[ga.count] = (int)tiles[1];
+            nb = tiles[0] * tiles[1] * tiles[2];
         }
-        const int shape = g.n <= 32 ? 0 : (g.m <= 32 ? 1 : 2);
-        const int bm = shape == 0 ? 128 : (shape == 1 ? 32 : 64), bn = shape == 0 ? 32 : (shape == 1 ? 128 : 64);
-        const bool akf = g.a_sk == 1 || g.a_sm != 1;
-        const bool bkf = g.b_sk == 1 && g.b_sn != 1;
-        const int64_t gx = tipk_ceil_div(g.n, bn), gy = tipk_ceil_div(g.m, bm), gz = descs[i].batch * g.ksplit;
-        if (gx > 0x7fffffLL || gy > 65535 || gz > 65535 || gx * gy * gz > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
-        ga.cfg[ga.count] = shape * 4 + (akf ? 2 : 0) + (bkf ? 1 : 0);
-        ga.gx[ga.count] = (int)gx;
-        ga.gy[ga.count] = (int)gy;
         ga.first_block[ga.count] = (int)blocks;
-        blocks += gx * gy * gz;
+        blocks += nb;
         if (blocks > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
         ++ga.count;
     }
@@ -895,7 +939,7 @@ extern "C" int tipk_sum_slabs_group(const tipk_slab_sum_desc* descs, int32_t cou
 static int fill_wgk(const tipk_wg_gemm_desc& d, WgkJob& j) {
     const tipk_gemm_desc& p = d.p;
     if (p.m <= 0 || p.n <= 0 || p.k < 0 || p.batch <= 0 || p.kbatch < 1 || p.ksplit != 1) return TIPK_EINVAL;
-    if (!p.a || !p.b || !p.c || p.a_sm < 0 || p.a_sk < 0 || p.b_sk < 0 || p.b_sn < 0) return TIPK_EINVAL;
+    if (!p.c || (p.k > 0 && (!p.a || !p.b)) || p.a_sm < 0 || p.a_sk < 0 || p.b_sk < 0 || p.b_sn < 0) return TIPK_EINVAL;
     const bool second = d.a2 != nullptr;
     if (second && (!d.b2 || d.k2 <= 0 || p.batch != 1 || d.a2_sm < 0 || d.a2_sk < 0 || d.b2_sk < 0 || d.b2_sn < 0)) return TIPK_EINVAL;
     const int64_t lim = 1LL << 30;                       // element offsets inside one term: 32-bit byte offsets

@@ -183,7 +183,7 @@ extern "C" int tipk_col_sum(const float* in, int64_t ld_in, int64_t rows, int64_
                             tipk_stream_t stream) {
     if (rows < 0 || cols < 0) return TIPK_EINVAL;
     if (cols == 0) return TIPK_OK;
-    if (!in || !out || !scratch) return TIPK_EINVAL;
+    if (!out || !scratch || (rows > 0 && !in)) return TIPK_EINVAL;       // rows == 0: an empty sum, `in` is not read
     const int cl = cols < 256 ? (int)cols : 256;
     const int lanes_r = 256 / cl;
     int64_t groups = tipk_ceil_div(rows, (int64_t)lanes_r * 8);
