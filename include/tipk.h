@@ -1032,6 +1032,56 @@ int     tipk_pair_table_partner_rank(const float* s1t, const float* s2t, int64_t
                                      int32_t* out_rank, float* out_logit /* nullable */, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * 4h. Screen rank: the filtered rank of given drug pairs (held-out pairs) among ALL unordered pairs, per relation query, on
+ *     the logit (evaluation of what the relation queries of 4c serve: "Hits@50 of relation r" is how many held-out pairs the
+ *     screen's 50 best show -- Decagon's AP@50 idea; no reference call site).  DistMult only, as 4c.
+ *
+ *   Input, query-major, DEVICE: q_rel int32 [n_q]; tgt_ptr int64 [n_q + 1], tgt_u / tgt_v int32 [n_tgt]: query q is relation
+ *   q_rel[q] and owns the target pairs tgt_u/tgt_v[tgt_ptr[q] : tgt_ptr[q+1]].  Targets may come in any order, may repeat, a
+ *   query may have none, and two queries may name the same relation.  tgt_ptr is clamped to n_tgt: positions outside
+ *   [0, n_tgt) are neither read nor written.
+ *   Pair form: a target (u, v) is ranked as the unordered pair (a, b) = (min, max) with key a*n+b; (u, v) and (v, u) give the
+ *   same rank and the same logit bits.
+ *   Logits: bit for bit those of a 4c relation query -- x_k = z[a,k] * w[r,k] rounded once, then acc = fmaf(x_k, z[b,k], acc)
+ *   for k ascending from 0 -- for the candidates and, by the same arithmetic, for the targets.
+ *   Candidates of relation r: every pair a < b < n_nodes with neither a*n+b nor b*n+a a key of r in the relation-major lists
+ *   of 4c (known_keys sorted inside each relation, known_ptr [n_rel + 1]; nullable together; lists that hold one direction
+ *   only are handled; keys outside [0, n^2) are ignored).  Whether a target is itself listed changes only whether it is a
+ *   candidate for OTHER targets; it is never counted against itself.
+ *   Rank (1-based): rank(t) = 1 + #{candidates c != t : L[c] > L[t] or (L[c] == L[t] and key(c) < key(t))} -- the total order
+ *   of 4c.  A candidate whose logit is NaN beats nothing.
+ *   Relation to 4c: run the 4c relation query (r, -1) under the same known list.  A target that is not listed sits at
+ *   position rank - 1 of that list (with the same logit bits); for a listed target, rank - 1 is the number of list entries
+ *   that are better than it.
+ *   Output per target (device): out_rank int32 [n_tgt]; out_logit fp32 [n_tgt] (nullable) = the target's logit.
+ *   Not ranked -- rank 0, logit NaN, nothing read out of bounds: q_rel[q] outside [0, n_rel) (every target of that query),
+ *   u or v outside [0, n_nodes), u == v, a target whose logit is NaN.
+ *   Filter routes: the LDS bitmap of the relation's known pairs exactly where tipk_distmult_screen_bitmap_route(n_nodes) says
+ *   so, binary search in the keys otherwise or under option "screen_search"; same bits.
+ *   Passes: a workgroup ranks tipk_distmult_screen_rank_chunk() targets of its query per pass over its candidates; a query
+ *   with more targets takes several passes (any number of targets per query).
+ *   Supported (tipk_distmult_screen_rank_supported): 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (z 16-byte aligned),
+ *   1 <= n_rel <= 65 536.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes, n_rel or dim < 1, a NULL
+ *   required pointer (z, rel_w, the lists, out_rank; with n_q > 0 and n_tgt > 0), keys without offsets or the reverse, a NULL
+ *   workspace where tipk_distmult_screen_rank_workspace_bytes > 0; then TIPK_EUNSUPPORTED outside the supported range or for
+ *   a misaligned z; n_q == 0 or n_tgt == 0 is TIPK_OK with no launch; TIPK_OK implies correct numbers.
+ *   workspace: tipk_distmult_screen_rank_workspace_bytes(n_nodes, dim, n_q, n_tgt) bytes (-1: unsupported).  It is 0 today --
+ *   the per-part counts are summed in out_rank itself with integer atomics -- and workspace may then be NULL.
+ *   Nothing lives in host memory: the entry does NOT synchronise, may be captured into a hipGraph (two launches) and is
+ *   BITWISE repeatable, run to run and route to route (integer counts; no float atomics).
+ */
+int     tipk_distmult_screen_rank_supported(int64_t n_nodes, int dim, int64_t n_rel);
+int64_t tipk_distmult_screen_rank_workspace_bytes(int64_t n_nodes, int dim, int64_t n_q, int64_t n_tgt);   /* -1: unsupported; may be 0 */
+int     tipk_distmult_screen_rank_chunk(void);      /* targets of one query ranked per pass (host query; tests read it) */
+int     tipk_distmult_screen_rank(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                  const int32_t* q_rel /* device [n_q] */, int64_t n_q,
+                                  const int64_t* tgt_ptr /* device [n_q+1] */,
+                                  const int32_t* tgt_u, const int32_t* tgt_v /* device [n_tgt] */, int64_t n_tgt,
+                                  const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                                  int32_t* out_rank, float* out_logit /* nullable */, void* workspace, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).
  *

@@ -834,6 +834,12 @@ class MultiInnerProductDecoder(nn.Module):
         q_rel, q_drug [Q], tgt_ptr [Q + 1], tgt_node [T]: `ops.targets_by_query`.  known: (keys, ptr) as `screen`."""
         return ops.distmult_partner_rank(z.detach(), self.weight.detach(), q_rel, q_drug, tgt_ptr, tgt_node, known)
 
+    def pair_ranks(self, z, q_rel, tgt_ptr, tgt_u, tgt_v, known=None):
+        """Screen rank (extension, `tipk_distmult_screen_rank`): the rank of every target pair among all unordered pairs of
+        its relation query by the screen's LOGIT -> (rank int32 [T], logit [T]), rank 0 = not ranked; no autograd.
+        q_rel [Q], tgt_ptr [Q + 1], tgt_u, tgt_v [T]: `ops.targets_by_relation`.  known: (keys, ptr) as `screen`."""
+        return ops.distmult_screen_rank(z.detach(), self.weight.detach(), q_rel, tgt_ptr, tgt_u, tgt_v, known)
+
     def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
         """Regimen top-k (extension, `tipk_distmult_regimen_topk`): the k best relations of every drug list of the CSR pair
         (reg_drugs, reg_ptr) by the aggregate of its pairs' LOGITS -> (score [G, k], relation int32 [G, k], pair_i, pair_j
@@ -1358,6 +1364,53 @@ class TIP(nn.Module):
         with torch.no_grad():
             q_rel, q_drug, tgt_ptr, tgt_node, order = ops.targets_by_query(idx, et, d.n_drug)
             r, s = self.decoder.partner_ranks(self.embeddings, q_rel, q_drug, tgt_ptr, tgt_node, known)
+            rank = torch.empty_like(r, dtype=torch.int64)
+            rank[order] = r.to(torch.int64)
+            logit = torch.empty_like(s)
+            logit[order] = s
+        return RankReport(rank, logit, **rank_report(rank, et, d.n_dd_et, ks))
+
+    def rank_pairs(self, triples=None, filter='all', ks=(1, 10, 50)):
+        """Evaluation of what the relation screen `screen()` serves (extension): where the pair {u, v} of each given (drug u,
+        drug v, side effect r) triple lands among ALL drug pairs not recorded for r, and filtered MRR / Hits@k over the
+        triples, micro and per side effect (`decoder.pair_ranks`: one `tipk_distmult_screen_rank` call on `self.embeddings`,
+        under no_grad; DistMult only, as `screen`).
+        triples: None = the held-out set (data.dd_test_idx, data.dd_test_et), which is stored in both directions, so every
+        pair appears twice with equal ranks; else (edge_index int [2, T], edge_type int [T]): (u, v) and (v, u) are one pair.
+        filter: 'all' drops the train and test positives of r (the standard filtered setting), 'train' only its training
+        ones -- exactly what `screen(exclude='train')` shows: rank - 1 is the pair's position there, and Hits@50 of side
+        effect r is the share of its held-out pairs among that screen's 50 best -- and None nothing (the raw rank); the keys
+        are `screen`'s, a recorded pair is dropped in either direction, the triple's own pair is never counted against itself.
+        A triple with v == u is not ranked.  Ranks are 1-based on the screen's logit, ties by ascending key min * n + max.
+        -> RankReport(rank int64 [T] (0 = not ranked), logit [T] (NaN there), mrr, hits {k: share of ranks <= k},
+        per_relation {'count' [R], 'mrr' [R], 'hits' [len(ks), R]}, macro_mrr, unranked): `utils.rank_report` of the ranks;
+        the tensors are on the model's device, in the triples' order."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('rank_pairs ranks DistMult logits over all pairs; the NN decoder has no screen kernel')
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the pairs '
+                                      'with the unsharded model (tip_amd.dist.gather_state_dict)')
+        if filter not in ('train', 'all', None):
+            raise ValueError("filter must be 'train', 'all' or None, not %r" % (filter,))
+        d = self.data
+        dev = self.embeddings.device
+        idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
+        idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
+        if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
+                or idx.dtype.is_floating_point or et.dtype.is_floating_point:
+            raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
+                             % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
+        if et.numel():
+            lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
+            if lo < 0 or hi >= d.n_drug:
+                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
+            if rlo < 0 or rhi >= d.n_dd_et:
+                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
+        known = _screen_known(d, filter)
+        et = et.to(torch.int64)
+        with torch.no_grad():
+            q_rel, tgt_ptr, tgt_u, tgt_v, order = ops.targets_by_relation(idx, et, d.n_dd_et)
+            r, s = self.decoder.pair_ranks(self.embeddings, q_rel, tgt_ptr, tgt_u, tgt_v, known)
             rank = torch.empty_like(r, dtype=torch.int64)
             rank[order] = r.to(torch.int64)
             logit = torch.empty_like(s)

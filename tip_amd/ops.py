@@ -1385,6 +1385,57 @@ def pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known=No
     return out_rank, out_logit
 
 
+def targets_by_relation(edge_index, edge_type, n_rel):
+    """Triples (u, v, r) grouped by the relation query r that ranks the pair {u, v} -- for the screen rank entry
+    (include/tipk.h section 4h) -> (q_rel int32 [Q], tgt_ptr int64 [Q + 1], tgt_u int32 [T], tgt_v int32 [T], order int64
+    [T]): one query per relation that has triples, relations ascending; query q owns tgt_u/tgt_v[tgt_ptr[q]:tgt_ptr[q + 1]]
+    in the given orientation and the caller's order (repeats stay), and order[i] is the caller's position of grouped triple
+    i: `out[order] = result` scatters a result back.  n_rel only documents the id range (ids are not checked here: the
+    entry leaves a query outside [0, n_rel) unranked).  Torch ops on edge_index's device (CPU tensors work too)."""
+    edge_index, edge_type = _triples(edge_index, edge_type)
+    keys, tgt_ptr, order = _group_by_key(edge_type.to(device=edge_index.device, dtype=torch.int64))
+    return (keys.to(torch.int32), tgt_ptr, edge_index[0][order].to(torch.int32).contiguous(),
+            edge_index[1][order].to(torch.int32).contiguous(), order)
+
+
+def distmult_screen_rank(z, rel_w, q_rel, tgt_ptr, tgt_u, tgt_v, known=None):
+    """The filtered rank of given drug pairs among all unordered pairs, per relation query, by DistMult logit (include/tipk.h
+    section 4h).
+
+    q_rel: int tensor [Q]; tgt_ptr int [Q + 1], tgt_u / tgt_v int [T]: query q is relation q_rel[q] and owns the target pairs
+    tgt_u/tgt_v[tgt_ptr[q]:tgt_ptr[q+1]] (`targets_by_relation`); known: None or (keys int64 u*n+v sorted inside each
+    relation, ptr int64 [n_rel + 1]), the relation-major lists `distmult_screen` takes; all on the device.
+    -> (rank int32 [T], logit float32 [T]): rank = 1 + the number of pairs a < b, with neither a*n+b nor b*n+a listed for r,
+    that beat the target (higher logit, or equal logit and lower key); rank - 1 is the pair's position in the relation query
+    (r, -1) of `distmult_screen` under the same filter, and the logit is that query's, equal for (u, v) and (v, u).
+    (0, NaN): not ranked -- r outside [0, n_rel), u or v outside [0, n), u == v, a NaN logit.  Does not synchronise."""
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_screen_rank')
+    dev = z.device
+    q_rel, tgt_v = torch.as_tensor(q_rel), torch.as_tensor(tgt_v)
+    require_device(q_rel, tgt_v)
+    if q_rel.dim() != 1 or q_rel.dtype.is_floating_point:
+        raise _lib.TipkError('queries: an int tensor q_rel [Q] expected, got %s %s' % (q_rel.dtype, tuple(q_rel.shape)))
+    tptr, tu, n_tgt, out_rank, out_logit = _rank_targets(tgt_ptr, tgt_u, q_rel.numel(), dev)
+    if tgt_v.dim() != 1 or tgt_v.numel() != n_tgt or tgt_v.dtype.is_floating_point:
+        raise _lib.TipkError('targets: int tensors tgt_u [%d] and tgt_v [%d] expected, got tgt_v %s %s'
+                             % (n_tgt, n_tgt, tgt_v.dtype, tuple(tgt_v.shape)))
+    keys = kptr = None
+    if known is not None:
+        keys, kptr = known
+        require_device(keys, kptr)
+        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+        if keys.numel() == 0:                                            # nothing to drop (empty tensors have no address)
+            keys = kptr = None
+    qr, tv = q_rel.to(torch.int32).contiguous(), tgt_v.to(torch.int32).contiguous()
+    n, dim = z.shape
+    ws_bytes = int(lib().tipk_distmult_screen_rank_workspace_bytes(n, dim, qr.numel(), n_tgt))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    check(lib().tipk_distmult_screen_rank(ptr(z), n, dim, ptr(rel_w), rel_w.shape[0], ptr(qr), qr.numel(), ptr(tptr), ptr(tu),
+                                          ptr(tv), n_tgt, ptr(keys), ptr(kptr), ptr(out_rank), ptr(out_logit), ptr(ws),
+                                          stream_ptr(dev)), 'tipk_distmult_screen_rank')
+    return out_rank, out_logit
+
+
 REGIMEN_AGGREGATES = {'max': 0, 'noisy_or': 1}                        # TIPK_REGIMEN_MAX, TIPK_REGIMEN_NOISY_OR
 
 
