@@ -61,6 +61,8 @@ const char* tipk_build_id(void);
  *                            (section 4f; both routes return the same bits)
  *      "partner_rank_global" 1 = tipk_distmult_partner_rank reads z rows from global memory even where the LDS image fits
  *                            (section 4g; both routes return the same bits)
+ *      "addon_global"        1 = tipk_distmult_addon_burden reads rel_w rows from global memory even where the LDS image
+ *                            fits (section 4i; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -1080,6 +1082,81 @@ int     tipk_distmult_screen_rank(const float* z, int64_t n_nodes, int dim, cons
                                   const int32_t* tgt_u, const int32_t* tgt_v /* device [n_tgt] */, int64_t n_tgt,
                                   const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
                                   int32_t* out_rank, float* out_logit /* nullable */, void* workspace, tipk_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * 4i. Add-on burden: the expected weighted number of side effects a CANDIDATE drug brings to a patient's drug list through
+ *     its own pairs with that list, per (query, candidate), and the k candidates of every query with the lowest burden
+ *     (serving; the prescriptive question after 4e: which drug to add, or which replacement; no reference call site).
+ *
+ *   Contexts, CSR, DEVICE: ctx_drugs int32 [n_entries], ctx_ptr int64 [n_q + 1].  Context q is the list
+ *   ctx_drugs[ctx_ptr[q] .. ctx_ptr[q+1]) of the drugs the patient already takes, in list order.
+ *   Candidates, DEVICE: cand int32, cand_ptr int64 [n_q + 1]: query q owns the entries cand[cand_ptr[q] .. cand_ptr[q+1]) and
+ *   n_cand is the total number of entries (= cand_ptr[n_q]).  cand_ptr == NULL: the ONE list cand[0 .. n_cand) is shared by
+ *   all queries.  A TASK is one (query, candidate entry); the position of a task is its index in its query's list.
+ *   weights fp32 [n_rel], nullable (NULL: every weight is 1): finite and >= 0, e.g. a severity per side effect.
+ *   Logit of (c, s, r), c the candidate, s a context drug: exactly that of 4d.  DistMult: h_k = z[c,k] * z[s,k] rounded
+ *   once, then acc = fmaf(h_k, w[r,k], acc) for k ascending from 0 -- the same bits for (c, s) and (s, c).  Table variant:
+ *   the single fp32 add s1[u,r] + s2[v,r] with u = min(c, s), v = max(c, s): what 4e scores for the sorted list S + {c}.
+ *   A triple contributes nothing when it is KNOWN: listed for the pair's unordered key in the pair-major lists
+ *   (known_pair_keys, known_pair_ptr, known_rel) of 4d, nullable together.
+ *   Per task (q, c) and relation r, over the context drugs s of q in list order, chosen by `aggregate` (the constants of 4e):
+ *     TIPK_REGIMEN_NOISY_OR  A_r = sum over the contributing triples, in context order, in fp32 (A_r starts at 0.0f and each
+ *                            term is added with one rounding), of softplus(s) = fmaxf(s, 0) + log1pf(expf(-fabsf(s))) -- the
+ *                            formula of 4e --, and P_r = -expm1f(-A_r): the probability that at least one pair causes r.
+ *     TIPK_REGIMEN_MAX       P_r = sigma(L) = 1.0f / (1.0f + expf(-L)), L the largest contributing logit.
+ *   A relation with no contributing triple has P_r = 0.
+ *   Burden B = sum over r of weights[r] * P_r, an fp32 sum in this fixed order: with l = r mod 64, b_l starts at 0.0f and
+ *   takes b_l = fmaf(weights[r], P_r, b_l) for r = l, l + 64, l + 128, ... ascending; then for off = 32, 16, 8, 4, 2, 1:
+ *   b_l = b_l + b_(l + off) for l < off; B = b_0.  The order does not depend on the data, the grid, the route or the other
+ *   tasks of the call, and the result is BITWISE repeatable.
+ *   NOT APPLICABLE -- the burden is NaN, the task is never selected, nothing is read out of bounds: c outside
+ *   [0, n_nodes); c occurs in its query's context; a context of 0 or of more than tipk_addon_max_context() (64) entries; a
+ *   context that holds an id outside [0, n_nodes); any triple of the task that is not known has a NaN logit (under either
+ *   aggregate, whatever the relation's weight); an entry of cand that no query of cand_ptr owns.
+ *   Output (device): out_burden fp32, one per task: [n_cand] in the order of cand (cand_ptr given) or [n_q x n_cand] (shared
+ *   list).  k > 0: out_best_burden fp32 [n_q x k] and out_best_pos int32 [n_q x k] = the k tasks of each query with the
+ *   lowest burden, ascending, ties by ascending position; the selection reads the fp32 values written to out_burden, so the
+ *   returned values are bit-equal to out_burden[position]; a row with fewer than k applicable tasks is padded with
+ *   (+inf, -1).  k == 0 skips the selection and both pointers may be NULL.
+ *   Work: one launch with one wavefront per task (a lane keeps one context drug, lanes own relations as in 4e, the wave
+ *   reduces at the end), then, for k > 0, one launch with one wavefront per query on the same stream.
+ *   Routes (DistMult): rel_w is staged in LDS once per workgroup when it fits beside the wavefronts' state
+ *   (tipk_distmult_addon_burden_lds_route: 1 097 x 16 does); otherwise, or under option "addon_global", every lane reads its
+ *   rows from global memory; same bits.
+ *   Supported: as 4e -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; rel_w 16-byte aligned), 1 <= n_rel <=
+ *   65 536, 0 <= k <= 128; at most 2^31 - 1 candidate entries (n_cand).
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k < 0, a negative size, n_nodes or n_rel < 1,
+ *   ld < n_rel, an unknown `aggregate`, a NULL required pointer (ctx_drugs, ctx_ptr, cand, the tables, out_burden, and with
+ *   k > 0 the two best outputs; with n_q > 0 and n_cand > 0), known arrays given only in part; then TIPK_EUNSUPPORTED outside
+ *   the supported range; n_q == 0 or n_cand == 0 is TIPK_OK with no launch and nothing written; TIPK_OK implies correct
+ *   numbers.
+ *   workspace: tipk_distmult_addon_burden_workspace_bytes(...) bytes (-1: unsupported); 0 for every supported shape today
+ *   and `workspace` may then be NULL.
+ *   Nothing lives in host memory: these entries do NOT synchronise and may be captured into a hipGraph (sequential launches,
+ *   no parallel branches).
+ */
+int     tipk_addon_max_context(void);
+int     tipk_distmult_addon_burden_supported(int64_t n_nodes, int dim, int64_t n_rel, int k);
+int64_t tipk_distmult_addon_burden_workspace_bytes(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_q, int64_t n_cand,
+                                                   int k);
+int     tipk_distmult_addon_burden_lds_route(int dim, int64_t n_rel);   /* 1 = rel_w is staged in LDS once (options apply) */
+int     tipk_distmult_addon_burden(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                   const int32_t* ctx_drugs, const int64_t* ctx_ptr /* device */, int64_t n_q,
+                                   const int32_t* cand, const int64_t* cand_ptr /* device; nullable: shared list */,
+                                   int64_t n_cand, const float* weights /* nullable */,
+                                   const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                   int64_t n_known_pairs /* nullable together */,
+                                   int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
+                                   int32_t* out_best_pos /* nullable with k == 0 */, void* workspace, tipk_stream_t stream);
+int     tipk_pair_table_addon_burden_supported(int64_t n_nodes, int64_t n_rel, int k);
+int     tipk_pair_table_addon_burden(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                     const int32_t* ctx_drugs, const int64_t* ctx_ptr /* device */, int64_t n_q,
+                                     const int32_t* cand, const int64_t* cand_ptr /* device; nullable: shared list */,
+                                     int64_t n_cand, const float* weights /* nullable */,
+                                     const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                     int64_t n_known_pairs /* nullable together */,
+                                     int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
+                                     int32_t* out_best_pos /* nullable with k == 0 */, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

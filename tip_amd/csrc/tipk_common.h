@@ -37,7 +37,8 @@ enum {
     TIPK_OPT_REGIMEN_GLOBAL = 10,     // tipk_distmult_regimen_topk: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_PAIR_RANK_STREAM = 11,   // tipk_distmult_pair_rank: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_PARTNER_RANK_GLOBAL = 12, // tipk_distmult_partner_rank: z rows read from global memory even where the LDS image fits
-    TIPK_OPT_COUNT = 13
+    TIPK_OPT_ADDON_GLOBAL = 13,       // tipk_distmult_addon_burden: rel_w rows read from global memory even where the LDS image fits
+    TIPK_OPT_COUNT = 14
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

@@ -40,8 +40,6 @@ struct RegimenArgs {
     int32_t* out_p;
 };
 
-__device__ __forceinline__ float softplus(float s) { return fmaxf(s, 0.f) + log1pf(expf(-fabsf(s))); }
-
 template <int MODE, bool IMAGE>
 __global__ void __launch_bounds__(WT_NT) regimen_topk_kernel(RegimenArgs a) {
     extern __shared__ __align__(16) unsigned char rg_smem[];
@@ -145,7 +143,7 @@ __global__ void __launch_bounds__(WT_NT) regimen_topk_kernel(RegimenArgs a) {
                         }
                         if (take) {
                             if (bpr[x] < 0 || s > best[x]) { best[x] = s; bpr[x] = tag; }   // ties: the first in pair order
-                            if (a.noisy) agg[x] += softplus(s);
+                            if (a.noisy) agg[x] += wt_softplus(s);
                         }
                     }
                 }

@@ -1,8 +1,8 @@
 // The one home of what the wave-per-row kernels share (tipk_pair_topk.hip, tipk_regimen_topk.hip, tipk_pair_rank.hip,
-// tipk_partner_rank.hip; include/tipk.h sections 4d, 4e, 4f, 4g).  A workgroup of WT_NT threads takes blocks of WT_NW rows
-// (pairs, regimens, queries), ONE WAVEFRONT PER ROW.  The kernels must agree to the bit, so each piece exists once:
+// tipk_partner_rank.hip, tipk_addon_burden.hip; include/tipk.h sections 4d, 4e, 4f, 4g, 4i).  A workgroup of WT_NT threads
+// takes blocks of WT_NW rows (pairs, regimens, queries, tasks), ONE WAVEFRONT PER ROW.  The kernels must agree to the bit, so each piece exists once:
 //   logits     wt_stage_rows (LDS image, bank-spreading stride wt_stride), wt_write_row / wt_row16 (the wave's product row
-//              and its dim-16 register copy), wt_dot (THE fma chain, k ascending)
+//              and its dim-16 register copy), wt_dot (THE fma chain, k ascending), wt_softplus (the noisy-or term)
 //   known      find_key, wt_lower_bound (64-ary searches), wt_merge_window (ids of a window -> bits), wt_bit
 //   rank       wt_target_range, wt_count_beaten, wt_write_rank, under the total order `better`
 //   top-k      wt_flush_at, flush (bitonic cut to k); the ballot append and the padded write-out stay written out in the two
@@ -136,6 +136,9 @@ __device__ __forceinline__ float wt_dot(const float* wr, const float* hs, const 
     }
     return s;
 }
+
+// the noisy-or term of a logit (sections 4e, 4i): -log(1 - sigma(s))
+__device__ __forceinline__ float wt_softplus(float s) { return fmaxf(s, 0.f) + log1pf(expf(-fabsf(s))); }
 
 // index of `key` in the strictly ascending keys [0, n), or -1: every lane calls it with the same arguments and gets the
 // same answer; the 64 lanes probe 64 keys per step

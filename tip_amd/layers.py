@@ -34,6 +34,7 @@ ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
+AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
@@ -849,6 +850,18 @@ class MultiInnerProductDecoder(nn.Module):
             w = w[relations]
         return ops.distmult_regimen_topk(z.detach(), w, reg_drugs, reg_ptr, k, aggregate, known)
 
+    def addon_burden(self, z, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate='noisy_or', weights=None, known=None,
+                     relations=None):
+        """Add-on burden (extension, `tipk_distmult_addon_burden`): sum_r weights[r] * P_r of every candidate of every
+        context of the CSR pairs (ctx_drugs, ctx_ptr) and (cand, cand_ptr) (cand_ptr None: one shared list), and the k
+        candidates of each query with the lowest burden -> (burden, best_burden [Q, k], best_pos int32 [Q, k]) as
+        `ops.distmult_addon_burden`; no autograd.  known and relations as `top_relations`; weights: one per candidate
+        relation."""
+        w = self.weight.detach()
+        if relations is not None:
+            w = w[relations]
+        return ops.distmult_addon_burden(z.detach(), w, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
+
 
 def normalize_regimens(regimens, n_drug, max_drugs):
     """Host normalisation of `TIP.regimen_side_effects`: a list of lists of drug ids, or a (drugs, ptr) pair of int tensors
@@ -885,6 +898,74 @@ def normalize_regimens(regimens, n_drug, max_drugs):
     ptr = torch.zeros(size.numel() + 1, dtype=torch.int64)
     ptr[1:] = torch.cumsum(size, 0)
     return (uniq % max(1, int(n_drug))).to(torch.int32), ptr
+
+
+def normalize_add_on_queries(regimens, candidates, replace, n_drug, max_context):
+    """Host normalisation of `TIP.add_on_risk` -> (ctx_drugs int32, ctx_ptr int64 [G + 1], cand int32, cand_ptr int64
+    [G + 1] or None) on the host.
+    regimens: as `normalize_regimens` (each sorted ascending and de-duplicated).  replace: None, or one drug id per regimen
+    (-1: none): that drug is taken out of the regimen, and what is left is the query's context; ValueError when it is not a
+    member.  A context may be empty (its burdens are NaN) and holds at most max_context drugs.
+    candidates: None = every drug, as the shared list 0 .. n_drug - 1 (cand_ptr None); a flat list or 1-d int tensor = one
+    list shared by all regimens (cand_ptr None); a list of G lists = one list per regimen (CSR).  Candidate lists keep
+    their order and their repeats.  For the two shared forms the G x C tasks are query-major: `burden.view(G, C)`.
+    ValueError for an id outside [0, n_drug), a context of more than max_context drugs, or lists that are not what the
+    above says."""
+    drugs, ptr = normalize_regimens(regimens, n_drug, max_context + (0 if replace is None else 1))
+    G = ptr.numel() - 1
+    if replace is not None:
+        try:
+            rep = torch.as_tensor(replace).detach().to('cpu')
+            bad = rep.dim() != 1 or rep.numel() != G or rep.dtype.is_floating_point or rep.dtype == torch.bool
+        except (TypeError, ValueError, RuntimeError):
+            bad = True
+        if bad:
+            raise ValueError('replace: one drug id per regimen (-1: none) expected, %d regimens' % G)
+        rep = rep.to(torch.int64)
+        owner = torch.repeat_interleave(torch.arange(G), ptr[1:] - ptr[:-1])
+        hit = drugs.to(torch.int64) == rep[owner]
+        found = torch.zeros(G, dtype=torch.int64).index_add_(0, owner, hit.to(torch.int64))
+        missing = (rep != -1) & (found == 0)
+        if bool(missing.any()):
+            g = int(torch.nonzero(missing)[0])
+            raise ValueError('replace: drug %d is not a member of regimen %d' % (int(rep[g]), g))
+        drugs, owner = drugs[~hit], owner[~hit]
+        size = torch.bincount(owner, minlength=G)
+        ptr = torch.zeros(G + 1, dtype=torch.int64)
+        ptr[1:] = torch.cumsum(size, 0)
+    size = ptr[1:] - ptr[:-1]
+    if G and int(size.max()) > max_context:
+        raise ValueError('a context of %d drugs: at most %d are scored' % (int(size.max()), max_context))
+    cand_ptr = None
+    if candidates is None:
+        cand = torch.arange(int(n_drug), dtype=torch.int64)
+    elif torch.is_tensor(candidates):
+        cand = candidates.detach().to('cpu')
+        if cand.dim() != 1 or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+            raise ValueError('candidates: a 1-d int tensor expected, got %s %s' % (cand.dtype, tuple(cand.shape)))
+        cand = cand.to(torch.int64)
+    else:
+        try:
+            items = list(candidates)
+            nested = len(items) > 0 and all(isinstance(c, (list, tuple)) or (torch.is_tensor(c) and c.dim() == 1)
+                                            for c in items)
+            if nested:
+                lists = [[int(x) for x in c] for c in items]
+            else:
+                cand = torch.tensor([int(x) for x in items], dtype=torch.int64)
+        except (TypeError, ValueError):
+            raise ValueError('candidates: None, a list of drug ids, or one list of drug ids per regimen expected') from None
+        if nested:
+            if len(lists) != G:
+                raise ValueError('candidates: %d lists for %d regimens' % (len(lists), G))
+            cand = torch.tensor([x for c in lists for x in c], dtype=torch.int64)
+            cand_ptr = torch.zeros(G + 1, dtype=torch.int64)
+            cand_ptr[1:] = torch.cumsum(torch.tensor([len(c) for c in lists], dtype=torch.int64), 0)
+    if cand.numel():
+        lo, hi = int(cand.min()), int(cand.max())
+        if lo < 0 or hi >= n_drug:
+            raise ValueError('candidate drug id out of range: [%d, %d] for %d drugs' % (lo, hi, n_drug))
+    return drugs.to(torch.int32), ptr, cand.to(torch.int32), cand_ptr
 
 
 def screen_queries(num_et, relations=None, drugs=None):
@@ -1006,6 +1087,18 @@ class NNDecoder(nn.Module):
             s1 = ops.matmul(p, w1.t())
             s2 = ops.matmul(q, w2.t())
         return ops.pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate, known)
+
+    def addon_burden(self, z, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate='noisy_or', weights=None, known=None,
+                     relations=None):
+        """Add-on burden (extension, `tipk_pair_table_addon_burden`) on the two tables `forward` forms; arguments and result
+        as `MultiInnerProductDecoder.addon_burden`.  The smaller drug id of a pair is the decoder's first argument."""
+        with torch.no_grad():
+            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
+            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
+            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
+            s1 = ops.matmul(p, w1.t())
+            s2 = ops.matmul(q, w2.t())
+        return ops.pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
 
     def objective(self, z, pos_index, neg_index, edge_type):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps) (src/layers.py:335-340 with this decoder as
@@ -1268,6 +1361,81 @@ class TIP(nn.Module):
             u = torch.where(have, lookup[(first + pi).clamp(min=0, max=lookup.numel() - 1)], none)
             v = torch.where(have, lookup[(first + pj).clamp(min=0, max=lookup.numel() - 1)], none)
         return RegimenSideEffects(score, idx, u, v)
+
+    def add_on_risk(self, regimens, candidates=None, k=10, replace=None, aggregate='noisy_or', weights=None, relations=None,
+                    exclude=None):
+        """Serving (extension): which CANDIDATE drug adds the least expected side-effect burden to every drug regimen
+        (`decoder.addon_burden`: one `tipk_distmult_addon_burden` / `tipk_pair_table_addon_burden` call on
+        `self.embeddings`, under no_grad; both decoder kinds).  The burden of candidate c for a patient on drugs S is
+        sum_r weights[r] * P_r, P_r the probability of side effect r from the pairs (c, s), s in S: 1 - prod (1 - sigma) under
+        'noisy_or', sigma(largest logit) under 'max' -- the expected weighted number of side effects c brings itself.
+        regimens: as `regimen_side_effects` (each sorted and de-duplicated).  replace: None, or one drug id per regimen
+        (-1: none): that drug is taken out of the context before scoring -- the substitution question; it may itself be a
+        candidate, and its burden is then the baseline to compare against; ValueError when it is not a member.
+        candidates: None = every drug (members of a regimen come back NaN); one list = shared by all regimens; a list of
+        lists = one list per regimen (`normalize_add_on_queries`).  weights: None (every side effect counts 1) or one
+        finite weight >= 0 per side effect -- per entry of `relations` when that is given --, e.g. a severity.
+        exclude / relations: as `regimen_side_effects` -- a recorded (pair, side effect) does not contribute.
+        -> AddOnRisk(burden float32 [T], candidate int64 [T], ptr int64 [G + 1], best_burden float32 [G, k], best_drug
+        int64 [G, k]) on the model's device: regimen g owns the tasks ptr[g]:ptr[g + 1] (flat CSR; for the two shared
+        candidate forms `burden.view(G, C)`), burden NaN where a candidate is not applicable (a member of the context, an
+        empty context, a NaN logit); best_*: the k candidates with the lowest burden, ascending, ties by position in the
+        regimen's candidate list, padded with (+inf, -1)."""
+        if self.shard is not None:
+            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the candidates '
+                                      'with the unsharded model (tip_amd.dist.gather_state_dict)')
+        if exclude not in ('train', 'all', None):
+            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        if aggregate not in ops.REGIMEN_AGGREGATES:
+            raise ValueError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+        k = int(k)
+        if k < 0:
+            raise ValueError('k must be >= 0, not %d' % k)
+        d = self.data
+        drugs, ptr, cand, cand_ptr = normalize_add_on_queries(regimens, candidates, replace, d.n_drug,
+                                                              ops.addon_max_context())
+        rel_host = None if relations is None else torch.as_tensor(relations).to('cpu', torch.int64).reshape(-1)
+        n_w = d.n_dd_et if rel_host is None else rel_host.numel()
+        if weights is not None:
+            try:
+                weights = torch.as_tensor(weights).detach().to(torch.float32)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError('weights: one number per side effect expected') from None
+            if weights.dim() != 1 or weights.numel() != n_w:
+                raise ValueError('weights: %d entries expected (one per side effect%s), got shape %s'
+                                 % (n_w, '' if rel_host is None else ' of `relations`', tuple(weights.shape)))
+            if not bool((torch.isfinite(weights) & (weights >= 0)).all()):
+                raise ValueError('weights must be finite and >= 0')
+        dev = self.embeddings.device
+        G, C = ptr.numel() - 1, cand.numel()
+        if cand_ptr is None:
+            cand_flat, task_ptr = cand.to(torch.int64).repeat(G), C * torch.arange(G + 1, dtype=torch.int64)
+        else:
+            cand_flat, task_ptr = cand.to(torch.int64), cand_ptr
+        both = torch.cat([ptr, task_ptr, drugs.to(torch.int64), cand_flat]).to(dev)            # one upload
+        ptr_d, task_ptr_d = both[:G + 1], both[G + 1:2 * G + 2]
+        drugs_d, cand_flat_d = both[2 * G + 2:2 * G + 2 + drugs.numel()], both[2 * G + 2 + drugs.numel():]
+        cand_d = cand_flat_d[:C] if cand_ptr is None else cand_flat_d
+        known = None
+        if exclude is not None:
+            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
+            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
+        rel = None if rel_host is None else rel_host.to(dev)
+        if rel is not None and known is not None:
+            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        with torch.no_grad():
+            w_d = None if weights is None else weights.to(dev)
+            burden, best_b, best_p = self.decoder.addon_burden(self.embeddings, drugs_d, ptr_d, cand_d,
+                                                               None if cand_ptr is None else task_ptr_d, k, aggregate, w_d,
+                                                               known, rel)
+            if k == 0:
+                best_b = torch.empty((G, 0), dtype=torch.float32, device=dev)
+                best_drug = torch.empty((G, 0), dtype=torch.int64, device=dev)
+            else:
+                lookup = cand_flat_d if cand_flat_d.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+                at = (task_ptr_d[:-1, None] + best_p).clamp(min=0, max=lookup.numel() - 1)
+                best_drug = torch.where(best_p >= 0, lookup[at], torch.full_like(at, -1))
+        return AddOnRisk(burden.reshape(-1), cand_flat_d, task_ptr_d, best_b, best_drug)
 
     def rank_side_effects(self, triples=None, filter='all', ks=(1, 3, 10), relations=None):
         """Evaluation of what `side_effects` serves (extension): where each given (drug, drug, side effect) triple lands

@@ -1502,6 +1502,85 @@ def pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate='max', know
     return _regimen_result(out_s, out_r, out_p)
 
 
+def addon_max_context():
+    """The longest context (drugs a patient already takes) the add-on burden entries score (include/tipk.h section 4i)."""
+    return int(lib().tipk_addon_max_context())
+
+
+def _addon_args(ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known, n_rel, dev):
+    if aggregate not in REGIMEN_AGGREGATES:
+        raise _lib.TipkError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+    ctx_drugs, ctx_ptr, cand = torch.as_tensor(ctx_drugs), torch.as_tensor(ctx_ptr), torch.as_tensor(cand)
+    cand_ptr = None if cand_ptr is None else torch.as_tensor(cand_ptr)
+    require_device(ctx_drugs, ctx_ptr, cand, cand_ptr, weights)
+    ints = (ctx_drugs, ctx_ptr, cand) + (() if cand_ptr is None else (cand_ptr,))
+    if any(t.dim() != 1 or t.dtype.is_floating_point for t in ints) or ctx_ptr.numel() < 1:
+        raise _lib.TipkError('add-on queries: 1-d int tensors ctx_drugs, ctx_ptr [Q + 1], cand and cand_ptr [Q + 1] (or None) '
+                             'expected, got %s' % ', '.join('%s %s' % (t.dtype, tuple(t.shape)) for t in ints))
+    n_q = ctx_ptr.numel() - 1
+    if cand_ptr is not None and cand_ptr.numel() != n_q + 1:
+        raise _lib.TipkError('add-on queries: cand_ptr has %d entries for %d queries' % (cand_ptr.numel(), n_q))
+    if weights is not None:
+        weights = _f32c(weights).contiguous()
+        if weights.dim() != 1 or weights.numel() != n_rel:
+            raise _lib.TipkError('weights: a float tensor [%d] expected, got %s' % (n_rel, tuple(weights.shape)))
+    drugs, cptr = ctx_drugs.to(torch.int32).contiguous(), ctx_ptr.to(torch.int64).contiguous()
+    cd = cand.to(torch.int32).contiguous()
+    dptr = None if cand_ptr is None else cand_ptr.to(torch.int64).contiguous()
+    n_cand, k = cd.numel(), int(k)
+    if drugs.numel() == 0:                                               # an empty tensor has no address
+        drugs = torch.zeros(1, dtype=torch.int32, device=dev)
+    out_b = torch.empty((n_cand,) if dptr is not None else (n_q, n_cand), dtype=torch.float32, device=dev)
+    best_b = best_p = None
+    if k > 0:                                                            # (no launch without candidates: the rows are padding)
+        best_b = torch.full((n_q, k), float('inf'), dtype=torch.float32, device=dev) if n_cand == 0 \
+            else torch.empty((n_q, k), dtype=torch.float32, device=dev)
+        best_p = torch.full((n_q, k), -1, dtype=torch.int32, device=dev) if n_cand == 0 \
+            else torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    return drugs, cptr, n_q, cd, dptr, n_cand, weights, k, REGIMEN_AGGREGATES[aggregate], _known_lists(known), out_b, \
+        best_b, best_p
+
+
+def distmult_addon_burden(z, rel_w, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights=None, known=None):
+    """The burden every candidate drug adds to every context (a patient's drug list) by the DistMult logits of its pairs with
+    the context, and the k candidates of each query with the lowest burden (include/tipk.h section 4i).
+
+    ctx_drugs int [n_entries], ctx_ptr int [Q + 1]: context q is ctx_drugs[ctx_ptr[q]:ctx_ptr[q + 1]].  cand int, cand_ptr
+    int [Q + 1]: query q owns cand[cand_ptr[q]:cand_ptr[q + 1]]; cand_ptr None: the one list `cand` serves every query.
+    aggregate: 'noisy_or' (P_r = 1 - prod (1 - sigma(logit)) over the context) or 'max' (P_r = sigma(largest logit));
+    weights: None (all 1) or float [n_rel], finite and >= 0; known: None or the pair-major lists of
+    `known_relations_by_pair`: a known triple contributes nothing.  All on the device.
+    -> (burden float32 [n_cand] (cand_ptr given) or [Q, n_cand] (shared list), best_burden float32 [Q, k], best_pos int32
+    [Q, k]): burden = sum_r weights[r] * P_r, NaN where the task is not applicable (candidate out of range or in its
+    context, a context of 0 or more than `addon_max_context()` drugs or with an id out of range, a NaN logit); best_*: the
+    k lowest burdens of each query, ascending, ties by position in the query's list, padded with (+inf, -1); both None for
+    k = 0.  Does not synchronise."""
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_addon_burden')
+    dev = z.device
+    n, dim, n_rel = z.shape[0], z.shape[1], rel_w.shape[0]
+    drugs, cptr, n_q, cd, dptr, n_cand, wts, k, agg, (keys, kptr, krel, n_keys), out_b, best_b, best_p = _addon_args(
+        ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known, n_rel, dev)
+    check(lib().tipk_distmult_addon_burden(ptr(z), n, dim, ptr(rel_w), n_rel, ptr(drugs), ptr(cptr), n_q, ptr(cd), ptr(dptr),
+                                           n_cand, ptr(wts), ptr(keys), ptr(kptr), ptr(krel), n_keys, agg, k, ptr(out_b),
+                                           ptr(best_b), ptr(best_p), None, stream_ptr(dev)), 'tipk_distmult_addon_burden')
+    return out_b, best_b, best_p
+
+
+def pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights=None, known=None):
+    """`distmult_addon_burden` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for
+    both): the logit of candidate c with context drug s under r is s1[min(c, s), r] + s2[max(c, s), r]."""
+    s1, s2 = _table_pair(s1, s2, 'pair_table_addon_burden')
+    dev = s1.device
+    n, n_rel = s1.shape[0], s1.shape[1]
+    drugs, cptr, n_q, cd, dptr, n_cand, wts, k, agg, (keys, kptr, krel, n_keys), out_b, best_b, best_p = _addon_args(
+        ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known, n_rel, dev)
+    check(lib().tipk_pair_table_addon_burden(ptr(s1), ptr(s2), s1.stride(0), n, n_rel, ptr(drugs), ptr(cptr), n_q, ptr(cd),
+                                             ptr(dptr), n_cand, ptr(wts), ptr(keys), ptr(kptr), ptr(krel), n_keys, agg, k,
+                                             ptr(out_b), ptr(best_b), ptr(best_p), stream_ptr(dev)),
+          'tipk_pair_table_addon_burden')
+    return out_b, best_b, best_p
+
+
 _DET_WS = {}
 
 
