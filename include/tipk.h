@@ -271,12 +271,18 @@ int tipk_rel_gather(int backward, const float* table, int64_t ld_table, int64_t 
  *     Epilogue of a finished row (rows without edges included): relu?(out_scale[row] * sum + bias[col]); out_scale /
  *     bias nullable.  max_split: the largest number of column blocks the caller accepts (every block walks all the ids
  *     again): 4 on the D-D passes, 16 for the P-P graph (which also admits 2-column blocks).
+ *     STREAMED OUTPUT: the launches whose rows are write-once pair-form output -- tipk_stream_gather with kind = 1 (pair
+ *     cells), tipk_stream_gather_two, and tipk_stream_gather_parts / _parts_two of section 2e -- write every row (zero rows
+ *     included) with 16-byte stores that do not keep the line in the writing XCD's L2, where a lane group covers whole
+ *     128-byte lines (column blocks of 32 columns and more).  Same values, same rows; but a kernel that re-reads those rows
+ *     right behind the launch finds none of them L2-resident -- they come from the Infinity Cache / HBM.
  */
 /* column blocks of the launch (grid = n_wg x blocks); 0 = the table does not fit in LDS */
 int tipk_stream_gather_supported(int64_t n_table, int d, int max_split);
 /* two tables of the same shape on ONE plan in one launch (no zero rows, no scaling, no epilogue): out0 <- table0, out1 <- table1;
  * the pair cells of both R-GCN layers of an encoder (they share the graph; the cells depend on the parameters only).  One column
- * block only (tipk_stream_gather_supported(n_table, d, 1) == 1), d in {16, 32, 64}. */
+ * block only (tipk_stream_gather_supported(n_table, d, 1) == 1), d in {16, 32, 64}.  out0 / out1 bypass L2 residency for d >= 32
+ * (STREAMED OUTPUT above). */
 int tipk_stream_gather_two(const float* table0, const float* table1, int64_t ld_table, int64_t n_table, int d, int64_t n_wg,
                            const int32_t* wave_ptr, const uint32_t* cells, const uint16_t* ids, int idx_unit,
                            float* out0, float* out1, int64_t ld_out, tipk_stream_t stream);
@@ -284,7 +290,7 @@ int tipk_stream_gather_piece(void);
 int tipk_stream_gather(const float* table, int64_t ld_table, int64_t n_table, int d, int64_t n_wg,
                         const int32_t* wave_ptr, const uint32_t* cells, const uint16_t* ids, int idx_unit,
                         const int32_t* zero_ptr, const int32_t* zero_rows, const float* row_scale,
-                        float* out, int64_t ld_out, int kind /* 0 | 1: names the kernel instance in profiles, nothing else */,
+                        float* out, int64_t ld_out, int kind /* 0 | 1: names the kernel instance in profiles; 1 (pair cells): `out` bypasses L2 residency (STREAMED OUTPUT above) */,
                         int max_split, const float* out_scale, const float* bias, int relu, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
@@ -515,6 +521,8 @@ int tipk_rgcn_node_products(const float* dyc, int64_t n_rows, int d, const int32
  *     from the partition's first, output rows = p * n_rel + r (out [n_parts * n_rel][d], added over p in order by
  *     tipk_sum_slabs(_group)).  d = 32 (one 128-byte row per pair); every partition is staged part_len rows long.  The plan is
  *     walked with 8 lanes per row (build it for lanes = 8, whatever column split the att table of the forward cells needs).
+ *     The slabs `out` (out0 / out1 of tipk_stream_gather_parts_two) bypass L2 residency (1d, STREAMED OUTPUT); pg and dxb of
+ *     tipk_rgcn_pair_grads are plain write-back stores.
  */
 int tipk_rgcn_pair_grads_supported(int n_bases, int d);
 int tipk_rgcn_pair_grads(const float* cells, int64_t n_lines, const float* xb, const float* g, int64_t ld_g,

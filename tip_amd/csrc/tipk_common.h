@@ -50,5 +50,18 @@ int tipk_option(int id);
 #ifdef __HIPCC__
 __device__ __forceinline__ float4 tipk_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void tipk_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// 16-byte store that does NOT stay in the XCD's L2 (`sc1`, MI355X_MICROARCH.md "stores of each flavour"): for write-once
+// output nobody on this XCD reads back -- the 10 GB stream of config 5's transposed pass (kept in L2 it evicts the 5 MB
+// table every gathered row comes from), and the pair cells and d att slabs of the stream gathers, which left dirty in
+// the write-back L2 drain at the END of their launch, in front of the dependent one.  Written through, scattered
+// 128-byte rows leave at well under 1 TB/s: only for a launch whose other work lasts longer than that (DESIGN.md
+// section 5, profiles/store_drain.md).  16 bytes per lane only: a dword `sc1` store is one fabric write each, ~6x the
+// time per byte.  The compiler pads nothing behind an asm statement: the `s_nop 1` keeps the next VALU write of the data
+// registers off a store that is still reading them.
+typedef float tipk_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st4_stream(float* p, float4 v) {
+    tipk_f4 q = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(q) : "memory");
+}
 __device__ __forceinline__ int tipk_lane() { return threadIdx.x & (TIPK_WAVE - 1); }
 #endif

@@ -635,15 +635,6 @@ extern "C" int tipk_gather_sum_finalize(const float* partial, const int32_t* row
 
 namespace {
 
-// 16-byte store that does NOT stay in the XCD's L2 (`sc1`, MI355X_MICROARCH.md "stores of each flavour"):
-// the output of the transposed pass is a 10 GB write-once stream in config 5; kept in L2 it evicts the
-// 5 MB table every gathered row comes from.
-typedef float tipk_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st4_stream(float* p, float4 v) {
-    tipk_f4 q = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(q) : "memory");
-}
-
 // ---------------------------------------------------------------------------------------------
 // CSR rows: out[r] = sum_{e in [row_ptr[r], row_ptr[r+1])} table[row_id[e]] for EVERY row r, rows short
 // (include/tipk.h section 1c).  The transposed D-D pass of a large graph writes R*N rows of ~2.5 edges

@@ -25,7 +25,9 @@
 //     bases] result leaves as 16 stores of two full 128-byte lines each.  Round 5, first version: the same waves did both
 //     products, 32 MFMAs + 16 stores per tile -- a hub node's wave walked 5 such tiles in a row while most of the chip had
 //     finished (debug decomposition, tools/bench_pair_grads.py: 21.8 us, 11.7 with at most one tile per wave); the tiles
-//     of this half are independent, so they are dealt one per wave over the whole chip.
+//     of this half are independent, so they are dealt one per wave over the whole chip.  These rows stay PLAIN stores
+//     (profiles/store_drain.md): turned through LDS into 16-byte rows they cost the same, and as streaming stores
+//     (tipk_common.h st4_stream) the launch took 29 / 32 us instead of 9 / 15 -- it is far too short to write 18 MB through.
 #include <stdlib.h>
 #include "tipk_common.h"
 

@@ -99,8 +99,12 @@ template <> struct RsVec<2> {
     static __device__ __forceinline__ void relu(T& a) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); }
 };
 
-// KIND 0 / 1 only name the launch in profiles (0: rows = (relation, node), the transposed pass; 1: rows = node pairs);
-// KIND 2: the table is per workgroup -- a partition of the symmetrised pair gradients (tipk_stream_gather_parts)
+// KIND 0: rows = (relation, node), the transposed pass and the P-P graph; KIND 1: rows = node pairs (the pair cells);
+// KIND 2: the table is per workgroup -- a partition of the symmetrised pair gradients (tipk_stream_gather_parts).
+// The rows of KIND 1 and 2 are 16-19 MB of write-once output per step that no workgroup of the launch reads back and no
+// consumer is placed to find in the producer's L2: where a lane group writes whole 128-byte lines (L >= 8, 16 bytes per
+// lane) they leave through st4_stream while the band loop still runs, not as dirty lines that drain behind the launch
+// (19-23 us of band loop per launch cover the write-through; measured -1.4 us each, profiles/store_drain.md).
 template <int L, bool UNIT, int KIND, int VW = 4>
 __global__ __launch_bounds__(1024) void stream_gather_kernel(RsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tab[];        // [n_nodes + 1][dc], last row = 0 (the pad id's row)
@@ -207,11 +211,13 @@ __global__ __launch_bounds__(1024) void stream_gather_kernel(RsArgs a) {
     // a finished row: relu?(out_scale[row] * sum + bias) (all optional), one store
     vec_t bias_v = V::zero();
     if (a.bias) bias_v = *reinterpret_cast<const vec_t*>(a.bias + col0 + c0);
+    constexpr bool STREAMED = KIND != 0 && VW == 4 && L >= 8;
     auto finish = [&](int64_t row, vec_t v) {
         if (a.out_scale) V::scale(v, a.out_scale[row]);
         V::add(v, bias_v);
         if (a.relu) V::relu(v);
-        *reinterpret_cast<vec_t*>(out + row * a.ld_out + c0) = v;
+        if constexpr (STREAMED) st4_stream(out + row * a.ld_out + c0, v);
+        else *reinterpret_cast<vec_t*>(out + row * a.ld_out + c0) = v;
     };
     // walk band `band` out of (cw, iw) and request band + RS_DEPTH into (nw, niw)
     auto walk = [&](int band, const uint32_t& cw, const uint4 (&iw)[RS_PIECE], uint32_t& nw, uint4 (&niw)[RS_PIECE]) {
