@@ -83,6 +83,25 @@ def test_screen_routes_identical_and_repeatable():
     check_screen(z, w, q, k, a, known)
 
 
+def test_screen_empty_known_lists_drop_nothing():
+    """A known list without any key is `known=None`, bit for bit (an empty tensor has no address to hand over); a list that
+    is empty for relation 0 only leaves the relation-0 rows as they are.  The smallest shape with both query kinds."""
+    n, dim, n_rel, k = 5, 4, 2, 3
+    g = torch.Generator().manual_seed(5)
+    z, w = torch.randn(n, dim, generator=g).to(DEV), torch.randn(n_rel, dim, generator=g).to(DEV)
+    q = torch.tensor([[0, -1], [1, 2]])
+    plain = ops.distmult_screen(z, w, q, k, known=None)
+    empty = (torch.empty(0, dtype=torch.int64, device=DEV), torch.zeros(n_rel + 1, dtype=torch.int64, device=DEV))
+    for x, y, name in zip(ops.distmult_screen(z, w, q, k, known=empty), plain, ('score', 'u', 'v')):
+        assert torch.equal(x, y), 'empty list vs None: ' + name
+    partner = int(plain[2][1, 0])                                         # drug 2's best partner under relation 1
+    half = (torch.tensor([2 * n + partner], device=DEV), torch.tensor([0, 0, 1], device=DEV))
+    got = ops.distmult_screen(z, w, q, k, known=half)
+    for x, y, name in zip(got, plain, ('score', 'u', 'v')):
+        assert torch.equal(x[0], y[0]), 'relation 0 has no keys: ' + name
+    assert partner not in got[2][1].tolist()                              # ... and relation 1's one key was read
+
+
 # ------------------------------------------------------------------ TIP.screen
 def _known_of(idx, rng, n, extra=None):
     """(keys, ptr) on the device from edge lists grouped by relation (optionally merged with a second one)."""

@@ -82,6 +82,30 @@ def test_ops_refuse_cpu_tensors():
         ops.distmult_screen(torch.ones(5, 4), torch.ones(2, 4), torch.tensor([[0, -1]]), 3)
 
 
+class _ClaimsDevice(torch.Tensor):
+    """A host tensor that says it is on the device (and so do the tensors derived from it): it takes a call past the
+    operand checks, so that the refusal of another argument can be seen without a device."""
+    is_cuda = property(lambda self: True)
+
+
+def test_ops_refuse_cpu_known_lists():
+    """The relation-major known lists of the screen and of the partner rank are refused on the host like every other
+    operand -- here they are the ONLY host tensors the call can see, and the refusal comes before any launch."""
+    from tip_amd import ops
+
+    def on(*shape, **kw):
+        return torch.ones(*shape, **kw).as_subclass(_ClaimsDevice)
+
+    z, w = on(5, 4), on(2, 4)
+    keys, kptr = torch.tensor([7]), torch.tensor([0, 0, 1])
+    for known in ((keys, kptr), (keys.as_subclass(_ClaimsDevice), kptr), (keys, kptr.as_subclass(_ClaimsDevice))):
+        with pytest.raises(_lib.TipkError, match='device'):
+            ops.distmult_screen(z, w, torch.tensor([[0, -1]]), 3, known=known)
+        ints = [on(n, dtype=torch.int64) for n in (2, 2, 3, 2)]             # q_rel, q_drug, tgt_ptr, tgt_node
+        with pytest.raises(_lib.TipkError, match='device'):
+            ops.distmult_partner_rank(z, w, *ints, known=known)
+
+
 def test_tip_screen_refusals():
     from tip_amd.layers import TIP
     with pytest.raises(NotImplementedError, match='NN decoder'):

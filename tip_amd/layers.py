@@ -801,6 +801,11 @@ class MultiInnerProductDecoder(nn.Module):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps), fused (K9+K10)."""
         return ops.distmult_objective(z, self.weight, pos_index, neg_index, edge_type)
 
+    def _rows(self, relations=None):
+        """The weight rows the queries rank with, detached: all, or those of the candidate ids `relations`."""
+        w = self.weight.detach()
+        return w if relations is None else w[relations]
+
     def screen(self, z, k, relations=None, drugs=None, known=None):
         """Screen (extension, `tipk_distmult_screen`): the k best candidates per query by LOGIT -> (logits [Q, k],
         u int32 [Q, k], v int32 [Q, k]); no autograd.  relations: ids (None = all num_et).  drugs None: one relation query
@@ -814,20 +819,14 @@ class MultiInnerProductDecoder(nn.Module):
         """Pair top-k (extension, `tipk_distmult_pair_topk`): the k best relations of every pair of `pairs` [2, P] by LOGIT ->
         (logits [P, k], relation int32 [P, k]); no autograd.  known: (pair_keys, pair_ptr, rel) to drop
         (`ops.known_relations_by_pair`).  relations: candidate ids (None = all); the returned ids are positions in it."""
-        w = self.weight.detach()
-        if relations is not None:
-            w = w[relations]
-        return ops.distmult_pair_topk(z.detach(), w, pairs, k, known)
+        return ops.distmult_pair_topk(z.detach(), self._rows(relations), pairs, k, known)
 
     def relation_ranks(self, z, pairs, tgt_ptr, tgt_rel, known=None, relations=None):
         """Pair rank (extension, `tipk_distmult_pair_rank`): the rank of every target relation among the relations of its
         pair by LOGIT -> (rank int32 [T], logit [T]), rank 0 = not ranked; no autograd.  pairs [2, P], tgt_ptr [P + 1], tgt_rel
         [T]: `ops.targets_by_pair`.  known and relations as `top_relations`: with a candidate subset, tgt_rel and the known
         lists (`ops.restrict_known_relations`) hold positions in `relations`."""
-        w = self.weight.detach()
-        if relations is not None:
-            w = w[relations]
-        return ops.distmult_pair_rank(z.detach(), w, pairs, tgt_ptr, tgt_rel, known)
+        return ops.distmult_pair_rank(z.detach(), self._rows(relations), pairs, tgt_ptr, tgt_rel, known)
 
     def partner_ranks(self, z, q_rel, q_drug, tgt_ptr, tgt_node, known=None):
         """Partner rank (extension, `tipk_distmult_partner_rank`): the rank of every target drug among the partners of its
@@ -845,10 +844,7 @@ class MultiInnerProductDecoder(nn.Module):
         """Regimen top-k (extension, `tipk_distmult_regimen_topk`): the k best relations of every drug list of the CSR pair
         (reg_drugs, reg_ptr) by the aggregate of its pairs' LOGITS -> (score [G, k], relation int32 [G, k], pair_i, pair_j
         int32 [G, k]: list positions of the driving pair); no autograd.  known and relations as `top_relations`."""
-        w = self.weight.detach()
-        if relations is not None:
-            w = w[relations]
-        return ops.distmult_regimen_topk(z.detach(), w, reg_drugs, reg_ptr, k, aggregate, known)
+        return ops.distmult_regimen_topk(z.detach(), self._rows(relations), reg_drugs, reg_ptr, k, aggregate, known)
 
     def addon_burden(self, z, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate='noisy_or', weights=None, known=None,
                      relations=None):
@@ -857,10 +853,7 @@ class MultiInnerProductDecoder(nn.Module):
         candidates of each query with the lowest burden -> (burden, best_burden [Q, k], best_pos int32 [Q, k]) as
         `ops.distmult_addon_burden`; no autograd.  known and relations as `top_relations`; weights: one per candidate
         relation."""
-        w = self.weight.detach()
-        if relations is not None:
-            w = w[relations]
-        return ops.distmult_addon_burden(z.detach(), w, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
+        return ops.distmult_addon_burden(z.detach(), self._rows(relations), ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
 
 
 def normalize_regimens(regimens, n_drug, max_drugs):
@@ -1036,11 +1029,18 @@ class NNDecoder(nn.Module):
         self.w1_l2.data.normal_(std=1 / np.sqrt(self.l1_dim))
         self.w2_l2.data.normal_(std=1 / np.sqrt(self.l1_dim))
 
-    def forward(self, z, edge_index, edge_type):
+    def _tables(self, z, relations=None, relation_major=False):
+        """The two score tables: every (node, relation) dot product, node-major [N, R] as `forward` reads them or
+        relation-major [R, N] as `objective` does.  relations: candidate ids (None = all), rows of w*_l2."""
+        w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
         p = torch.relu(ops.matmul(z, self.w1_l1))
         q = torch.relu(ops.matmul(z, self.w2_l1))
-        s1 = ops.matmul(p, self.w1_l2.t())                       # [N, R]: every (node, relation) dot product
-        s2 = ops.matmul(q, self.w2_l2.t())
+        if relation_major:
+            return ops.matmul(w1, p.t()), ops.matmul(w2, q.t())
+        return ops.matmul(p, w1.t()), ops.matmul(q, w2.t())
+
+    def forward(self, z, edge_index, edge_type):
+        s1, s2 = self._tables(z)
         return ops.pair_table_score(s1, s2, edge_index, edge_type, sigmoid=True)
 
     def top_relations(self, z, pairs, k, known=None, relations=None):
@@ -1048,22 +1048,14 @@ class NNDecoder(nn.Module):
         int32 [P, k]); no autograd.  relations: candidate ids (None = all): columns of the tables, i.e. rows of w*_l2; the
         returned ids are positions in it."""
         with torch.no_grad():
-            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
-            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
-            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
-            s1 = ops.matmul(p, w1.t())
-            s2 = ops.matmul(q, w2.t())
+            s1, s2 = self._tables(z.detach(), relations)
         return ops.pair_table_pair_topk(s1, s2, pairs, k, known)
 
     def relation_ranks(self, z, pairs, tgt_ptr, tgt_rel, known=None, relations=None):
         """Pair rank (extension, `tipk_pair_table_pair_rank`) on the two tables `forward` forms; arguments and result as
         `MultiInnerProductDecoder.relation_ranks`.  The pair's first drug is the decoder's first argument."""
         with torch.no_grad():
-            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
-            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
-            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
-            s1 = ops.matmul(p, w1.t())
-            s2 = ops.matmul(q, w2.t())
+            s1, s2 = self._tables(z.detach(), relations)
         return ops.pair_table_pair_rank(s1, s2, pairs, tgt_ptr, tgt_rel, known)
 
     def partner_ranks(self, z, q_rel, q_drug, tgt_ptr, tgt_node, known=None):
@@ -1071,21 +1063,14 @@ class NNDecoder(nn.Module):
         query's candidates are one contiguous row); arguments and result as `MultiInnerProductDecoder.partner_ranks`.  The
         queried drug is the decoder's first argument, the ranked partner its second."""
         with torch.no_grad():
-            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
-            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
-            s1t = ops.matmul(self.w1_l2, p.t())                  # [R, N]
-            s2t = ops.matmul(self.w2_l2, q.t())
+            s1t, s2t = self._tables(z.detach(), relation_major=True)
         return ops.pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known)
 
     def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
         """Regimen top-k (extension, `tipk_pair_table_regimen_topk`) on the two tables `forward` forms; arguments and result
         as `MultiInnerProductDecoder.top_regimen_relations`.  The earlier list position is the decoder's first argument."""
         with torch.no_grad():
-            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
-            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
-            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
-            s1 = ops.matmul(p, w1.t())
-            s2 = ops.matmul(q, w2.t())
+            s1, s2 = self._tables(z.detach(), relations)
         return ops.pair_table_regimen_topk(s1, s2, reg_drugs, reg_ptr, k, aggregate, known)
 
     def addon_burden(self, z, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate='noisy_or', weights=None, known=None,
@@ -1093,11 +1078,7 @@ class NNDecoder(nn.Module):
         """Add-on burden (extension, `tipk_pair_table_addon_burden`) on the two tables `forward` forms; arguments and result
         as `MultiInnerProductDecoder.addon_burden`.  The smaller drug id of a pair is the decoder's first argument."""
         with torch.no_grad():
-            w1, w2 = (self.w1_l2, self.w2_l2) if relations is None else (self.w1_l2[relations], self.w2_l2[relations])
-            p = torch.relu(ops.matmul(z.detach(), self.w1_l1))
-            q = torch.relu(ops.matmul(z.detach(), self.w2_l1))
-            s1 = ops.matmul(p, w1.t())
-            s2 = ops.matmul(q, w2.t())
+            s1, s2 = self._tables(z.detach(), relations)
         return ops.pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
 
     def objective(self, z, pos_index, neg_index, edge_type):
@@ -1117,6 +1098,80 @@ class NNDecoder(nn.Module):
         s1t = ops.matmul(self.w1_l2, p.t())                      # [R, N]
         s2t = ops.matmul(self.w2_l2, q.t())
         return ops.pair_table_objective(s1t, s2t, pos_index, neg_index, edge_type)
+
+
+# ---------------------------------------------------------------------------------------------
+# The steps the TIP queries share.  Functions of the values they need: the query methods also run unbound, on a bare
+# namespace, up to their last refusal.
+# ---------------------------------------------------------------------------------------------
+def _refuse_sharded(shard, what):
+    """NotImplementedError for a relation-sharded model: the queries need every decoder row.  what: the noun the message
+    ranks ('side effects', 'candidates', 'partners', 'pairs'), or 'screen'."""
+    if shard is not None:
+        how = 'screen the' if what == 'screen' else 'rank the %s with the' % what
+        raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; %s unsharded model '
+                                  '(tip_amd.dist.gather_state_dict)' % how)
+
+
+def _check_known_mode(name, mode):
+    """ValueError unless the `exclude` / `filter` argument `name` is 'train', 'all' or None."""
+    if mode not in ('train', 'all', None):
+        raise ValueError("%s must be 'train', 'all' or None, not %r" % (name, mode))
+
+
+def _relation_ids(relations, dev):
+    """The candidate side-effect ids `relations` as an int64 tensor on `dev`, or None (= all)."""
+    return None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
+
+
+def _pair_known(d, mode, rel):
+    """The pair-major known lists (`ops.known_relations_by_pair`) an `exclude` / `filter` mode drops: the training side
+    effects of every pair ('train'), train and test ones merged ('all'), or None (None).  rel: the candidate ids on the
+    lists' device or None -- the lists hold global ids, so with candidates they keep the candidates' entries only,
+    renumbered to positions in `rel` (`ops.restrict_known_relations`)."""
+    if mode is None:
+        return None
+    extra = (d.dd_test_idx, d.dd_test_range) if mode == 'all' else None
+    known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
+    return known if rel is None else ops.restrict_known_relations(known, rel, d.n_dd_et)
+
+
+def _checked_triples(triples, d, dev):
+    """The triples a rank evaluation ranks -> (edge_index [2, T], edge_type int64 [T]) on `dev`: the held-out set of `d` for
+    None, else the given (edge_index, edge_type), refused with ValueError unless int tensors of these shapes with ids in
+    range."""
+    idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
+    idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
+    if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
+            or idx.dtype.is_floating_point or et.dtype.is_floating_point:
+        raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
+                         % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
+    if et.numel():
+        lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
+        if lo < 0 or hi >= d.n_drug:
+            raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
+        if rlo < 0 or rhi >= d.n_dd_et:
+            raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
+    return idx, et.to(torch.int64)
+
+
+def _rank_result(order, r, s, et, n_rel, ks):
+    """The RankReport of a rank entry's (rank r, logit s) in grouped order: both scattered back through `order` (the
+    `ops.targets_by_*` permutation) to the triples' order, and `utils.rank_report` of the ranks by side effect `et`."""
+    rank = torch.empty_like(r, dtype=torch.int64)
+    rank[order] = r.to(torch.int64)
+    logit = torch.empty_like(s)
+    logit[order] = s
+    return RankReport(rank, logit, **rank_report(rank, et, n_rel, ks))
+
+
+def _ids_at(pos, lookup, first=None):
+    """Positions a kernel returned -> the int64 ids `lookup` holds there; padding (pos < 0) stays -1.  first: the offset of
+    each row's list in `lookup` (CSR), for positions that count inside a row's list."""
+    at = pos.to(torch.int64) if first is None else first + pos
+    if lookup.numel() == 0:                                              # only padding can point into an empty list
+        lookup = lookup.new_zeros(1)
+    return torch.where(pos >= 0, lookup[at.clamp(min=0, max=lookup.numel() - 1)], torch.full_like(at, -1))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1288,11 +1343,8 @@ class TIP(nn.Module):
         side-effect ids (None = all); the returned ids are global.  Ranking is on the logit, ties by ascending position in
         `relations`; sigmoid = True applies sigma afterwards (padding: score sigma(-inf) = 0, relation -1).
         -> SideEffects(score [P, k], relation int64 [P, k]) on the model's device."""
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
-                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if exclude not in ('train', 'all', None):
-            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        _refuse_sharded(self.shard, 'side effects')
+        _check_known_mode('exclude', exclude)
         d = self.data
         dev = self.embeddings.device
         pairs = torch.as_tensor(pairs).to(dev)
@@ -1302,20 +1354,12 @@ class TIP(nn.Module):
             lo, hi = torch.stack([pairs.min(), pairs.max()]).tolist()
             if lo < 0 or hi >= d.n_drug:
                 raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
-        known = None
-        if exclude is not None:
-            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
-            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
-        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
-        if rel is not None and known is not None:
-            # the lists hold global ids: keep the candidates' entries and renumber them to positions in `relations`
-            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        rel = _relation_ids(relations, dev)
+        known = _pair_known(d, exclude, rel)
         with torch.no_grad():
             logit, idx = self.decoder.top_relations(self.embeddings, pairs, k, known, rel)
             score = torch.sigmoid(logit) if sigmoid else logit
-            idx = idx.to(torch.int64)
-            if rel is not None:
-                idx = torch.where(idx >= 0, rel[idx.clamp(min=0)], idx)
+            idx = idx.to(torch.int64) if rel is None else _ids_at(idx, rel)
         return SideEffects(score, idx)
 
     def regimen_side_effects(self, regimens, k=10, aggregate='noisy_or', exclude=None, relations=None, probability=True):
@@ -1329,11 +1373,8 @@ class TIP(nn.Module):
         `side_effects` -- a recorded (pair, side effect) does not contribute.  probability = True maps the score after the
         kernel: sigmoid(A) for 'max', -expm1(-A) for 'noisy_or' (padding: score 0, relation -1, u = v = -1).
         -> RegimenSideEffects(score [G, k], relation int64 [G, k], u int64 [G, k], v int64 [G, k]) on the model's device."""
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
-                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if exclude not in ('train', 'all', None):
-            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        _refuse_sharded(self.shard, 'side effects')
+        _check_known_mode('exclude', exclude)
         if aggregate not in ops.REGIMEN_AGGREGATES:
             raise ValueError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
         d = self.data
@@ -1341,25 +1382,15 @@ class TIP(nn.Module):
         dev = self.embeddings.device
         both = torch.cat([ptr, drugs.to(torch.int64)]).to(dev)          # one upload
         ptr_d, drugs_d = both[:ptr.numel()], both[ptr.numel():]
-        known = None
-        if exclude is not None:
-            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
-            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
-        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
-        if rel is not None and known is not None:
-            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        rel = _relation_ids(relations, dev)
+        known = _pair_known(d, exclude, rel)
         with torch.no_grad():
             score, idx, pi, pj = self.decoder.top_regimen_relations(self.embeddings, drugs_d, ptr_d, k, aggregate, known, rel)
             if probability:
                 score = torch.sigmoid(score) if aggregate == 'max' \
                     else torch.where(idx >= 0, -torch.expm1(-score), torch.zeros_like(score))   # (padding: -expm1(inf))
-            idx, have = idx.to(torch.int64), idx >= 0
-            if rel is not None:
-                idx = torch.where(have, rel[idx.clamp(min=0)], idx)
-            lookup = drugs_d if drugs_d.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
-            first, none = ptr_d[:-1, None], torch.full_like(idx, -1)
-            u = torch.where(have, lookup[(first + pi).clamp(min=0, max=lookup.numel() - 1)], none)
-            v = torch.where(have, lookup[(first + pj).clamp(min=0, max=lookup.numel() - 1)], none)
+            idx = idx.to(torch.int64) if rel is None else _ids_at(idx, rel)
+            u, v = _ids_at(pi, drugs_d, ptr_d[:-1, None]), _ids_at(pj, drugs_d, ptr_d[:-1, None])
         return RegimenSideEffects(score, idx, u, v)
 
     def add_on_risk(self, regimens, candidates=None, k=10, replace=None, aggregate='noisy_or', weights=None, relations=None,
@@ -1381,11 +1412,8 @@ class TIP(nn.Module):
         candidate forms `burden.view(G, C)`), burden NaN where a candidate is not applicable (a member of the context, an
         empty context, a NaN logit); best_*: the k candidates with the lowest burden, ascending, ties by position in the
         regimen's candidate list, padded with (+inf, -1)."""
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the candidates '
-                                      'with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if exclude not in ('train', 'all', None):
-            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        _refuse_sharded(self.shard, 'candidates')
+        _check_known_mode('exclude', exclude)
         if aggregate not in ops.REGIMEN_AGGREGATES:
             raise ValueError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
         k = int(k)
@@ -1394,7 +1422,7 @@ class TIP(nn.Module):
         d = self.data
         drugs, ptr, cand, cand_ptr = normalize_add_on_queries(regimens, candidates, replace, d.n_drug,
                                                               ops.addon_max_context())
-        rel_host = None if relations is None else torch.as_tensor(relations).to('cpu', torch.int64).reshape(-1)
+        rel_host = _relation_ids(relations, 'cpu')
         n_w = d.n_dd_et if rel_host is None else rel_host.numel()
         if weights is not None:
             try:
@@ -1416,13 +1444,8 @@ class TIP(nn.Module):
         ptr_d, task_ptr_d = both[:G + 1], both[G + 1:2 * G + 2]
         drugs_d, cand_flat_d = both[2 * G + 2:2 * G + 2 + drugs.numel()], both[2 * G + 2 + drugs.numel():]
         cand_d = cand_flat_d[:C] if cand_ptr is None else cand_flat_d
-        known = None
-        if exclude is not None:
-            extra = (d.dd_test_idx, d.dd_test_range) if exclude == 'all' else None
-            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
         rel = None if rel_host is None else rel_host.to(dev)
-        if rel is not None and known is not None:
-            known = ops.restrict_known_relations(known, rel, d.n_dd_et)
+        known = _pair_known(d, exclude, rel)
         with torch.no_grad():
             w_d = None if weights is None else weights.to(dev)
             burden, best_b, best_p = self.decoder.addon_burden(self.embeddings, drugs_d, ptr_d, cand_d,
@@ -1432,9 +1455,7 @@ class TIP(nn.Module):
                 best_b = torch.empty((G, 0), dtype=torch.float32, device=dev)
                 best_drug = torch.empty((G, 0), dtype=torch.int64, device=dev)
             else:
-                lookup = cand_flat_d if cand_flat_d.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
-                at = (task_ptr_d[:-1, None] + best_p).clamp(min=0, max=lookup.numel() - 1)
-                best_drug = torch.where(best_p >= 0, lookup[at], torch.full_like(at, -1))
+                best_drug = _ids_at(best_p, cand_flat_d, task_ptr_d[:-1, None])
         return AddOnRisk(burden.reshape(-1), cand_flat_d, task_ptr_d, best_b, best_drug)
 
     def rank_side_effects(self, triples=None, filter='all', ks=(1, 3, 10), relations=None):
@@ -1452,46 +1473,22 @@ class TIP(nn.Module):
         -> RankReport(rank int64 [T] (0 = not ranked), logit [T] (NaN there), mrr, hits {k: share of ranks <= k},
         per_relation {'count' [R], 'mrr' [R], 'hits' [len(ks), R]}, macro_mrr, unranked): `utils.rank_report` of the ranks;
         the tensors are on the model's device, in the triples' order."""
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the side '
-                                      'effects with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if filter not in ('train', 'all', None):
-            raise ValueError("filter must be 'train', 'all' or None, not %r" % (filter,))
+        _refuse_sharded(self.shard, 'side effects')
+        _check_known_mode('filter', filter)
         d = self.data
         dev = self.embeddings.device
-        idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
-        idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
-        if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
-                or idx.dtype.is_floating_point or et.dtype.is_floating_point:
-            raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
-                             % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
-        if et.numel():
-            lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
-            if lo < 0 or hi >= d.n_drug:
-                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
-            if rlo < 0 or rhi >= d.n_dd_et:
-                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
-        known = None
-        if filter is not None:
-            extra = (d.dd_test_idx, d.dd_test_range) if filter == 'all' else None
-            known = ops.known_relations_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug, extra=extra)
-        rel = None if relations is None else torch.as_tensor(relations).to(device=dev, dtype=torch.int64).reshape(-1)
-        et = et.to(torch.int64)
+        idx, et = _checked_triples(triples, d, dev)
+        rel = _relation_ids(relations, dev)
+        known = _pair_known(d, filter, rel)
         tgt = et
         if rel is not None:
             pos = torch.full((d.n_dd_et,), -1, dtype=torch.int64, device=dev)
             pos[rel] = torch.arange(rel.numel(), device=dev)
             tgt = pos[et]                                                # -1: not a candidate, not ranked
-            if known is not None:
-                known = ops.restrict_known_relations(known, rel, d.n_dd_et)
         with torch.no_grad():
             pairs, tgt_ptr, tgt_rel, order = ops.targets_by_pair(idx, tgt, d.n_drug)
             r, s = self.decoder.relation_ranks(self.embeddings, pairs, tgt_ptr, tgt_rel, known, rel)
-            rank = torch.empty_like(r, dtype=torch.int64)
-            rank[order] = r.to(torch.int64)
-            logit = torch.empty_like(s)
-            logit[order] = s
-        return RankReport(rank, logit, **rank_report(rank, et, d.n_dd_et, ks))
+            return _rank_result(order, r, s, et, d.n_dd_et, ks)
 
     def rank_partners(self, triples=None, filter='all', ks=(1, 3, 10)):
         """Evaluation of what `screen(drugs=...)` serves (extension): where the partner v of each given (drug u, drug v, side
@@ -1508,35 +1505,16 @@ class TIP(nn.Module):
         -> RankReport(rank int64 [T] (0 = not ranked), logit [T] (NaN there), mrr, hits {k: share of ranks <= k},
         per_relation {'count' [R], 'mrr' [R], 'hits' [len(ks), R]} -- the per-side-effect partner MRR --, macro_mrr,
         unranked): `utils.rank_report` of the ranks; the tensors are on the model's device, in the triples' order."""
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the partners '
-                                      'with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if filter not in ('train', 'all', None):
-            raise ValueError("filter must be 'train', 'all' or None, not %r" % (filter,))
+        _refuse_sharded(self.shard, 'partners')
+        _check_known_mode('filter', filter)
         d = self.data
         dev = self.embeddings.device
-        idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
-        idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
-        if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
-                or idx.dtype.is_floating_point or et.dtype.is_floating_point:
-            raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
-                             % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
-        if et.numel():
-            lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
-            if lo < 0 or hi >= d.n_drug:
-                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
-            if rlo < 0 or rhi >= d.n_dd_et:
-                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
+        idx, et = _checked_triples(triples, d, dev)
         known = _screen_known(d, filter)
-        et = et.to(torch.int64)
         with torch.no_grad():
             q_rel, q_drug, tgt_ptr, tgt_node, order = ops.targets_by_query(idx, et, d.n_drug)
             r, s = self.decoder.partner_ranks(self.embeddings, q_rel, q_drug, tgt_ptr, tgt_node, known)
-            rank = torch.empty_like(r, dtype=torch.int64)
-            rank[order] = r.to(torch.int64)
-            logit = torch.empty_like(s)
-            logit[order] = s
-        return RankReport(rank, logit, **rank_report(rank, et, d.n_dd_et, ks))
+            return _rank_result(order, r, s, et, d.n_dd_et, ks)
 
     def rank_pairs(self, triples=None, filter='all', ks=(1, 10, 50)):
         """Evaluation of what the relation screen `screen()` serves (extension): where the pair {u, v} of each given (drug u,
@@ -1555,35 +1533,16 @@ class TIP(nn.Module):
         the tensors are on the model's device, in the triples' order."""
         if self.decoder_kind == 'nn':
             raise NotImplementedError('rank_pairs ranks DistMult logits over all pairs; the NN decoder has no screen kernel')
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; rank the pairs '
-                                      'with the unsharded model (tip_amd.dist.gather_state_dict)')
-        if filter not in ('train', 'all', None):
-            raise ValueError("filter must be 'train', 'all' or None, not %r" % (filter,))
+        _refuse_sharded(self.shard, 'pairs')
+        _check_known_mode('filter', filter)
         d = self.data
         dev = self.embeddings.device
-        idx, et = (d.dd_test_idx, d.dd_test_et) if triples is None else triples
-        idx, et = torch.as_tensor(idx).to(dev), torch.as_tensor(et).to(dev)
-        if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] \
-                or idx.dtype.is_floating_point or et.dtype.is_floating_point:
-            raise ValueError('triples: int tensors (edge_index [2, T], edge_type [T]) expected, got %s %s and %s %s'
-                             % (idx.dtype, tuple(idx.shape), et.dtype, tuple(et.shape)))
-        if et.numel():
-            lo, hi, rlo, rhi = torch.stack([idx.min(), idx.max(), et.min(), et.max()]).tolist()
-            if lo < 0 or hi >= d.n_drug:
-                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, d.n_drug))
-            if rlo < 0 or rhi >= d.n_dd_et:
-                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (rlo, rhi, d.n_dd_et))
+        idx, et = _checked_triples(triples, d, dev)
         known = _screen_known(d, filter)
-        et = et.to(torch.int64)
         with torch.no_grad():
             q_rel, tgt_ptr, tgt_u, tgt_v, order = ops.targets_by_relation(idx, et, d.n_dd_et)
             r, s = self.decoder.pair_ranks(self.embeddings, q_rel, tgt_ptr, tgt_u, tgt_v, known)
-            rank = torch.empty_like(r, dtype=torch.int64)
-            rank[order] = r.to(torch.int64)
-            logit = torch.empty_like(s)
-            logit[order] = s
-        return RankReport(rank, logit, **rank_report(rank, et, d.n_dd_et, ks))
+            return _rank_result(order, r, s, et, d.n_dd_et, ks)
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it
@@ -1595,11 +1554,8 @@ class TIP(nn.Module):
         -> ScreenResult(score [Q, k], u [Q, k], v [Q, k], relation [Q, k]) on the model's device."""
         if self.decoder_kind == 'nn':
             raise NotImplementedError('screen ranks DistMult logits over all pairs; the NN decoder has no screen kernel')
-        if self.shard is not None:
-            raise NotImplementedError('a relation-sharded model holds only its shard\'s decoder rows; screen the '
-                                      'unsharded model (tip_amd.dist.gather_state_dict)')
-        if exclude not in ('train', 'all', None):
-            raise ValueError("exclude must be 'train', 'all' or None, not %r" % (exclude,))
+        _refuse_sharded(self.shard, 'screen')
+        _check_known_mode('exclude', exclude)
         known = _screen_known(self.data, exclude)
         q = screen_queries(self.decoder.num_et, relations, drugs)
         with torch.no_grad():

@@ -1060,25 +1060,15 @@ def distmult_screen(z, rel_w, queries, k, known=None):
 
     queries: int [Q, 2] = (relation r, drug u), u = -1 for a relation query (all pairs u < v), else a drug query (all
     partners v != u); read on the host.  known: None or (keys int64 u*n+v sorted inside each relation, ptr int64
-    [n_rel + 1]) on z's device -- the sampler's layout (`neg_sampling._cached_keys`).
+    [n_rel + 1]) on z's device -- the sampler's layout (`neg_sampling._cached_keys`); a list without keys drops nothing.
     -> (logits float32 [Q, k], u int32 [Q, k], v int32 [Q, k]), descending logit then ascending key; (-inf, -1, -1)
     pads a query with fewer than k candidates.  Synchronises the current stream once (the query list goes to the device)."""
-    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
-    require_device(z, rel_w)
-    if z.dim() != 2 or rel_w.dim() != 2 or rel_w.shape[1] != z.shape[1]:
-        raise _lib.TipkError('distmult_screen: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
-                             % (tuple(z.shape), tuple(rel_w.shape)))
-    keys = kptr = None
-    if known is not None:
-        keys, kptr = known
-        require_device(keys, kptr)
-        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_screen')
+    keys, kptr = _relation_known(known)
     q = torch.as_tensor(queries).to('cpu', torch.int32).reshape(-1, 2).contiguous()
     n, dim, n_q, k = z.shape[0], z.shape[1], q.shape[0], int(k)
     dev = z.device
-    out_s = torch.empty((n_q, max(k, 0)), dtype=torch.float32, device=dev)
-    out_u = torch.empty((n_q, max(k, 0)), dtype=torch.int32, device=dev)
-    out_v = torch.empty((n_q, max(k, 0)), dtype=torch.int32, device=dev)
+    out_s, out_u, out_v = _topk_outputs(n_q, k, 2, dev)
     ws_bytes = int(lib().tipk_distmult_screen_workspace_bytes(n, dim, n_q, k))
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
     check(lib().tipk_distmult_screen(ptr(z), n, dim, ptr(rel_w), rel_w.shape[0], ptr(q), n_q, ptr(keys), ptr(kptr), k,
@@ -1142,6 +1132,25 @@ def _known_lists(known):
     return keys, kptr, krel, n_keys
 
 
+def _relation_known(known):
+    """(keys, ptr) of a relation-major known list (`distmult_screen`) for the C entries: int64 contiguous device tensors, or
+    (None, None) when there is nothing to drop -- None, or a list without keys (empty tensors have no address)."""
+    if known is None:
+        return None, None
+    keys, kptr = known
+    require_device(keys, kptr)
+    if keys.numel() == 0:
+        return None, None
+    return keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
+
+
+def _topk_outputs(n_rows, k, n_int, dev):
+    """The [n_rows, max(k, 0)] outputs of a top-k entry on `dev`: the float32 scores, then n_int int32 tensors."""
+    shape = (n_rows, max(int(k), 0))
+    return (torch.empty(shape, dtype=torch.float32, device=dev),) \
+        + tuple(torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(n_int))
+
+
 def _distmult_operands(z, rel_w, who):
     """z [n, dim] and rel_w [n_rel, dim] as contiguous fp32 device tensors for the entry `who`."""
     z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
@@ -1186,8 +1195,7 @@ def distmult_pair_topk(z, rel_w, pairs, k, known=None):
     dev = z.device
     pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
     n, dim, n_rel, n_p, k = z.shape[0], z.shape[1], rel_w.shape[0], pu.numel(), int(k)
-    out_s = torch.empty((n_p, max(k, 0)), dtype=torch.float32, device=dev)
-    out_r = torch.empty((n_p, max(k, 0)), dtype=torch.int32, device=dev)
+    out_s, out_r = _topk_outputs(n_p, k, 1, dev)
     ws_bytes = int(lib().tipk_distmult_pair_topk_workspace_bytes(n, dim, n_rel, n_p, k))
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
     check(lib().tipk_distmult_pair_topk(ptr(z), n, dim, ptr(rel_w), n_rel, ptr(pu), ptr(pv), n_p, ptr(keys), ptr(kptr),
@@ -1203,8 +1211,7 @@ def pair_table_pair_topk(s1, s2, pairs, k, known=None):
     dev = s1.device
     pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
     n, n_rel, n_p, k = s1.shape[0], s1.shape[1], pu.numel(), int(k)
-    out_s = torch.empty((n_p, max(k, 0)), dtype=torch.float32, device=dev)
-    out_r = torch.empty((n_p, max(k, 0)), dtype=torch.int32, device=dev)
+    out_s, out_r = _topk_outputs(n_p, k, 1, dev)
     check(lib().tipk_pair_table_pair_topk(ptr(s1), ptr(s2), s1.stride(0), n, n_rel, ptr(pu), ptr(pv), n_p, ptr(keys),
                                           ptr(kptr), ptr(krel), n_keys, k, ptr(out_s), ptr(out_r), stream_ptr(dev)),
           'tipk_pair_table_pair_topk')
@@ -1339,13 +1346,7 @@ def _partner_rank_lists(q_rel, q_drug, tgt_ptr, tgt_node, known, dev):
         raise _lib.TipkError('queries: int tensors q_rel [Q] and q_drug [Q] expected, got %s %s and %s %s'
                              % (q_rel.dtype, tuple(q_rel.shape), q_drug.dtype, tuple(q_drug.shape)))
     tptr, tnode, n_tgt, out_rank, out_logit = _rank_targets(tgt_ptr, tgt_node, q_rel.numel(), dev)
-    keys = kptr = None
-    if known is not None:
-        keys, kptr = known
-        require_device(keys, kptr)
-        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
-        if keys.numel() == 0:                                            # nothing to drop (empty tensors have no address)
-            keys = kptr = None
+    keys, kptr = _relation_known(known)
     qr, qd = q_rel.to(torch.int32).contiguous(), q_drug.to(torch.int32).contiguous()
     return qr, qd, tptr, tnode, n_tgt, keys, kptr, out_rank, out_logit
 
@@ -1419,13 +1420,7 @@ def distmult_screen_rank(z, rel_w, q_rel, tgt_ptr, tgt_u, tgt_v, known=None):
     if tgt_v.dim() != 1 or tgt_v.numel() != n_tgt or tgt_v.dtype.is_floating_point:
         raise _lib.TipkError('targets: int tensors tgt_u [%d] and tgt_v [%d] expected, got tgt_v %s %s'
                              % (n_tgt, n_tgt, tgt_v.dtype, tuple(tgt_v.shape)))
-    keys = kptr = None
-    if known is not None:
-        keys, kptr = known
-        require_device(keys, kptr)
-        keys, kptr = keys.to(torch.int64).contiguous(), kptr.to(torch.int64).contiguous()
-        if keys.numel() == 0:                                            # nothing to drop (empty tensors have no address)
-            keys = kptr = None
+    keys, kptr = _relation_known(known)
     qr, tv = q_rel.to(torch.int32).contiguous(), tgt_v.to(torch.int32).contiguous()
     n, dim = z.shape
     ws_bytes = int(lib().tipk_distmult_screen_rank_workspace_bytes(n, dim, qr.numel(), n_tgt))
@@ -1457,10 +1452,7 @@ def _regimen_args(reg_drugs, reg_ptr, k, aggregate, known, dev):
     if drugs.numel() == 0:                                               # an empty tensor has no address
         drugs = torch.zeros(1, dtype=torch.int32, device=dev)
     n_g, k = rptr.numel() - 1, int(k)
-    out_s = torch.empty((n_g, max(k, 0)), dtype=torch.float32, device=dev)
-    out_r = torch.empty((n_g, max(k, 0)), dtype=torch.int32, device=dev)
-    out_p = torch.empty((n_g, max(k, 0)), dtype=torch.int32, device=dev)
-    return drugs, rptr, n_g, k, REGIMEN_AGGREGATES[aggregate], _known_lists(known), out_s, out_r, out_p
+    return (drugs, rptr, n_g, k, REGIMEN_AGGREGATES[aggregate], _known_lists(known)) + _topk_outputs(n_g, k, 2, dev)
 
 
 def _regimen_result(out_s, out_r, out_p):
