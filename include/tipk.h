@@ -63,6 +63,8 @@ const char* tipk_build_id(void);
  *                            (section 4g; both routes return the same bits)
  *      "addon_global"        1 = tipk_distmult_addon_burden reads rel_w rows from global memory even where the LDS image
  *                            fits (section 4i; both routes return the same bits)
+ *      "attribution_global"  1 = tipk_rgcn_attribution keeps the per-query table in the caller's workspace even where it fits
+ *                            in LDS (section 4j; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -1165,6 +1167,60 @@ int     tipk_pair_table_addon_burden(const float* s1, const float* s2, int64_t l
                                      int64_t n_known_pairs /* nullable together */,
                                      int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
                                      int32_t* out_best_pos /* nullable with k == 0 */, tipk_stream_t stream);
+
+/* 4j. Edge attribution of the last R-GCN layer: which recorded interactions of a drug make the model say what it says
+ *     (serving; no reference call site -- the identity is that of MyRGCNConv2, src/layers.py:157-188, read backwards).
+ *
+ *   rgcn2 has no ReLU behind it, so with h [n_nodes x d_in] (row stride ld_h), basis [n_bases x d_in x d_out] dense,
+ *   att [n_rel x n_bases] (row stride ld_att), root [d_in x d_out] dense and the in-edges In(v) of node v
+ *     z[v] = 1/max(deg_v, 1) * sum_{e in In(v)} h[src_e] W_{rel_e} + h[v] root,      W_r = sum_b att[r,b] basis[b],
+ *   and for a probe g [d_out]:  g . z[v] = own + sum_{e in In(v)} c_e.  Both decoders are linear in z[v] with the other drug
+ *   held fixed, so a logit splits exactly into one number per recorded interaction of v plus v's own features.
+ *   In-edges, CSR, DEVICE: in_ptr int64 [n_nodes + 1], in_src / in_rel int32 [n_edges]: node v owns the positions
+ *   in_ptr[v] .. in_ptr[v+1], sorted by (relation, source); deg_v = in_ptr[v+1] - in_ptr[v], duplicates counted (each is an
+ *   entry of its own).  Keeping in_src in [0, n_nodes) and in_rel in [0, n_rel) is the caller's contract
+ *   (tip_amd.ops.in_edges_by_node guarantees it); in_ptr is clamped to [0, n_edges].
+ *   Query q = (node q_node[q], probe row probe[q * ld_probe .. + d_out)), all DEVICE.
+ *   Arithmetic, fp32, ONE value per edge on every route -- three nested fma chains, each starting at 0.0f:
+ *     G[b,i]  : acc = fmaf(basis[b,i,o], g[o], acc)        for o = 0 .. d_out - 1 ascending
+ *     M[s,b]  : acc = fmaf(h[s,i], G[b,i], acc)            for i = 0 .. d_in - 1 ascending
+ *     a_e     : acc = fmaf(att[rel_e,b], M[src_e,b], acc)  for b = 0 .. n_bases - 1 ascending
+ *     c_e = (1.0f / (float)max(deg_v, 1)) * a_e            (a correctly rounded reciprocal, then one multiply)
+ *     own     : R[i]: acc = fmaf(root[i,o], g[o], acc), o ascending; then acc = fmaf(h[v,i], R[i], acc), i ascending.
+ *   Output (device), per query: out_contrib fp32 / out_src int32 / out_rel int32 [n_q x k] = the k in-edges of the node with
+ *   the largest c_e, c_e descending, ties (+0 and -0 tie) by ascending position in the node's CSR segment, with the edge's
+ *   source and relation; a query with fewer than k edges is padded with (-inf, -1, -1); an edge whose c_e is NaN is never
+ *   listed.  out_own [n_q] = own.  out_sum [n_q] = the sum of ALL c_e of the node (not only the listed): every fp32 c_e is
+ *   added in fp64 -- thread t of 256 adds the edges at positions t, t + 256, ... ascending, lanes are combined by
+ *   x_l += x_(l + off) for off = 32, 16, 8, 4, 2, 1, the four wavefronts as ((w0 + w1) + w2) + w3 -- and rounded once to
+ *   fp32.  No float atomics anywhere: every output is BITWISE repeatable run to run and route to route.
+ *   q_node outside [0, n_nodes): a fully padded row, out_own = out_sum = NaN, nothing read out of bounds.  deg 0: padding
+ *   only, out_sum = +0.
+ *   Work: ONE launch, one workgroup of 256 threads per query: G, then the table M for every node from h staged through LDS,
+ *   then one pass over the node's in-edges with the selection of 4c (LDS buffer, running threshold, bitonic cut).
+ *   Routes: M [n_nodes x n_bases] lives in LDS where it fits beside the rest (tipk_rgcn_attribution_lds_route: 645 x 32
+ *   does); otherwise, or under option "attribution_global", in `workspace`, one slice per workgroup, and at most 256
+ *   workgroups loop over the queries; same code, same bits.
+ *   Supported: 1 <= n_nodes <= 46 340, 1 <= n_rel <= 65 536, 1 <= n_bases <= 64, 1 <= d_in, d_out <= 128 (any width),
+ *   1 <= k <= 1 024; n_edges and n_q below 2^31.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k <= 0, a negative size, n_nodes, n_rel, n_bases,
+ *   d_in or d_out < 1, a row stride shorter than its row, a NULL required pointer (with n_q > 0: everything but `workspace`
+ *   on the LDS route, and in_src / in_rel when n_edges == 0); then TIPK_EUNSUPPORTED outside the supported range; n_q == 0
+ *   is TIPK_OK with no launch and nothing written.
+ *   workspace: tipk_rgcn_attribution_workspace_bytes(...) bytes (-1: unsupported); 0 on the LDS route, and `workspace` may
+ *   then be NULL.  The value follows the option: ask after setting it.
+ *   Nothing lives in host memory: the entry does NOT synchronise or allocate and may be captured into a hipGraph.
+ */
+int     tipk_rgcn_attribution_supported(int64_t n_nodes, int64_t n_rel, int n_bases, int d_in, int d_out, int k);
+int     tipk_rgcn_attribution_lds_route(int64_t n_nodes, int n_bases);          /* 1 = per-query table lives in LDS (options apply) */
+int64_t tipk_rgcn_attribution_workspace_bytes(int64_t n_nodes, int n_bases, int64_t n_q);   /* -1 unsupported; may be 0 */
+int     tipk_rgcn_attribution(const float* h, int64_t ld_h, int64_t n_nodes, int d_in,
+                              const float* basis, const float* att, int64_t ld_att, int64_t n_rel, int n_bases,
+                              const float* root, int d_out,
+                              const int64_t* in_ptr /* [n_nodes+1] */, const int32_t* in_src, const int32_t* in_rel, int64_t n_edges,
+                              const int32_t* q_node /* [n_q] */, const float* probe, int64_t ld_probe, int64_t n_q, int k,
+                              float* out_contrib, int32_t* out_src, int32_t* out_rel /* [n_q x k] */,
+                              float* out_own, float* out_sum /* [n_q] */, void* workspace, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

@@ -38,7 +38,8 @@ enum {
     TIPK_OPT_PAIR_RANK_STREAM = 11,   // tipk_distmult_pair_rank: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_PARTNER_RANK_GLOBAL = 12, // tipk_distmult_partner_rank: z rows read from global memory even where the LDS image fits
     TIPK_OPT_ADDON_GLOBAL = 13,       // tipk_distmult_addon_burden: rel_w rows read from global memory even where the LDS image fits
-    TIPK_OPT_COUNT = 14
+    TIPK_OPT_ATTRIBUTION_GLOBAL = 14, // tipk_rgcn_attribution: the per-query table in the caller's workspace even where it fits in LDS
+    TIPK_OPT_COUNT = 15
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

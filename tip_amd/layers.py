@@ -33,6 +33,7 @@ EPS = 1e-13                    # src/layers.py:15
 ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
+Explanation = namedtuple('Explanation', ['logit', 'offset', 'own', 'neighbours', 'contribution', 'partner', 'relation', 'degree'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
@@ -630,6 +631,18 @@ class MyRGCNConv2(_RGCNBase):
             partner = (next_layer.att, next_layer.graph_for(n, edge_index, range_list), next_layer.out_channels, cells_token)
         return self._run(x, graph, fuse_relu, gate_input, defer_output, partner, cells_token if next_layer is None else None)
 
+    def attribute(self, h, edge_index, range_list, q_node, probe, k):
+        """Edge attribution (extension, `tipk_rgcn_attribution`): with z = this layer applied to h, the k in-edges of every
+        node of q_node [Q] that contribute most to probe[q] . z[node] -> (contribution [Q, k], source int32 [Q, k], relation
+        int32 [Q, k], own [Q], total [Q]) as `ops.rgcn_edge_attribution`; no autograd.  Exact only where nothing follows
+        the layer's sum: a layer with a bias or a relation shard is refused."""
+        if self.bias is not None or self.shard is not None:
+            raise NotImplementedError('attribute splits the sum of a bias-free layer that holds every relation; this layer '
+                                      'has a bias or a relation shard')
+        in_edges = ops.in_edges_by_node(edge_index, range_list, h.shape[0])
+        return ops.rgcn_edge_attribution(h.detach(), self.basis.detach(), self.att.detach(), self.root.detach(), in_edges,
+                                         q_node, probe, k)
+
 
 class MyRGCNConv(_RGCNBase):
     """Per-edge-type variant (:21-99): same arithmetic, relation id taken from `edge_type`; the
@@ -719,6 +732,16 @@ class FMEncoder(nn.Module):
                         next_layer=self.rgcn2, cells_token=tok)
         return self.rgcn2(x1, dd_edge_index, dd_edge_type, dd_range_list, gate_input=True, cells_token=tok)
 
+    def encode_layers(self, x_drug, dd_edge_index, dd_edge_type, dd_range_list, d_norm,
+                      x_prot, pp_edge_index, dp_edge_index, dp_range_list):
+        """`forward`'s arguments -> (h, z) under no_grad: h = relu(rgcn1(x0)), the input of the last layer, and z = rgcn2(h),
+        the embeddings, layer by layer (what `TIP.explain` splits).  z equals `forward`'s result up to the rounding between
+        the per-layer and the fused route."""
+        with torch.no_grad():
+            x0 = self.mixed_drug_features(x_drug, d_norm, x_prot, pp_edge_index, dp_edge_index, dp_range_list)
+            h = self.rgcn1(x0, dd_edge_index, dd_edge_type, dd_range_list, fuse_relu=True)
+            return h, self.rgcn2(h, dd_edge_index, dd_edge_type, dd_range_list)
+
     def mixed_drug_features(self, x_drug, d_norm, x_prot, pp_edge_index, dp_edge_index, dp_range_list):
         """The input of the D-D layers (src/layers.py:522-539): P-P GCN x2 -> P -> D mean -> dense map, drug embedding /
         d_norm, cat | add.  (The part of the step a relation-sharded run repeats on every rank.)"""
@@ -800,6 +823,17 @@ class MultiInnerProductDecoder(nn.Module):
     def objective(self, z, pos_index, neg_index, edge_type):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps), fused (K9+K10)."""
         return ops.distmult_objective(z, self.weight, pos_index, neg_index, edge_type)
+
+    def probe(self, z, edge_index, edge_type, side='v'):
+        """The logit of every triple (u, v, r) as a linear function of ONE drug's embedding (extension, `TIP.explain`) ->
+        (node int64 [T], probe [T, in_dim], offset [T]) with logit = offset + probe . z[node]: side 'v' explains v with
+        probe = z[u] * weight[r], side 'u' explains u with probe = z[v] * weight[r]; the offset is 0 (DistMult is bilinear).
+        Plain torch ops under no_grad."""
+        with torch.no_grad():
+            u, v = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+            node, other = (v, u) if side == 'v' else (u, v)
+            g = z.detach()[other] * self.weight.detach()[edge_type]
+            return node, g, g.new_zeros(g.shape[0])
 
     def _rows(self, relations=None):
         """The weight rows the queries rank with, detached: all, or those of the candidate ids `relations`."""
@@ -1038,6 +1072,20 @@ class NNDecoder(nn.Module):
         if relation_major:
             return ops.matmul(w1, p.t()), ops.matmul(w2, q.t())
         return ops.matmul(p, w1.t()), ops.matmul(q, w2.t())
+
+    def probe(self, z, edge_index, edge_type, side='v'):
+        """`MultiInnerProductDecoder.probe` for this decoder -> (node int64 [T], probe [T, in_dim], offset [T]).  The
+        decoder is bias-free and piecewise linear in z[node], so its part of the logit equals its own gradient times
+        z[node]: side 'v': probe = w2_l1 (m * w2_l2[r]) with the ReLU mask m = (z[v] w2_l1 > 0), offset = the first drug's
+        part relu(z[u] w1_l1) . w1_l2[r]; side 'u' is the mirror image with w1_* and the second drug's part as offset."""
+        with torch.no_grad():
+            u, v = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+            z = z.detach()
+            first = (self.w1_l1.detach(), self.w1_l2.detach()[edge_type], u)
+            second = (self.w2_l1.detach(), self.w2_l2.detach()[edge_type], v)
+            (l1, l2, node), (o1, o2, other) = (second, first) if side == 'v' else (first, second)
+            mask = (z[node] @ l1 > 0).to(z.dtype)
+            return node, (mask * l2) @ l1.t(), (torch.relu(z[other] @ o1) * o2).sum(1)
 
     def forward(self, z, edge_index, edge_type):
         s1, s2 = self._tables(z)
@@ -1543,6 +1591,49 @@ class TIP(nn.Module):
             q_rel, tgt_ptr, tgt_u, tgt_v, order = ops.targets_by_relation(idx, et, d.n_dd_et)
             r, s = self.decoder.pair_ranks(self.embeddings, q_rel, tgt_ptr, tgt_u, tgt_v, known)
             return _rank_result(order, r, s, et, d.n_dd_et, ks)
+
+    def explain(self, triples=None, k=10, side='v', direction='raise'):
+        """Why the model predicts what it predicts (extension): the logit of every given (drug u, drug v, side effect r)
+        triple, split EXACTLY over the recorded interactions of one of its drugs.  The last encoder layer has no ReLU behind
+        it and both decoders are linear in one drug's embedding with the other held fixed, so
+            logit = offset + own + neighbours,   neighbours = the sum of one contribution per training interaction of the drug,
+        and the k largest contributions are listed (`MyRGCNConv2.attribute`: one `tipk_rgcn_attribution` launch, no E x d
+        temporary; both decoder kinds).
+        triples: None = the held-out set, else (edge_index int [2, T], edge_type int [T]), as `rank_pairs`.  side: 'v'
+        explains the second drug of every triple, 'u' the first.  direction: 'raise' lists the interactions that push the
+        logit up most, largest first; 'lower' those that pull it down most, most negative first.
+        The model is RE-ENCODED with its current parameters, layer by layer (`FMEncoder.encode_layers`, under no_grad);
+        `self.embeddings` is not overwritten.  After a `forward()` with no optimiser step since, `logit` equals `pred`'s
+        logit up to the rounding between the per-layer and the fused encoder route.
+        -> Explanation(logit [T]: the decoder's logit of the re-encoded embeddings; offset [T]: the other drug's part (NN
+        decoder; 0 for DistMult); own [T]: the part of the drug's own features; neighbours [T]: the sum of ALL its
+        interactions' contributions; contribution [T, k], partner int64 [T, k], relation int64 [T, k]: the listed
+        interactions -- the partner drug and side effect of each --, padded with (-inf, or +inf under 'lower'; -1; -1);
+        degree int64 [T]: the drug's number of training interactions) on the model's device, in the triples' order."""
+        _refuse_sharded(self.shard, 'interactions')
+        if side not in ('u', 'v'):
+            raise ValueError("side must be 'u' or 'v', not %r" % (side,))
+        if direction not in ('raise', 'lower'):
+            raise ValueError("direction must be 'raise' or 'lower', not %r" % (direction,))
+        d = self.data
+        dev = self.embeddings.device
+        idx, et = _checked_triples(triples, d, dev)
+        with torch.no_grad():
+            h, z = self.encoder.encode_layers(d.d_feat, d.dd_train_idx, d.dd_train_et, d.dd_train_range, d.d_norm,
+                                              d.p_feat, d.pp_train_indices, d.dp_edge_index, d.dp_range_list)
+            node, probe, offset = self.decoder.probe(z, idx, et, side)
+            if self.decoder_kind == 'nn':
+                logit = ops.pair_table_score(*self.decoder._tables(z), idx, et, sigmoid=False)
+            else:
+                logit = self.decoder(z, idx, et, sigmoid=False)
+            lower = direction == 'lower'
+            c, src, rel, own, total = self.encoder.rgcn2.attribute(h, d.dd_train_idx, d.dd_train_range, node,
+                                                                   -probe if lower else probe, k)
+            if lower:
+                c, own, total = -c, -own, -total
+            in_ptr = ops.in_edges_by_node(d.dd_train_idx, d.dd_train_range, h.shape[0])[0]
+            return Explanation(logit, offset, own, total, c, src.to(torch.int64), rel.to(torch.int64),
+                               in_ptr[node + 1] - in_ptr[node])
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

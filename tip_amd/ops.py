@@ -1573,6 +1573,111 @@ def pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggre
     return out_b, best_b, best_p
 
 
+_IN_EDGES = {}
+
+
+def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
+    """The in-edge CSR of include/tipk.h section 4j from a directed edge list (source_to_target: edge e runs from
+    edge_index[0][e] to edge_index[1][e]) -> (in_ptr int64 [n_nodes + 1], in_src int32 [E], in_rel int32 [E]): node v owns the
+    positions in_ptr[v] .. in_ptr[v+1], sorted by (relation, source); duplicate edges stay separate entries.
+    range_list_or_type: range_list [R, 2] (relation r owns the edge positions [begin, end), the blocks tile the list in
+    relation order) or edge_type int [E].  Built with torch ops on edge_index's device (CPU tensors work too): one stable
+    sort of the key (dst * R + rel) * n + src.  IndexError for a node id outside [0, n_nodes) or a negative relation.
+    Cached per edge tensor(s)."""
+    def ident(t):
+        return (t.data_ptr(), t._version, tuple(t.shape), str(t.device)) if torch.is_tensor(t) else None
+
+    edge_index = torch.as_tensor(edge_index)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype.is_floating_point:
+        raise _lib.TipkError('in_edges_by_node: an int tensor edge_index [2, E] expected, got %s %s'
+                             % (edge_index.dtype, tuple(edge_index.shape)))
+    n, n_edges, dev = int(n_nodes), edge_index.shape[1], edge_index.device
+    tag = (ident(edge_index), ident(range_list_or_type), n)
+    hit = _IN_EDGES.get(tag) if tag[1] is not None else None
+    if hit is not None:
+        return hit
+    rt = torch.as_tensor(range_list_or_type)
+    if rt.dtype.is_floating_point:
+        raise _lib.TipkError('in_edges_by_node: an int range_list [R, 2] or edge_type [E] expected, got %s' % rt.dtype)
+    if rt.dim() == 2 and rt.shape[1] == 2:
+        ends = rt.to(device=dev, dtype=torch.int64)[:, 1].contiguous()
+        if rt.shape[0] == 0 or int(ends[-1]) != n_edges:
+            raise _lib.TipkError('in_edges_by_node: range_list must tile all %d edges' % n_edges)
+        rel = torch.bucketize(torch.arange(n_edges, device=dev), ends, right=True)
+        n_rel = rt.shape[0]
+    elif rt.dim() == 1 and rt.numel() == n_edges:
+        rel = rt.to(device=dev, dtype=torch.int64)
+        n_rel = int(rel.max()) + 1 if n_edges else 1
+    else:
+        raise _lib.TipkError('in_edges_by_node: range_list [R, 2] or edge_type [%d] expected, got %s'
+                             % (n_edges, tuple(rt.shape)))
+    src, dst = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+    if n_edges:
+        lo, hi, rlo = torch.stack([edge_index.min(), edge_index.max(), rel.min()]).tolist()
+        if lo < 0 or hi >= n:
+            raise IndexError('node id out of range: [%d, %d] for %d nodes' % (lo, hi, n))
+        if rlo < 0:
+            raise IndexError('relation id out of range: %d' % rlo)
+    order = torch.sort((dst * n_rel + rel) * n + src, stable=True)[1]
+    in_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    in_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
+    hit = (in_ptr, src[order].to(torch.int32).contiguous(), rel[order].to(torch.int32).contiguous())
+    if tag[1] is not None:
+        if len(_IN_EDGES) > 8:
+            _IN_EDGES.clear()
+        _IN_EDGES[tag] = hit
+    return hit
+
+
+def rgcn_edge_attribution(h, basis, att, root, in_edges, q_node, probe, k):
+    """The k in-edges of every queried node that contribute most to probe . z[node], z = the bias-free R-GCN layer
+    (basis, att, root) applied to h (include/tipk.h section 4j; one launch, no E x d temporary).
+
+    h [n, d_in] (row stride free), basis [B, d_in, d_out], att [R, B], root [d_in, d_out]: fp32 device tensors; in_edges:
+    `in_edges_by_node` of the layer's graph, on the device; q_node int [Q]; probe fp32 [Q, d_out].
+    -> (contrib float32 [Q, k], src int32 [Q, k], rel int32 [Q, k], own float32 [Q], total float32 [Q]): the k largest
+    per-edge contributions c_e, descending, ties by position in the node's segment, with the edge's source and relation,
+    padded with (-inf, -1, -1); own = probe . (h[node] root); total = the sum of ALL c_e of the node (fp64 accumulation,
+    rounded once), so probe . z[node] = own + total up to rounding.  A node outside [0, n): padding and NaN own / total.
+    Bitwise repeatable.  Does not synchronise (a first call checks the ids of `in_edges` once per tensor)."""
+    h, basis, att, root, probe = _f32c(h), _f32c(basis).contiguous(), _f32c(att), _f32c(root).contiguous(), _f32c(probe)
+    in_ptr, in_src, in_rel = in_edges
+    q_node = torch.as_tensor(q_node)
+    require_device(h, basis, att, root, probe, in_ptr, in_src, in_rel, q_node)
+    if h.dim() != 2 or basis.dim() != 3 or att.dim() != 2 or root.dim() != 2 or basis.shape[1] != h.shape[1] or \
+            att.shape[1] != basis.shape[0] or tuple(root.shape) != tuple(basis.shape[1:]):
+        raise _lib.TipkError('rgcn_edge_attribution: h [n, d_in], basis [B, d_in, d_out], att [R, B], root [d_in, d_out] expected, '
+                             'got %s, %s, %s, %s' % (tuple(h.shape), tuple(basis.shape), tuple(att.shape), tuple(root.shape)))
+    n, d_in = h.shape
+    n_bases, _, d_out = basis.shape
+    n_rel, k = att.shape[0], int(k)
+    if q_node.dim() != 1 or q_node.dtype.is_floating_point or probe.dim() != 2 or \
+            tuple(probe.shape) != (q_node.numel(), d_out):
+        raise _lib.TipkError('rgcn_edge_attribution: q_node int [Q] and probe [Q, %d] expected, got %s %s and %s'
+                             % (d_out, q_node.dtype, tuple(q_node.shape), tuple(probe.shape)))
+    if in_ptr.dtype != torch.int64 or in_src.dtype != torch.int32 or in_rel.dtype != torch.int32 or \
+            in_ptr.numel() != n + 1 or in_src.dim() != 1 or in_src.shape != in_rel.shape:
+        raise _lib.TipkError('rgcn_edge_attribution: in_edges = (int64 [%d], int32 [E], int32 [E]) of in_edges_by_node expected'
+                             % (n + 1))
+    if h.stride(0) < d_in or att.stride(0) < n_bases or probe.stride(0) < d_out:
+        h, att, probe = h.contiguous(), att.contiguous(), probe.contiguous()
+    _range_checked(in_src, n, 'in_edges source')
+    _range_checked(in_rel, n_rel, 'in_edges relation')
+    dev, n_q = h.device, q_node.numel()
+    in_ptr, in_src, in_rel = in_ptr.contiguous(), in_src.contiguous(), in_rel.contiguous()
+    qn = q_node.to(torch.int32).contiguous()
+    contrib, src, rel = _topk_outputs(n_q, k, 2, dev)
+    own = torch.empty(n_q, dtype=torch.float32, device=dev)
+    total = torch.empty(n_q, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib().tipk_rgcn_attribution_workspace_bytes(n, n_bases, n_q))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes > 0 else None
+    check(lib().tipk_rgcn_attribution(ptr(h), h.stride(0), n, d_in, ptr(basis), ptr(att), att.stride(0), n_rel, n_bases,
+                                      ptr(root), d_out, ptr(in_ptr), ptr(in_src), ptr(in_rel), in_src.numel(), ptr(qn),
+                                      ptr(probe), probe.stride(0), n_q, k, ptr(contrib), ptr(src), ptr(rel), ptr(own),
+                                      ptr(total), ptr(ws), stream_ptr(dev)), 'tipk_rgcn_attribution')
+    return contrib, src, rel, own, total
+
+
 _DET_WS = {}
 
 
