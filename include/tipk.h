@@ -1353,6 +1353,9 @@ int tipk_peer_status(void* mailbox, int world, int64_t max_floats, uint64_t* err
  *    exp_avg, exp_avg_sq must share one dense layout of numel[i] elements):
  *        g += weight_decay * p;  m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g g;
  *        p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps),      t = *steps[i] + 1
+ *    in fp32, every hyper-parameter constant -- beta2, 1 - beta1, 1 - beta2, weight_decay, eps, lr / (1 - beta1^t),
+ *    1 / sqrt(1 - beta2^t) -- formed in double and rounded ONCE to fp32 (never 1.0f - (float)beta: that is 216 u = 1.3e-5
+ *    off for beta2 = 0.999); `/` and sqrt correctly rounded.  tests/adam_spec.py holds the step to the rounding bound of that.
  *    steps: host array [n_tensors] of device uint64 words, the steps tensor i has made (torch keeps the count per
  *    parameter: one without a gradient sits the step out); ticket: device uint64[528], zeros (left zeroed; 33 ticket words, one per 128-byte line).  The launch's last workgroup adds 1 to
  *    the counts of its tensors -- a captured hipGraph keeps counting on replay.  Tensors with numel 0 are skipped (their

@@ -45,8 +45,13 @@ def test_adam_matches_torch(kw):
         for pa, pb in zip(a, b):
             torch.testing.assert_close(pa, pb, rtol=1e-5, atol=2e-6)    # parameters ~ N(0, 1): a few ulps
     for pa, pb in zip(a[1:], b[1:]):
-        torch.testing.assert_close(mine.state[pa]['exp_avg'], ref.state[pb]['exp_avg'], rtol=1e-4, atol=1e-6)
-        torch.testing.assert_close(mine.state[pa]['exp_avg_sq'], ref.state[pb]['exp_avg_sq'], rtol=1e-4, atol=1e-8)
+        # measured on an MI355X with the complements rounded once from double: largest error 0 -- both moments are bitwise
+        # torch's after 7 steps, for both hyper-parameter sets (1.0f - (float)beta2 put 1.3e-5 on exp_avg_sq).  20 x 0 is no
+        # tolerance, and equal bits with another implementation are not a contract: what is left is the rounding bound of
+        # two correct fp32 steps (tests/adam_spec.py), 3 u of V each and step (u = 2^-24; every term of V is positive, so
+        # the bound is relative and needs no atol), u |M| + (1 - beta1) 2u (|g| + |m|) each and step with |g| < 30
+        torch.testing.assert_close(mine.state[pa]['exp_avg'], ref.state[pb]['exp_avg'], rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(mine.state[pa]['exp_avg_sq'], ref.state[pb]['exp_avg_sq'], rtol=1e-6, atol=0.0)
         assert int(mine.state[pa]['step']) == 7 == int(ref.state[pb]['step'])
     assert set(mine.state_dict()['state'][1].keys()) == {'step', 'exp_avg', 'exp_avg_sq'}
 

@@ -30,13 +30,16 @@ struct AdamArgs {
     int n_tensors;
     int dbg;                                  // -DTIPK_DEBUG builds: 1 no ticket, 2 no bias-correction arithmetic, 4 no stores
     double lr, beta1, beta2, eps, weight_decay;
+    float c1, c2;                             // (float)(1 - beta1), (float)(1 - beta2): the host rounds the double difference
 };
 
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float b1, float b2, float wd, float step_size,
-                                         float inv_sqrt_bc2, float eps) {
+// c1, c2: (float)(1 - beta1), (float)(1 - beta2), rounded ONCE from the double difference like every other constant here
+// (1.0f - (float)beta2 is 216 u off 1 - beta2 for beta2 = 0.999, u = 2^-24: a bias of 1.3e-5 on every exp_avg_sq).
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float c1, float b2, float c2, float wd,
+                                         float step_size, float inv_sqrt_bc2, float eps) {
     if (wd != 0.0f) g = fmaf(wd, p, g);                       // L2 form (torch.optim.Adam, not AdamW)
-    m = fmaf(1.0f - b1, g - m, m);                            // exp_avg.lerp_(grad, 1 - beta1)
-    v = fmaf(1.0f - b2, g * g, b2 * v);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    m = fmaf(c1, g - m, m);                                   // exp_avg.lerp_(grad, 1 - beta1)
+    v = fmaf(c2, g * g, b2 * v);                              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
     p -= step_size * (m / denom);
 }
@@ -67,7 +70,8 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
     float* __restrict__ v = a.v[ti];
     const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                        reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-    const float b1 = (float)a.beta1, b2 = (float)a.beta2, wd = (float)a.weight_decay, eps = (float)a.eps;
+    const float b2 = (float)a.beta2, wd = (float)a.weight_decay, eps = (float)a.eps;
+    const float c1 = a.c1, c2 = a.c2;
     float pr[4], gr[4], mr[4], vr[4];
     const bool full = vec && i0 + 4 <= n;
     if (full) {
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
     __syncthreads();
     const float step_size = sc[0], inv_sqrt_bc2 = sc[1];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) adam_one(pr[j], gr[j], mr[j], vr[j], b1, b2, wd, step_size, inv_sqrt_bc2, eps);
+    for (int j = 0; j < 4; ++j) adam_one(pr[j], gr[j], mr[j], vr[j], c1, b2, c2, wd, step_size, inv_sqrt_bc2, eps);
     if (TIPK_DBG(a.dbg & 4) && pr[0] != 12345.f) {}
     else if (full) {
         *reinterpret_cast<float4*>(p + i0) = *reinterpret_cast<const float4*>(pr);
@@ -142,6 +146,7 @@ extern "C" int tipk_adam_step(int n_tensors, float* const* params, const float* 
         a.ticket = reinterpret_cast<unsigned long long*>(ticket);
         a.dbg = TIPK_DBG(tipk_option(TIPK_OPT_DM_DEBUG));
         a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+        a.c1 = (float)(1.0 - beta1); a.c2 = (float)(1.0 - beta2);
         int64_t wgs = 0;
         for (; i <= last && a.n_tensors < ADAM_MAX_TENSORS; ++i) {
             if (numel[i] == 0) continue;
