@@ -1222,6 +1222,67 @@ int     tipk_rgcn_attribution(const float* h, int64_t ld_h, int64_t n_nodes, int
                               float* out_contrib, int32_t* out_src, int32_t* out_rel /* [n_q x k] */,
                               float* out_own, float* out_sum /* [n_q] */, void* workspace, tipk_stream_t stream);
 
+/* 4k. Fold-in: embed drugs that are NOT nodes of the training graph, with the trained model frozen (serving; no reference
+ *     call site -- one destination row of MyRGCNConv2, src/layers.py:157-188, twice, behind the P -> D mean of
+ *     MyHierarchyConv, src/layers.py:196-247).
+ *
+ *   A row of an R-GCN layer's output depends on the node's own input row and its in-neighbours' input rows only, so the
+ *   embedding of a new drug needs nothing but the tables the encoder already produces: h_prot [n_prot x p] (the P-P encoder's
+ *   output, row stride ld_h_prot), x0 [n_nodes x d0] (the mixed drug features, ld_x0) and h1 = relu(rgcn1(x0)) [n_nodes x d1]
+ *   (ld_h1); and the parameters hgcn_w [p x pd] dense, basis1 [n_bases x d0 x d1], root1 [d0 x d1], basis2 [n_bases x d1 x
+ *   d2], root2 [d1 x d2] dense, att1 / att2 [n_rel x n_bases] (row strides ld_att1 / ld_att2).  d0 = ne + pd with cat != 0,
+ *   d0 = ne = pd with cat == 0.
+ *   Per new drug m of n_new, all DEVICE: xd [n_new x ne] (ld_xd), its normalised drug-feature embedding (zeros: none);
+ *   targets, CSR: tgt_ptr int64 [n_new + 1], tgt_prot int32 [n_tgt] in [0, n_prot); recorded interactions, CSR: in_ptr int64
+ *   [n_new + 1], in_src int32 [n_edges] (an EXISTING drug in [0, n_nodes)), in_rel int32 [n_edges] in [0, n_rel): each entry
+ *   is one in-edge partner -> new drug; duplicates count.  Keeping the ids in range is the caller's contract
+ *   (tip_amd.ops.drug_fold_in checks each tensor once); tgt_ptr and in_ptr are clamped to [0, n_tgt] and [0, n_edges].
+ *   With t_m targets and deg_m interactions:
+ *     pd_m  = (1/max(t_m,1) * sum_{q in targets} h_prot[q]) hgcn_w
+ *     x0_m  = cat(xd_m, pd_m)  |  xd_m + pd_m
+ *     h1_m  = relu( 1/max(deg_m,1) * sum_e sum_b att1[rel_e,b] * (x0[src_e] basis1[b]) + x0_m root1 )
+ *     z_m   =       1/max(deg_m,1) * sum_e sum_b att2[rel_e,b] * (h1[src_e] basis2[b]) + h1_m root2
+ *   -> x0_new [n_new x d0], h1_new [n_new x d1], z_new [n_new x d2] (row strides given).  The existing drugs' rows are held
+ *   fixed: the new edges point INTO the new drug only.
+ *   Arithmetic, fp32, AGGREGATE FIRST: A1[b,:] = sum_e att1[rel_e,b] * x0[src_e,:] and A2[b,:] = sum_e att2[rel_e,b] *
+ *   h1[src_e,:], both in one walk over the segment: per drug this is the product att[rel_e,:]^T [B x deg] . x[src_e,:]
+ *   [deg x d] with the edges as K, run on v_mfma_f32_16x16x4_f32 four edges at a time in segment order -- one exact fmaf
+ *   chain per entry along the segment, from 0.0f.  Then the contraction [drugs x n_bases d_in] . [n_bases d_in x d_out] on the
+ *   same instruction (an exact fmaf chain per output; the K range is dealt to 8 wavefronts in steps of 16 and their partial
+ *   sums are added as ((w0+w1)+(w2+w3))+((w4+w5)+(w6+w7))); then one multiply by the correctly rounded
+ *   1.0f / (float)max(deg_m, 1), plus the root chain (i ascending, from 0.0f).  The target mean: a chain of adds in segment
+ *   order, one multiply by 1.0f / (float)max(t_m, 1), then fmaf over j ascending.
+ *   No atomics: every row is BITWISE repeatable and does not depend on which other drugs share the call.
+ *   Work: ONE launch, a workgroup of 512 threads per tile of up to 16 new drugs (16 from 4 096 drugs on; fewer per tile in a
+ *   smaller call, down to one below 257, so that few drugs with long lists still spread over the chip); each basis is read
+ *   once per workgroup; no per-edge or per-drug temporary leaves the chip (LDS images of at most 16 bases at a time; with
+ *   more, the segment is walked once per 16 bases).  A long segment is walked by four wavefronts side by side (each owns a
+ *   share of the columns) and holds up half of its own tile only.
+ *   Supported: 1 <= ne, d0 <= 128; 1 <= p, pd, d1, d2, n_bases <= 64 (any width); 1 <= n_rel <= 2^24; n_nodes, n_prot, n_tgt,
+ *   n_edges below 2^31.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes, n_prot, n_rel, n_bases or
+ *   a width < 1, ne != pd with cat == 0, a row stride shorter than its row, a NULL required pointer (with n_new > 0:
+ *   everything but `workspace`, and tgt_prot / in_src / in_rel when their list is empty); then TIPK_EUNSUPPORTED outside the
+ *   supported range; n_new == 0 is TIPK_OK with no launch and nothing written.
+ *   workspace: tipk_drug_fold_in_workspace_bytes(...) bytes (-1: unsupported); 0 today -- every sum ends inside its
+ *   workgroup -- and `workspace` may then be NULL.
+ *   Nothing lives in host memory: the entry does NOT synchronise or allocate and may be captured into a hipGraph.
+ */
+int     tipk_drug_fold_in_supported(int64_t n_nodes, int64_t n_prot, int64_t n_rel, int n_bases, int ne, int p, int pd,
+                                    int d1, int d2, int cat);
+int64_t tipk_drug_fold_in_workspace_bytes(int64_t n_nodes, int64_t n_prot, int64_t n_rel, int n_bases, int ne, int p, int pd,
+                                          int d1, int d2, int cat, int64_t n_new, int64_t n_edges);   /* -1 unsupported; may be 0 */
+int     tipk_drug_fold_in(const float* h_prot, int64_t ld_h_prot, int64_t n_prot, int p, const float* hgcn_w, int pd,
+                          const float* x0, int64_t ld_x0, const float* h1, int64_t ld_h1, int64_t n_nodes,
+                          const float* basis1, const float* att1, int64_t ld_att1, const float* root1,
+                          const float* basis2, const float* att2, int64_t ld_att2, const float* root2,
+                          int64_t n_rel, int n_bases, int d1, int d2,
+                          const float* xd, int64_t ld_xd, int ne, int cat,
+                          const int64_t* tgt_ptr /* [n_new+1] */, const int32_t* tgt_prot, int64_t n_tgt,
+                          const int64_t* in_ptr /* [n_new+1] */, const int32_t* in_src, const int32_t* in_rel, int64_t n_edges,
+                          int64_t n_new, float* x0_new, int64_t ld_x0_new, float* h1_new, int64_t ld_h1_new,
+                          float* z_new, int64_t ld_z_new, void* workspace, tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

@@ -34,6 +34,7 @@ ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 Explanation = namedtuple('Explanation', ['logit', 'offset', 'own', 'neighbours', 'contribution', 'partner', 'relation', 'degree'])
+NewDrugs = namedtuple('NewDrugs', ['x0', 'h', 'z', 'degree', 'n_targets'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
@@ -742,6 +743,17 @@ class FMEncoder(nn.Module):
             h = self.rgcn1(x0, dd_edge_index, dd_edge_type, dd_range_list, fuse_relu=True)
             return h, self.rgcn2(h, dd_edge_index, dd_edge_type, dd_range_list)
 
+    def fold_in_tables(self, x_drug, dd_edge_index, dd_edge_type, dd_range_list, d_norm,
+                       x_prot, pp_edge_index, dp_edge_index, dp_range_list):
+        """`forward`'s arguments -> (h_prot_all, x0, h) under no_grad: the tables a drug outside the graph is embedded from
+        (`ops.drug_fold_in`, `TIP.embed_new_drugs`).  h_prot_all: the P-P encoder's output for EVERY protein (the un-pruned
+        `PPEncoder.forward`: a new drug may target a protein no training drug targets); x0: the mixed drug features; h =
+        relu(rgcn1(x0)), the input of the last layer."""
+        with torch.no_grad():
+            h_prot_all = self.pp_encoder(x_prot, pp_edge_index)
+            x0 = self.mixed_drug_features(x_drug, d_norm, x_prot, pp_edge_index, dp_edge_index, dp_range_list)
+            return h_prot_all, x0, self.rgcn1(x0, dd_edge_index, dd_edge_type, dd_range_list, fuse_relu=True)
+
     def mixed_drug_features(self, x_drug, d_norm, x_prot, pp_edge_index, dp_edge_index, dp_range_list):
         """The input of the D-D layers (src/layers.py:522-539): P-P GCN x2 -> P -> D mean -> dense map, drug embedding /
         d_norm, cat | add.  (The part of the step a relation-sharded run repeats on every rank.)"""
@@ -1213,6 +1225,24 @@ def _rank_result(order, r, s, et, n_rel, ks):
     return RankReport(rank, logit, **rank_report(rank, et, n_rel, ks))
 
 
+def _csr_of_lists(lists, width, limits, names, what):
+    """A list of per-row lists of `width`-tuples (bare ints for width 1) -> (ptr int64 [len + 1], then `width` int32 id
+    tensors) on the host; ValueError unless column c holds ints in [0, limits[c]) -- `names[c]` says what it is."""
+    ptr, cols = [0], [[] for _ in range(width)]
+    for row in lists:
+        for item in (row if row is not None else ()):
+            item = (item,) if width == 1 else tuple(item)
+            if len(item) != width:
+                raise ValueError('%s: entries of %d ids expected, got %r' % (what, width, item))
+            for c in range(width):
+                v = int(item[c])
+                if v < 0 or v >= limits[c]:
+                    raise ValueError('%s: %s id out of range: %d for %d' % (what, names[c], v, limits[c]))
+                cols[c].append(v)
+        ptr.append(len(cols[0]))
+    return (torch.tensor(ptr, dtype=torch.int64),) + tuple(torch.tensor(c, dtype=torch.int32) for c in cols)
+
+
 def _ids_at(pos, lookup, first=None):
     """Positions a kernel returned -> the int64 ids `lookup` holds there; padding (pos < 0) stays -1.  first: the offset of
     each row's list in `lookup` (CSR), for positions that count inside a row's list."""
@@ -1634,6 +1664,61 @@ class TIP(nn.Module):
             in_ptr = ops.in_edges_by_node(d.dd_train_idx, d.dd_train_range, h.shape[0])[0]
             return Explanation(logit, offset, own, total, c, src.to(torch.int64), rel.to(torch.int64),
                                in_ptr[node + 1] - in_ptr[node])
+
+    def embed_new_drugs(self, targets, interactions=None, features=None, d_norm=None):
+        """Embed drugs that are NOT nodes of the training graph (extension): a compound known by its protein targets and
+        perhaps a few recorded interactions, with the trained model frozen (`ops.drug_fold_in`: one `tipk_drug_fold_in`
+        launch for all M drugs, no per-edge temporary).
+        targets: a list of M lists of protein ids (possibly empty).  interactions: None, or a list of M lists of (partner
+        drug id, side-effect id): each is one in-edge partner -> new drug; partners are EXISTING drugs; duplicates count.
+        features: None = no drug feature (xd = 0), else dense or sparse [M, n_drug_feat]; xd = features @ encoder.embed /
+        d_norm[:, None] (torch ops).  d_norm [M]: defaults to ones.
+        A row of an R-GCN layer depends on the node's own input row and its in-neighbours' rows only, so the new rows come
+        from the tables of `FMEncoder.fold_in_tables`: the model is RE-ENCODED with its current parameters (under no_grad);
+        `self.embeddings` is not overwritten.
+        The approximation: the existing drugs' embeddings are held fixed, as if the new edges were directed INTO the new
+        drug only -- neither their degrees nor their neighbourhoods change, and new drugs do not see each other.
+        -> NewDrugs(x0 [M, d0], h [M, n_hid1], z [M, n_hid2], degree int64 [M], n_targets int64 [M]) on the model's
+        device.  The decoders take z as an argument, so with
+            z_ext = torch.cat([model.embeddings, new.z])
+        new drug i is node n_drug + i of `model.decoder(z_ext, idx, et)` and of the decoders' other queries.
+        ValueError for an id out of range; NotImplementedError for a relation-sharded model, a layer with a bias, or widths
+        `tipk_drug_fold_in_supported` refuses.  Both `mod`s."""
+        _refuse_sharded(self.shard, 'new drugs')
+        d, enc = self.data, self.encoder
+        m = len(targets)
+        if interactions is None:
+            interactions = [()] * m
+        if len(interactions) != m:
+            raise ValueError('interactions: one list per new drug expected, got %d for %d' % (len(interactions), m))
+        tgt = _csr_of_lists(targets, 1, (d.n_prot,), ('protein',), 'targets')
+        inter = _csr_of_lists(interactions, 2, (d.n_drug, d.n_dd_et), ('partner drug', 'side-effect'), 'interactions')
+        r1, r2 = enc.rgcn1, enc.rgcn2
+        if r1.bias is not None or r2.bias is not None:
+            raise NotImplementedError('embed_new_drugs folds into bias-free R-GCN layers')
+        ne, cat = enc.embed.shape[1], enc.mod == 'cat'
+        if not ops.drug_fold_in_supported(d.n_drug, d.n_prot, d.n_dd_et, r1.num_bases, ne, enc.pp_encoder.out_dim,
+                                          enc.hgcn.out_dim, r1.out_channels, r2.out_channels, cat):
+            raise NotImplementedError('embed_new_drugs: tipk_drug_fold_in does not take these widths (include/tipk.h 4k)')
+        dev = self.embeddings.device
+        with torch.no_grad():
+            if features is None:
+                xd = torch.zeros((m, ne), dtype=torch.float32, device=dev)
+            else:
+                features = torch.as_tensor(features).to(dev)
+                if features.dim() != 2 or tuple(features.shape) != (m, enc.embed.shape[0]):
+                    raise ValueError('features: [%d, %d] expected, got %s' % (m, enc.embed.shape[0], tuple(features.shape)))
+                mm = torch.sparse.mm if features.is_sparse else torch.mm
+                xd = mm(features.to(torch.float32), enc.embed.detach())
+                if d_norm is not None:
+                    xd = xd / torch.as_tensor(d_norm).to(device=dev, dtype=torch.float32).reshape(m, 1)
+            h_prot, x0, h = enc.fold_in_tables(d.d_feat, d.dd_train_idx, d.dd_train_et, d.dd_train_range, d.d_norm,
+                                               d.p_feat, d.pp_train_indices, d.dp_edge_index, d.dp_range_list)
+            tgt, inter = tuple(t.to(dev) for t in tgt), tuple(t.to(dev) for t in inter)
+            x0n, hn, zn = ops.drug_fold_in(h_prot, enc.hgcn.weight.detach(), x0, h,
+                                           (r1.basis.detach(), r1.att.detach(), r1.root.detach()),
+                                           (r2.basis.detach(), r2.att.detach(), r2.root.detach()), xd.contiguous(), tgt, inter, cat)
+            return NewDrugs(x0n, hn, zn, inter[0][1:] - inter[0][:-1], tgt[0][1:] - tgt[0][:-1])
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

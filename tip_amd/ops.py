@@ -1678,6 +1678,74 @@ def rgcn_edge_attribution(h, basis, att, root, in_edges, q_node, probe, k):
     return contrib, src, rel, own, total
 
 
+def drug_fold_in_supported(n_nodes, n_prot, n_rel, n_bases, ne, p, pd, d1, d2, cat):
+    """Whether `drug_fold_in` takes these sizes (include/tipk.h section 4k)."""
+    return bool(lib().tipk_drug_fold_in_supported(int(n_nodes), int(n_prot), int(n_rel), int(n_bases), int(ne), int(p), int(pd),
+                                                  int(d1), int(d2), int(bool(cat))))
+
+
+def drug_fold_in(h_prot, hgcn_w, x0, h1, layer1, layer2, xd, targets, interactions, cat):
+    """x0, h1 and z rows of M drugs that are no node of the graph, from the frozen model's tables (include/tipk.h section 4k;
+    one launch, no per-edge or [M, B d] temporary).
+
+    h_prot [n_prot, p], x0 [N, d0], h1 [N, d1] (row strides free), hgcn_w [p, pd]; layer1 = (basis1 [B, d0, d1], att1 [R, B],
+    root1 [d0, d1]), layer2 = (basis2 [B, d1, d2], att2 [R, B], root2 [d1, d2]); xd [M, ne]: fp32 device tensors; d0 = ne + pd
+    with cat, else ne = pd = d0.  targets = (tgt_ptr int64 [M + 1], tgt_prot int32 [T]), interactions = (in_ptr int64
+    [M + 1], in_src int32 [E], in_rel int32 [E]): CSR lists per new drug, on the device; each interaction is an in-edge from
+    the existing drug in_src under relation in_rel, duplicates count.
+    -> (x0_new [M, d0], h1_new [M, d1], z_new [M, d2]) float32.  Bitwise repeatable, row by row whatever else is in the call.
+    Does not synchronise (a first call checks the ids of `targets` and `interactions` once per tensor: IndexError)."""
+    basis1, att1, root1 = layer1
+    basis2, att2, root2 = layer2
+    h_prot, x0, h1, att1, att2, xd = _f32c(h_prot), _f32c(x0), _f32c(h1), _f32c(att1), _f32c(att2), _f32c(xd)
+    hgcn_w, basis1, root1, basis2, root2 = (_f32c(t).contiguous() for t in (hgcn_w, basis1, root1, basis2, root2))
+    tgt_ptr, tgt_prot = targets
+    in_ptr, in_src, in_rel = interactions
+    require_device(h_prot, hgcn_w, x0, h1, basis1, att1, root1, basis2, att2, root2, xd, tgt_ptr, tgt_prot, in_ptr, in_src, in_rel)
+    if h_prot.dim() != 2 or hgcn_w.dim() != 2 or x0.dim() != 2 or h1.dim() != 2 or xd.dim() != 2 or \
+            hgcn_w.shape[0] != h_prot.shape[1] or x0.shape[0] != h1.shape[0]:
+        raise _lib.TipkError('drug_fold_in: h_prot [n_prot, p], hgcn_w [p, pd], x0 [N, d0], h1 [N, d1], xd [M, ne] expected, got '
+                             '%s, %s, %s, %s, %s' % tuple(tuple(t.shape) for t in (h_prot, hgcn_w, x0, h1, xd)))
+    (n_prot, p), pd, (n, d0), d1, (n_new, ne) = h_prot.shape, hgcn_w.shape[1], x0.shape, h1.shape[1], xd.shape
+    cat = bool(cat)
+    if d0 != (ne + pd if cat else ne) or (not cat and ne != pd):
+        raise _lib.TipkError('drug_fold_in: d0 = ne + pd (cat) or d0 = ne = pd (add) expected, got d0 %d, ne %d, pd %d, cat %s'
+                             % (d0, ne, pd, cat))
+    if basis1.dim() != 3 or basis2.dim() != 3 or att1.dim() != 2 or tuple(basis1.shape[1:]) != (d0, d1) or \
+            basis2.shape[:2] != (basis1.shape[0], d1) or tuple(root1.shape) != (d0, d1) or \
+            tuple(root2.shape) != tuple(basis2.shape[1:]) or att1.shape[1] != basis1.shape[0] or att2.shape != att1.shape:
+        raise _lib.TipkError('drug_fold_in: basis1 [B, %d, %d], att1 [R, B], root1 [%d, %d], basis2 [B, %d, d2], att2 [R, B], '
+                             'root2 [%d, d2] expected, got %s, %s, %s, %s, %s, %s'
+                             % ((d0, d1, d0, d1, d1, d1) + tuple(tuple(t.shape) for t in (basis1, att1, root1, basis2, att2, root2))))
+    n_bases, d2, n_rel = basis1.shape[0], basis2.shape[2], att1.shape[0]
+    if tgt_ptr.dtype != torch.int64 or tgt_prot.dtype != torch.int32 or tgt_ptr.numel() != n_new + 1 or tgt_prot.dim() != 1:
+        raise _lib.TipkError('drug_fold_in: targets = (int64 [%d], int32 [T]) expected' % (n_new + 1))
+    if in_ptr.dtype != torch.int64 or in_src.dtype != torch.int32 or in_rel.dtype != torch.int32 or \
+            in_ptr.numel() != n_new + 1 or in_src.dim() != 1 or in_src.shape != in_rel.shape:
+        raise _lib.TipkError('drug_fold_in: interactions = (int64 [%d], int32 [E], int32 [E]) expected' % (n_new + 1))
+    if h_prot.stride(0) < p or x0.stride(0) < d0 or h1.stride(0) < d1 or att1.stride(0) < n_bases or att2.stride(0) < n_bases \
+            or xd.stride(0) < ne:
+        h_prot, x0, h1, att1, att2, xd = (t.contiguous() for t in (h_prot, x0, h1, att1, att2, xd))
+    _range_checked(tgt_prot, n_prot, 'targets protein')
+    _range_checked(in_src, n, 'interactions partner')
+    _range_checked(in_rel, n_rel, 'interactions relation')
+    dev = x0.device
+    tgt_ptr, tgt_prot, in_ptr, in_src, in_rel = (t.contiguous() for t in (tgt_ptr, tgt_prot, in_ptr, in_src, in_rel))
+    x0_new = torch.empty((n_new, d0), dtype=torch.float32, device=dev)
+    h1_new = torch.empty((n_new, d1), dtype=torch.float32, device=dev)
+    z_new = torch.empty((n_new, d2), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib().tipk_drug_fold_in_workspace_bytes(n, n_prot, n_rel, n_bases, ne, p, pd, d1, d2, int(cat), n_new,
+                                                           in_src.numel()))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes > 0 else None
+    check(lib().tipk_drug_fold_in(ptr(h_prot), h_prot.stride(0), n_prot, p, ptr(hgcn_w), pd, ptr(x0), x0.stride(0), ptr(h1),
+                                  h1.stride(0), n, ptr(basis1), ptr(att1), att1.stride(0), ptr(root1), ptr(basis2), ptr(att2),
+                                  att2.stride(0), ptr(root2), n_rel, n_bases, d1, d2, ptr(xd), max(xd.stride(0), ne), ne, int(cat),
+                                  ptr(tgt_ptr), ptr(tgt_prot), tgt_prot.numel(), ptr(in_ptr), ptr(in_src), ptr(in_rel),
+                                  in_src.numel(), n_new, ptr(x0_new), d0, ptr(h1_new), d1, ptr(z_new), d2, ptr(ws),
+                                  stream_ptr(dev)), 'tipk_drug_fold_in')
+    return x0_new, h1_new, z_new
+
+
 _DET_WS = {}
 
 
