@@ -738,14 +738,45 @@ int tipk_distmult_fwd(const float* z, int64_t n_nodes, int k, const float* rel_w
  * lists each pair in both directions ([u<v half | mirrored half], src/utils.py:35-65) the host may give
  * the first half weight 2 and the mirrored half weight 0 (identical scores and gradients): the objective
  * and all gradients are unchanged, a quarter of the work disappears.  TIP's triples are grouped by relation
- * (src/utils.py:57-63), so the host builds this once; with it (and k a power of two in 4..64,
- * 2*n_nodes*(k+4)*4 B <= 150 KB) the LDS-resident fast kernel runs, otherwise the generic one. */
+ * (src/utils.py:57-63), so the host builds this once; with it, z and rel_w on 16-byte addresses, k a power of two in 4..64,
+ * n_nodes <= 65 535 and the kernel's LDS images inside 158 KB -- per node (k + 1) 64-bit words of the fixed-point d z image
+ * and (k + 4) floats of the z image (each image rounded up to 16 bytes), plus 16 k + 16 floats of reduction space and 16 KB
+ * of staged ids: n_nodes <= 2 015 for k = 4, 668 for k = 16, 178 for k = 64 -- the LDS-resident task kernel runs,
+ * otherwise the generic one (tipk_distmult_route names the route; ask it, do not copy this).
+ *
+ * Non-finite rule of tipk_distmult_bwd.  No element of g_z / g_w that the exact gradient makes NaN or infinite comes out
+ * finite.  The generic routes add float terms: what is finite in exact arithmetic (and in fp32 range) stays a rounded
+ * number.  The task route scales its fixed-point d z image by a bound, 4 max|z| max|w| sum |g_score| over the positions of
+ * ONE workgroup; where that bound is not a finite float -- a NaN or an infinity anywhere in z or rel_w, or in a g_score of
+ * that workgroup's tasks, or finite g_score whose magnitudes sum past FLT_MAX -- the workgroup adds NaN to EVERY element of
+ * g_z: it poisons more than the exact gradient does, never less (the fused objective does the same for z and rel_w).
+ * g_w is a float sum on every route. */
 int tipk_distmult_bwd(const float* g_score, const float* score,
                       const float* z, int64_t n_nodes, int k, const float* rel_w, int64_t n_rel,
                       const void* idx_u, const void* idx_v, int idx_bytes,
                       const void* edge_type, int et_bytes, int64_t n_triples,
                       int sigmoid, const int32_t* tasks, int64_t n_tasks,
                       float* g_z, float* g_w, tipk_stream_t stream);
+
+/* The route of tipk_distmult_bwd / tipk_distmult_loss for a shape: a pure host query, and the ONE decision the two entries
+ * take themselves (options apply: "dm_task_kernel").
+ *   mode          TIPK_DM_MODE_BWD, _LOSS (g_z / g_w given) or _LOSS_NOGRAD (objective only)
+ *   has_tasks     a task table is passed (non-NULL, 0 < n_tasks < 2^31);  has_workspace: tipk_distmult_loss's workspace
+ *   idx_bytes     4, 8, or 2 (packed pairs, the loss only);  aligned16: z and rel_w both on 16-byte addresses
+ * -> TIPK_DM_ROUTE_GENERIC_GLOBAL  one thread per triple, d z by global float atomics (n_nodes k 4 B > 96 KB, or no gradients)
+ *    TIPK_DM_ROUTE_GENERIC_LDS     the same kernel, d z in a per-workgroup float LDS image (n_nodes k 4 B <= 96 KB)
+ *    TIPK_DM_ROUTE_TASK            distmult_task_kernel: tasks, z and the fixed-point d z image in LDS
+ *    TIPK_DM_ROUTE_OBJECTIVE       distmult_objective_kernel (the loss with tasks, a workspace and k in {4, 8, 16})
+ *    TIPK_EUNSUPPORTED             packed pairs outside the objective kernel;  TIPK_EINVAL: no such mode / id width / shape.
+ * (tipk_distmult_loss_store additionally needs a workspace route: TIPK_EUNSUPPORTED on the generic ones.) */
+#define TIPK_DM_MODE_BWD 0
+#define TIPK_DM_MODE_LOSS 1
+#define TIPK_DM_MODE_LOSS_NOGRAD 2
+#define TIPK_DM_ROUTE_GENERIC_GLOBAL 0
+#define TIPK_DM_ROUTE_GENERIC_LDS 1
+#define TIPK_DM_ROUTE_TASK 2
+#define TIPK_DM_ROUTE_OBJECTIVE 3
+int tipk_distmult_route(int64_t n_nodes, int k, int mode, int has_tasks, int has_workspace, int idx_bytes, int aligned16);
 
 /* Fused training objective of TIP.forward (src/layers.py:335-340, K9+K10): one pass over the
  * positive triples and their negatives (same relation per position):

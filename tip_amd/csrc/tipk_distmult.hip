@@ -249,6 +249,7 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
         wmax = block_max_1024(wmax, red, t);
     }
     double scale = 1.0;
+    float gbound = 0.f;                                       // MODE 0: this workgroup's bound (non-finite: see the flush)
     if (want_grad) {
         // bound on sum |contribution| into any element: every position adds <= 4 |q| zmax wmax with
         // sum |q| <= 1 (fused objective: |q| <= 1/n each) or <= sum |g| over this workgroup's positions
@@ -258,6 +259,7 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
             for (int task = blockIdx.x; task < n_tasks; task += gridDim.x)
                 for (int p = tasks[4 * task + 1] + t; p < tasks[4 * task + 2]; p += 1024) sg += fabsf(g_score[p]);
             bound *= block_sum_1024(sg, red, t);
+            gbound = bound;
         }
         int ex = 60;
         if (bound > 0.f && bound < 3.0e38f) ex = 60 - (ilogbf(bound) + 1);
@@ -445,7 +447,13 @@ __global__ __launch_bounds__(1024) void distmult_task_kernel(
     if (want_grad) {
         __syncthreads();
         const double inv_scale = 1.0 / nonfinite_scale(scale, zmax, wmax);
-        for (int i = t; i < n_nodes * k; i += 1024) {
+        // MODE 0: a bound that is not a finite number -- a NaN or an infinity in z, w or this workgroup's g_score, or finite
+        // g_score whose sum of magnitudes overflows -- has no fixed-point scale, and the integer image holds converted
+        // NaNs (finite garbage, possibly 0).  The same device as `nonfinite_scale`, extended to the g_score sum: this
+        // workgroup adds NaN to EVERY element of d z (tipk.h section 4, "non-finite rule").  d w is a float sum already.
+        const bool poisoned = MODE == 0 && !(gbound <= 3.402823466e38f);       // (workgroup-uniform)
+        for (int i = t; poisoned && i < n_nodes * k; i += 1024) atomicAdd(g_z + i, __builtin_nanf(""));
+        for (int i = t; !poisoned && i < n_nodes * k; i += 1024) {
             const int r = i / k, c = i - r * k;
             const long long a = (long long)gzl[r * lg + c];
             if (TIPK_DBG(dbg & 4)) continue;                           // debug builds: no flush of the d z image
@@ -734,6 +742,32 @@ inline bool task_path_ok(int64_t n_nodes, int k, int64_t* lds_bytes) {
     return *lds_bytes <= 158 * 1024;
 }
 
+constexpr int64_t LDS_GZ_LIMIT = 96 * 1024;              // generic kernel: the float d z image lives in LDS up to here
+
+// THE route decision of tipk_distmult_bwd and tipk_distmult_loss / _loss_store (include/tipk.h: tipk_distmult_route
+// exports it).  mode: TIPK_DM_MODE_*; has_tasks: a usable task table (non-NULL, 0 < n_tasks < 2^31); aligned16: z and rel_w
+// on 16-byte addresses.  *lds_bytes: the dynamic LDS of the route's launch (task kernel, generic LDS image).
+int distmult_route(int64_t n_nodes, int k, int mode, bool has_tasks, bool has_ws, int idx_bytes, bool aligned16,
+                   int64_t* lds_bytes) {
+    *lds_bytes = 0;
+    if (n_nodes < 0 || k <= 0 || mode < TIPK_DM_MODE_BWD || mode > TIPK_DM_MODE_LOSS_NOGRAD) return TIPK_EINVAL;
+    if (idx_bytes != 4 && idx_bytes != 8 && !(idx_bytes == 2 && mode != TIPK_DM_MODE_BWD)) return TIPK_EINVAL;
+    const bool tasks_ok = has_tasks && aligned16 && k % 4 == 0;
+    if (idx_bytes == 2 && !tasks_ok) return TIPK_EUNSUPPORTED;       // packed pairs: the objective kernel only
+    if (tasks_ok && task_path_ok(n_nodes, k, lds_bytes)) {
+        if (mode == TIPK_DM_MODE_BWD) return TIPK_DM_ROUTE_TASK;
+        const bool obj = has_ws && (k == 4 || k == 8 || k == 16);
+        if (idx_bytes == 2 && !obj) return TIPK_EUNSUPPORTED;
+        if (obj && (idx_bytes == 2 || !tipk_option(TIPK_OPT_DM_TASK_KERNEL))) return TIPK_DM_ROUTE_OBJECTIVE;
+        return TIPK_DM_ROUTE_TASK;
+    }
+    if (idx_bytes == 2) return TIPK_EUNSUPPORTED;
+    *lds_bytes = n_nodes * k * (int64_t)sizeof(float);
+    if (mode != TIPK_DM_MODE_LOSS_NOGRAD && *lds_bytes <= LDS_GZ_LIMIT) return TIPK_DM_ROUTE_GENERIC_LDS;
+    *lds_bytes = 0;
+    return TIPK_DM_ROUTE_GENERIC_GLOBAL;
+}
+
 // ws layout (u64 words): [n_nodes*k] d z | [n_rel*k] d w | [1] loss | 3 doubles: the three scales.
 // Converts, ADDS into the outputs (same contract as the float path) and zeroes the words again, so the caller's
 // workspace is reusable without a memset.
@@ -804,14 +838,11 @@ int launch_objective(const float* z, int64_t n_nodes, int k, const float* w, int
     return launch_finalize(n_nodes, k, n_rel, loss_out, g_z, g_w, ws, st, store);
 }
 
-constexpr int64_t LDS_GZ_LIMIT = 96 * 1024;
-
 template <typename IT, typename ET, int V, int MODE>
 int launch_grad(const float* g_score, const float* score, const float* z, int64_t n_nodes, int k, const float* w,
                 const void* iu, const void* iv, const void* ju, const void* jv, const void* et, int64_t n, int sig,
-                float* loss_out, float* g_z, float* g_w, hipStream_t st) {
-    const int64_t lds_bytes = n_nodes * k * (int64_t)sizeof(float);
-    const bool use_lds = g_z && lds_bytes <= LDS_GZ_LIMIT;
+                float* loss_out, float* g_z, float* g_w, bool use_lds, hipStream_t st) {
+    const int64_t lds_bytes = n_nodes * k * (int64_t)sizeof(float);     // (use_lds: distmult_route said so)
     // enough workgroups to fill 256 CUs a few times over, but each long enough to amortise the
     // LDS image flush (n_nodes*k atomics)
     int64_t per_block = tipk_ceil_div(n, 1024);
@@ -835,9 +866,10 @@ int launch_grad(const float* g_score, const float* score, const float* z, int64_
     TIPK_RETURN_LAUNCH();
 }
 
-inline bool vec_ok(const float* z, const float* w, int k) {
-    return k % 4 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+inline bool aligned16(const float* z, const float* w) {
+    return (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
 }
+inline bool vec_ok(const float* z, const float* w, int k) { return k % 4 == 0 && aligned16(z, w); }
 
 }  // namespace
 
@@ -884,7 +916,11 @@ extern "C" int tipk_distmult_bwd(const float* g_score, const float* score, const
     hipStream_t st = (hipStream_t)stream;
     const bool vec = vec_ok(z, rel_w, k);
     int64_t lds_bytes = 0;
-    if (tasks && n_tasks > 0 && vec && n_tasks < 0x7fffffffLL && task_path_ok(n_nodes, k, &lds_bytes)) {
+    const int route = distmult_route(n_nodes, k, TIPK_DM_MODE_BWD, tasks && n_tasks > 0 && n_tasks < 0x7fffffffLL, false,
+                                     idx_bytes, aligned16(z, rel_w), &lds_bytes);
+    if (route < 0) return route;
+    const bool use_lds = route == TIPK_DM_ROUTE_GENERIC_LDS;
+    if (route == TIPK_DM_ROUTE_TASK) {
         if (idx_bytes == 8)
             return launch_tasks<int64_t, 0>(z, n_nodes, k, rel_w, n_rel, tasks, n_tasks, idx_u, idx_v, nullptr, nullptr,
                                             g_score, sigmoid, n_triples, nullptr, g_z, g_w, lds_bytes, st);
@@ -896,12 +932,18 @@ extern "C" int tipk_distmult_bwd(const float* g_score, const float* score, const
 #define CALL(IT, ET)                                                                                          \
     {                                                                                                         \
         if (vec) return launch_grad<IT, ET, 4, 0>(g_score, score, z, n_nodes, k, rel_w, idx_u, idx_v, nullptr, \
-                                                  nullptr, edge_type, n_triples, sigmoid, nullptr, g_z, g_w, st); \
+                                                  nullptr, edge_type, n_triples, sigmoid, nullptr, g_z, g_w, use_lds, st); \
         return launch_grad<IT, ET, 1, 0>(g_score, score, z, n_nodes, k, rel_w, idx_u, idx_v, nullptr, nullptr,    \
-                                         edge_type, n_triples, sigmoid, nullptr, g_z, g_w, st);                \
+                                         edge_type, n_triples, sigmoid, nullptr, g_z, g_w, use_lds, st);       \
     }
     TIPK_DISPATCH_IDX(CALL);
 #undef CALL
+}
+
+extern "C" int tipk_distmult_route(int64_t n_nodes, int k, int mode, int has_tasks, int has_workspace, int idx_bytes,
+                                   int aligned16) {
+    int64_t lds_bytes = 0;
+    return distmult_route(n_nodes, k, mode, has_tasks != 0, has_workspace != 0, idx_bytes, aligned16 != 0, &lds_bytes);
 }
 
 extern "C" int64_t tipk_distmult_workspace_bytes(int64_t n_nodes, int k, int64_t n_rel) {
@@ -923,13 +965,15 @@ static int distmult_loss_impl(const float* z, int64_t n_nodes, int k, const floa
     hipStream_t st = (hipStream_t)stream;
     const bool vec = vec_ok(z, rel_w, k);
     int64_t lds_bytes = 0;
-    if (idx_bytes == 2 && !(tasks && n_tasks > 0 && vec)) return TIPK_EUNSUPPORTED;
-    if (tasks && n_tasks > 0 && vec && n_tasks < 0x7fffffffLL && task_path_ok(n_nodes, k, &lds_bytes)) {
-        if (idx_bytes == 2 && !(ws && (k == 4 || k == 8 || k == 16) && n_nodes <= 65535)) return TIPK_EUNSUPPORTED;
-        if (ws && (k == 4 || k == 8 || k == 16) && (idx_bytes == 8 || idx_bytes == 4 || idx_bytes == 2) && n_nodes <= 0x7fffffffLL &&
-            (idx_bytes == 2 || !tipk_option(TIPK_OPT_DM_TASK_KERNEL)))
-            return launch_objective(z, n_nodes, k, rel_w, n_rel, tasks, n_tasks, pos_u, pos_v, neg_u, neg_v, idx_bytes,
-                                    n_triples, loss_out, g_z, g_w, ws, st, store);
+    const int route = distmult_route(n_nodes, k, g_z ? TIPK_DM_MODE_LOSS : TIPK_DM_MODE_LOSS_NOGRAD,
+                                     tasks && n_tasks > 0 && n_tasks < 0x7fffffffLL, ws != nullptr, idx_bytes,
+                                     aligned16(z, rel_w), &lds_bytes);
+    if (route < 0) return route;
+    const bool use_lds = route == TIPK_DM_ROUTE_GENERIC_LDS;
+    if (route == TIPK_DM_ROUTE_OBJECTIVE)
+        return launch_objective(z, n_nodes, k, rel_w, n_rel, tasks, n_tasks, pos_u, pos_v, neg_u, neg_v, idx_bytes,
+                                n_triples, loss_out, g_z, g_w, ws, st, store);
+    if (route == TIPK_DM_ROUTE_TASK) {
         if (store && !ws) return TIPK_EUNSUPPORTED;       // only the finalize launch of the workspace path can overwrite
         if (idx_bytes == 8)
             return launch_tasks<int64_t, 1>(z, n_nodes, k, rel_w, n_rel, tasks, n_tasks, pos_u, pos_v, neg_u, neg_v, nullptr,
@@ -939,13 +983,13 @@ static int distmult_loss_impl(const float* z, int64_t n_nodes, int k, const floa
                                             1, n_triples, loss_out, g_z, g_w, lds_bytes, st, ws, store);
         return TIPK_EINVAL;
     }
-    if (idx_bytes == 2 || store) return TIPK_EUNSUPPORTED;     // packed pairs / overwriting outputs: the workspace path only
+    if (store) return TIPK_EUNSUPPORTED;                       // overwriting outputs: the workspace path only
 #define CALL(IT, ET)                                                                                             \
     {                                                                                                            \
         if (vec) return launch_grad<IT, ET, 4, 1>(nullptr, nullptr, z, n_nodes, k, rel_w, pos_u, pos_v, neg_u, neg_v, \
-                                                  edge_type, n_triples, 1, loss_out, g_z, g_w, st);             \
+                                                  edge_type, n_triples, 1, loss_out, g_z, g_w, use_lds, st);    \
         return launch_grad<IT, ET, 1, 1>(nullptr, nullptr, z, n_nodes, k, rel_w, pos_u, pos_v, neg_u, neg_v,          \
-                                         edge_type, n_triples, 1, loss_out, g_z, g_w, st);                      \
+                                         edge_type, n_triples, 1, loss_out, g_z, g_w, use_lds, st);             \
     }
     TIPK_DISPATCH_IDX(CALL);
 #undef CALL
