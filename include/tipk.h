@@ -65,6 +65,8 @@ const char* tipk_build_id(void);
  *                            fits (section 4i; both routes return the same bits)
  *      "attribution_global"  1 = tipk_rgcn_attribution keeps the per-query table in the caller's workspace even where it fits
  *                            in LDS (section 4j; both routes return the same bits)
+ *      "partner_sum_global"  1 = tipk_distmult_partner_sum reads z rows from global memory even where the LDS image fits
+ *                            (section 4l; both routes return the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -1313,6 +1315,73 @@ int     tipk_drug_fold_in(const float* h_prot, int64_t ld_h_prot, int64_t n_prot
                           const int64_t* in_ptr /* [n_new+1] */, const int32_t* in_src, const int32_t* in_rel, int64_t n_edges,
                           int64_t n_new, float* x0_new, int64_t ld_x0_new, float* h1_new, int64_t ld_h1_new,
                           float* z_new, int64_t ld_z_new, void* workspace, tipk_stream_t stream);
+
+/* 4l. Partner sum: the expected number of UNRECORDED partners of a drug per side effect -- the marginal of the model over
+ *     the partner axis -- and the k side effects of every queried drug with the largest expectation (serving: the
+ *     liability profile of one drug, above all of a folded-in compound of 4k; no reference call site).
+ *
+ *       out_sum[q, j] = sum over the candidates c of  partner_w[c] * sigma(logit(r, u, c)),     u = q_drug[q], r = rel_ids[j]
+ *
+ *   Input, DEVICE: q_drug int32 [n_q], the queried drugs (entries may repeat); rel_ids int32 [n_sel], nullable: the
+ *   relations that are the COLUMNS of the result (entries may repeat); NULL: all relations, column j is relation j, and
+ *   n_sel must equal n_rel.  partner_w fp32 [n_nodes], nullable (NULL: every weight is 1), e.g. a co-prescription
+ *   frequency; finite and >= 0 is the caller's contract.  known_keys / known_ptr [n_rel + 1]: the relation-major lists of
+ *   4c, nullable together.
+ *   Candidates of cell (q, j): every drug c in [0, n_nodes) with c != u and partner_w[c] != 0 whose key u*n+c is NOT a key of
+ *   relation r.  ONLY THE FORWARD KEY u*n+c is looked up: a caller who wants a recorded pair dropped in both directions
+ *   passes lists that hold both directions of every pair (tip_amd.ops.symmetric_known makes them so).
+ *   Logits: as 4g.  DistMult: a_k = z[u,k] * w[r,k] rounded once, then acc = fmaf(a_k, z[c,k], acc) for k ascending from 0
+ *   -- the queried drug is the one multiplied with w first.  Table variant (tipk_pair_table_partner_sum; the NN decoder of
+ *   4b): the RELATION-major tables s1t, s2t [n_rel x ld], ld >= n_nodes; the logit is the single fp32 add
+ *   s1t[r,u] + s2t[r,c]: the queried drug is the decoder's first argument.  (The contract of a logit is the per-logit bound
+ *   of tests/partner_rank_spec.py, which holds for any order of the dim products; today's kernels give 4g's bits.)
+ *   Cell: out_sum fp32 [n_q x n_sel] = the sum over the candidates of partner_w[c] * sigma(logit), sigma(s) =
+ *   1.0f / (1.0f + expf(-s)); out_count int32 [n_q x n_sel] = the number of candidates.  Order of the fp32 sum: with
+ *   l = c mod 64, p_l starts at +0.0f and takes p_l = p_l + term_c for the candidates c = l, l + 64, ... ascending; then for
+ *   off = 32, 16, 8, 4, 2, 1: p_l = p_l + p_(l + off); the cell is p_0.  The order depends on nothing but n_nodes: BITWISE
+ *   repeatable, run to run and route to route; no floating-point atomics.
+ *   A drug that is no candidate (u itself, weight 0, recorded) is SKIPPED, not multiplied: its logit, NaN or not, does not
+ *   reach the sum.  A NaN logit of a candidate makes the cell NaN; a logit of +inf contributes exactly partner_w[c], one of
+ *   -inf exactly 0.  A cell without candidates has sum +0 and count 0.
+ *   A row whose u is outside [0, n_nodes) and a column whose r is outside [0, n_rel) hold sum NaN and count 0; nothing is
+ *   read out of bounds.
+ *   Selection, per row (k > 0): out_top_val fp32 [n_q x k], out_top_pos int32 [n_q x k] = the k largest non-NaN cells of the
+ *   row, value descending, ties (+0 and -0 tie) by ascending column position; the selection reads the fp32 values written
+ *   to out_sum, so the returned values are bit-equal to out_sum at those positions; a row with fewer than k such cells is
+ *   padded with (-inf, -1).  k == 0 skips the selection and both pointers may be NULL.
+ *   Work: one launch with one wavefront per (queried drug, block of 4 columns): a partner's row is read once and serves the
+ *   block's relations (register blocking: the vector ALU is the limit, not LDS); then, for k > 0, one launch with one
+ *   wavefront per queried drug on the same stream.
+ *   Routes (DistMult): z is staged in LDS once per workgroup when it fits beside the wavefronts' state
+ *   (tipk_distmult_partner_sum_lds_route: 645 x 16 does); otherwise, or under option "partner_sum_global", every lane reads
+ *   its rows from global memory; same bits.
+ *   Supported: as 4g -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; z 16-byte aligned),
+ *   1 <= n_rel <= 65 536; n_sel below 2^31.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k outside 0..128, a negative size, n_nodes or
+ *   n_rel < 1, dim < 1, ld < n_nodes, rel_ids == NULL with n_sel != n_rel, a NULL required pointer (q_drug, the tables,
+ *   out_sum, out_count, and with k > 0 the two top outputs; with n_q > 0 and n_sel > 0), keys without offsets or the
+ *   reverse; then TIPK_EUNSUPPORTED outside the supported range; n_q == 0 or n_sel == 0 is TIPK_OK with no launch and
+ *   nothing written; TIPK_OK implies correct numbers.
+ *   No workspace.  Nothing lives in host memory: these entries do NOT synchronise and may be captured into a hipGraph
+ *   (sequential launches, no parallel branches).
+ */
+int     tipk_distmult_partner_sum_supported(int64_t n_nodes, int dim, int64_t n_rel);
+int     tipk_distmult_partner_sum_lds_route(int64_t n_nodes, int dim);   /* 1 = z is staged in LDS once (options apply) */
+int     tipk_distmult_partner_sum(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                  const int32_t* q_drug /* device */, int64_t n_q,
+                                  const int32_t* rel_ids /* device; nullable: all relations */, int64_t n_sel,
+                                  const float* partner_w /* nullable */,
+                                  const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                                  int k, float* out_sum, int32_t* out_count, float* out_top_val /* nullable with k == 0 */,
+                                  int32_t* out_top_pos /* nullable with k == 0 */, tipk_stream_t stream);
+int     tipk_pair_table_partner_sum_supported(int64_t n_nodes, int64_t n_rel);
+int     tipk_pair_table_partner_sum(const float* s1t, const float* s2t, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                    const int32_t* q_drug /* device */, int64_t n_q,
+                                    const int32_t* rel_ids /* device; nullable: all relations */, int64_t n_sel,
+                                    const float* partner_w /* nullable */,
+                                    const int64_t* known_keys /* nullable */, const int64_t* known_ptr /* [n_rel+1], nullable */,
+                                    int k, float* out_sum, int32_t* out_count, float* out_top_val /* nullable with k == 0 */,
+                                    int32_t* out_top_pos /* nullable with k == 0 */, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

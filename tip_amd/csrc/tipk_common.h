@@ -39,7 +39,8 @@ enum {
     TIPK_OPT_PARTNER_RANK_GLOBAL = 12, // tipk_distmult_partner_rank: z rows read from global memory even where the LDS image fits
     TIPK_OPT_ADDON_GLOBAL = 13,       // tipk_distmult_addon_burden: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_ATTRIBUTION_GLOBAL = 14, // tipk_rgcn_attribution: the per-query table in the caller's workspace even where it fits in LDS
-    TIPK_OPT_COUNT = 15
+    TIPK_OPT_PARTNER_SUM_GLOBAL = 15, // tipk_distmult_partner_sum: z rows read from global memory even where the LDS image fits
+    TIPK_OPT_COUNT = 16
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

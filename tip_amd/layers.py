@@ -37,6 +37,8 @@ Explanation = namedtuple('Explanation', ['logit', 'offset', 'own', 'neighbours',
 NewDrugs = namedtuple('NewDrugs', ['x0', 'h', 'z', 'degree', 'n_targets'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
+# TIP.drug_profile's result: per queried drug the expected number of unrecorded partners for every side effect column
+DrugProfile = namedtuple('DrugProfile', ['expected', 'candidates', 'top_expected', 'top_relation'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
@@ -880,6 +882,14 @@ class MultiInnerProductDecoder(nn.Module):
         q_rel, q_drug [Q], tgt_ptr [Q + 1], tgt_node [T]: `ops.targets_by_query`.  known: (keys, ptr) as `screen`."""
         return ops.distmult_partner_rank(z.detach(), self.weight.detach(), q_rel, q_drug, tgt_ptr, tgt_node, known)
 
+    def partner_sums(self, z, q_drug, k, relations=None, partner_w=None, known=None):
+        """Partner sum (extension, `tipk_distmult_partner_sum`): per queried drug and relation the sum over the unrecorded
+        partners c of partner_w[c] * sigma(LOGIT), their number, and the k relations of each drug with the largest sum ->
+        (sum [Q, S], count int32 [Q, S], top_val [Q, k], top_pos int32 [Q, k]) as `ops.distmult_partner_sum`; no autograd.
+        relations: the ids that are the columns (None = all; global ids, so `known` stays as it is); known: (keys, ptr) as
+        `screen`, dropped in both directions."""
+        return ops.distmult_partner_sum(z.detach(), self.weight.detach(), q_drug, k, relations, partner_w, known)
+
     def pair_ranks(self, z, q_rel, tgt_ptr, tgt_u, tgt_v, known=None):
         """Screen rank (extension, `tipk_distmult_screen_rank`): the rank of every target pair among all unordered pairs of
         its relation query by the screen's LOGIT -> (rank int32 [T], logit [T]), rank 0 = not ranked; no autograd.
@@ -1051,6 +1061,26 @@ def _screen_known(d, exclude):
     return hit
 
 
+_REKEYED = {}
+
+
+def _rekeyed_known(known, n, n_wide):
+    """The relation-major lists `known` (keys u * n + v) as keys u * n_wide + v of a wider node set -- the same pairs in the
+    same order --, cached per key tensor like `_SCREEN_KEYS`; None stays None."""
+    if known is None:
+        return None
+    keys, ptr = known
+    ident = (keys.data_ptr(), keys._version, tuple(keys.shape), str(keys.device), int(n), int(n_wide))
+    hit = _REKEYED.get(ident)
+    if hit is None:
+        kk = keys.to(torch.int64)
+        hit = ((torch.div(kk, int(n), rounding_mode='floor') * int(n_wide) + kk % int(n)).contiguous(), ptr, keys)
+        if len(_REKEYED) > 8:
+            _REKEYED.clear()
+        _REKEYED[ident] = hit
+    return hit[:2]
+
+
 class NNDecoder(nn.Module):
     """The paper's DR-NN decoder (reference `src/layers.py:598-637`):
     score = sigma( relu(z[u] w1_l1) . w1_l2[r] + relu(z[v] w2_l1) . w2_l2[r] ).
@@ -1125,6 +1155,14 @@ class NNDecoder(nn.Module):
         with torch.no_grad():
             s1t, s2t = self._tables(z.detach(), relation_major=True)
         return ops.pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known)
+
+    def partner_sums(self, z, q_drug, k, relations=None, partner_w=None, known=None):
+        """Partner sum (extension, `tipk_pair_table_partner_sum`) on the two TRANSPOSED tables `objective` forms ([R, N]);
+        arguments and result as `MultiInnerProductDecoder.partner_sums`.  The queried drug is the decoder's first argument,
+        the partner its second."""
+        with torch.no_grad():
+            s1t, s2t = self._tables(z.detach(), relation_major=True)
+        return ops.pair_table_partner_sum(s1t, s2t, q_drug, k, relations, partner_w, known)
 
     def top_regimen_relations(self, z, reg_drugs, reg_ptr, k, aggregate='max', known=None, relations=None):
         """Regimen top-k (extension, `tipk_pair_table_regimen_topk`) on the two tables `forward` forms; arguments and result
@@ -1719,6 +1757,71 @@ class TIP(nn.Module):
                                            (r1.basis.detach(), r1.att.detach(), r1.root.detach()),
                                            (r2.basis.detach(), r2.att.detach(), r2.root.detach()), xd.contiguous(), tgt, inter, cat)
             return NewDrugs(x0n, hn, zn, inter[0][1:] - inter[0][:-1], tgt[0][1:] - tgt[0][:-1])
+
+    def drug_profile(self, drugs=None, k=10, exclude='all', relations=None, partner_weights=None, new=None):
+        """Serving (extension): the liability profile of single drugs -- for every side effect, with how many OTHER drugs the
+        model expects the drug to cause it, beyond the pairs already recorded (`decoder.partner_sums`: one
+        `tipk_distmult_partner_sum` / `tipk_pair_table_partner_sum` call on `self.embeddings`, under no_grad; no N x N x R
+        temporary; both decoder kinds).
+            expected[q, j] = sum over partners c of partner_weights[c] * sigma(logit(relations[j], drugs[q], c)),
+        over the drugs c != drugs[q] with a weight != 0 whose pair with drugs[q] is not recorded for the side effect.
+        drugs: ids (None = all training drugs; repeats allowed).  exclude: 'all' drops the train and test pairs of the side
+        effect, 'train' the training pairs, None nothing; a recorded pair is dropped in either direction.  relations:
+        side-effect ids that become the columns (None = all), as `side_effects`; the returned ids are global.
+        partner_weights: None (every partner counts 1, `expected` is a number of drugs) or one finite weight >= 0 per training
+        drug, e.g. a co-prescription frequency.  The queried drug is the decoder's first argument.
+        new: the `NewDrugs` of `embed_new_drugs`; an id n_drug + i in `drugs` then queries new drug i, on
+        torch.cat([self.embeddings, new.z]).  The partners are the EXISTING drugs only (new drugs weigh 0, so they are never
+        partners, of each other or of a training drug), and a new drug has no recorded list: nothing is dropped from its row.
+        -> DrugProfile(expected float32 [Q, R'], candidates int64 [Q, R']: the number of partners summed over, top_expected
+        float32 [Q, k], top_relation int64 [Q, k]: the k side effects of each drug with the largest expectation, descending,
+        ties by position in `relations`, padded with (-inf, -1)) on the model's device."""
+        _refuse_sharded(self.shard, 'partners')
+        _check_known_mode('exclude', exclude)
+        d = self.data
+        k = int(k)
+        if k < 0 or k > 128:
+            raise ValueError('k must be in 0..128, not %d' % k)
+        n_new = 0 if new is None else int(new.z.shape[0])
+        n_all = d.n_drug + n_new
+        if drugs is None:
+            q_host = torch.arange(d.n_drug, dtype=torch.int64)
+        else:
+            q_host = torch.as_tensor(drugs).to('cpu')
+            if q_host.dtype.is_floating_point or q_host.dtype == torch.bool:
+                raise ValueError('drugs: int ids expected, got %s' % q_host.dtype)
+            q_host = q_host.to(torch.int64).reshape(-1)
+        if q_host.numel() and (int(q_host.min()) < 0 or int(q_host.max()) >= n_all):
+            raise ValueError('drug id out of range: [%d, %d] for %d drugs%s'
+                             % (int(q_host.min()), int(q_host.max()), d.n_drug, ' and %d new ones' % n_new if new is not None else ''))
+        rel_host = _relation_ids(relations, 'cpu')
+        if rel_host is not None and rel_host.numel() and (int(rel_host.min()) < 0 or int(rel_host.max()) >= d.n_dd_et):
+            raise ValueError('side-effect id out of range: [%d, %d] for %d side effects'
+                             % (int(rel_host.min()), int(rel_host.max()), d.n_dd_et))
+        if partner_weights is not None:
+            try:
+                partner_weights = torch.as_tensor(partner_weights).detach().to('cpu', torch.float32)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError('partner_weights: one number per drug expected') from None
+            if partner_weights.dim() != 1 or partner_weights.numel() != d.n_drug:
+                raise ValueError('partner_weights: %d entries expected (one per drug), got shape %s'
+                                 % (d.n_drug, tuple(partner_weights.shape)))
+            if not bool((torch.isfinite(partner_weights) & (partner_weights >= 0)).all()):
+                raise ValueError('partner_weights must be finite and >= 0')
+        dev = self.embeddings.device
+        known = _screen_known(d, exclude)
+        with torch.no_grad():
+            z = self.embeddings
+            pw = None if partner_weights is None else partner_weights.to(dev)
+            if new is not None:
+                z = torch.cat([z.detach(), new.z.detach().to(dev)])
+                ones = torch.ones(d.n_drug, dtype=torch.float32, device=dev) if pw is None else pw
+                pw = torch.cat([ones, torch.zeros(n_new, dtype=torch.float32, device=dev)])
+                known = _rekeyed_known(known, d.n_drug, n_all)
+            rel = None if rel_host is None else rel_host.to(dev)
+            total, count, top_v, top_p = self.decoder.partner_sums(z, q_host.to(dev), k, rel, pw, known)
+            top_rel = top_p.to(torch.int64) if rel is None else _ids_at(top_p, rel)
+        return DrugProfile(total, count.to(torch.int64), top_v, top_rel)
 
     def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it

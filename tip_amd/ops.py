@@ -1386,6 +1386,105 @@ def pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known=No
     return out_rank, out_logit
 
 
+_SYMMETRIC_KNOWN = {}
+
+
+def symmetric_known(known, n_nodes):
+    """Relation-major known lists (keys int64 u*n+v sorted inside each relation, ptr int64 [n_rel + 1]) that hold BOTH
+    directions of every pair: each key is mirrored to v*n+u, the keys are sorted inside each relation and duplicates dropped
+    (a self key u*n+u is its own mirror).  Lists that are already symmetric come back UNCHANGED (the same tuple); None stays
+    None.  Torch ops on the lists' device (CPU tensors work too); cached per list tensors, like the screen's merged keys."""
+    if known is None:
+        return None
+    keys, kptr = known
+    n = int(n_nodes)
+    tag = (keys.data_ptr(), keys._version, tuple(keys.shape), kptr.data_ptr(), kptr._version, str(keys.device), n)
+    hit = _SYMMETRIC_KNOWN.get(tag)
+    if hit is None:
+        k64, p64 = keys.to(torch.int64), kptr.to(torch.int64)
+        n_rel = p64.numel() - 1
+        rel = torch.repeat_interleave(torch.arange(n_rel, device=keys.device), p64[1:] - p64[:-1])
+        comb = rel * (n * n) + k64
+        mirror = rel * (n * n) + (k64 % n) * n + torch.div(k64, n, rounding_mode='floor')
+        both = torch.unique(torch.cat([comb, mirror]))                  # sorted by (relation, key), duplicates gone
+        if both.numel() == comb.numel() and torch.equal(both, comb):
+            hit = known
+        else:
+            ptr = torch.zeros(n_rel + 1, dtype=torch.int64, device=keys.device)
+            ptr[1:] = torch.cumsum(torch.bincount(torch.div(both, n * n, rounding_mode='floor'), minlength=n_rel), 0)
+            hit = ((both % (n * n)).contiguous(), ptr)
+        if len(_SYMMETRIC_KNOWN) > 8:
+            _SYMMETRIC_KNOWN.clear()
+        _SYMMETRIC_KNOWN[tag] = hit = (hit, known)                       # (the input is pinned: its address stays its own)
+    return hit[0]
+
+
+def _partner_sum_lists(q_drug, k, rel_ids, partner_w, known, n, n_rel, dev):
+    """(q_drug int32 [Q], rel_ids int32 [S] or None, n_sel, partner_w or None, keys, ptr, k, outputs) of the partner sum
+    entries, all on `dev`; the known lists are made symmetric (`symmetric_known`)."""
+    q_drug = torch.as_tensor(q_drug)
+    rel_ids = None if rel_ids is None else torch.as_tensor(rel_ids)
+    require_device(q_drug, rel_ids, partner_w)
+    ints = (q_drug,) + (() if rel_ids is None else (rel_ids,))
+    if any(t.dim() != 1 or t.dtype.is_floating_point for t in ints):
+        raise _lib.TipkError('partner sum: 1-d int tensors q_drug [Q] and rel_ids [S] (or None) expected, got %s'
+                             % ', '.join('%s %s' % (t.dtype, tuple(t.shape)) for t in ints))
+    if partner_w is not None:
+        partner_w = _f32c(partner_w).contiguous()
+        if partner_w.dim() != 1 or partner_w.numel() != n:
+            raise _lib.TipkError('partner_w: a float tensor [%d] expected, got %s' % (n, tuple(partner_w.shape)))
+    keys, kptr = _relation_known(symmetric_known(known, n))
+    qd = q_drug.to(torch.int32).contiguous()
+    rel = None if rel_ids is None else rel_ids.to(torch.int32).contiguous()
+    n_q, n_sel, k = qd.numel(), (n_rel if rel is None else rel.numel()), int(k)
+    out_sum = torch.empty((n_q, n_sel), dtype=torch.float32, device=dev)
+    out_cnt = torch.empty((n_q, n_sel), dtype=torch.int32, device=dev)
+    if n_sel == 0 and k > 0:                                             # (no launch without columns: the rows are padding)
+        top_v = torch.full((n_q, k), float('-inf'), dtype=torch.float32, device=dev)
+        top_p = torch.full((n_q, k), -1, dtype=torch.int32, device=dev)
+    else:
+        top_v, top_p = _topk_outputs(n_q, k, 1, dev)
+    return qd, rel, n_sel, partner_w, keys, kptr, k, out_sum, out_cnt, top_v, top_p
+
+
+def distmult_partner_sum(z, rel_w, q_drug, k, rel_ids=None, partner_w=None, known=None):
+    """The expected number of unrecorded partners of every queried drug per relation by DistMult logit, and the k relations of
+    each drug with the largest expectation (include/tipk.h section 4l).
+
+    q_drug int [Q] (entries may repeat); rel_ids None (all relations) or int [S]: the relations that are the columns of the
+    result (entries may repeat); partner_w None (all 1) or float [n], finite and >= 0; known: None or (keys int64 u*n+v sorted
+    inside each relation, ptr int64 [n_rel + 1]), the relation-major lists `distmult_screen` takes -- made symmetric here
+    (`symmetric_known`), so a recorded pair is dropped in both directions.  All on the device.
+    -> (sum float32 [Q, S], count int32 [Q, S], top_val float32 [Q, k], top_pos int32 [Q, k]): sum = the sum over the
+    candidates c (c != u, partner_w[c] != 0, (u, c) not recorded for the relation) of partner_w[c] * sigma(logit), count =
+    their number; (NaN, 0) for a drug outside [0, n) or a relation outside [0, n_rel); NaN where a candidate's logit is NaN.
+    top_*: the k largest non-NaN cells of each row, descending, ties by column position, padded with (-inf, -1); empty for
+    k = 0.  Does not synchronise (the first call on new known lists does, once, to mirror them)."""
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_partner_sum')
+    dev = z.device
+    n, dim, n_rel = z.shape[0], z.shape[1], rel_w.shape[0]
+    qd, rel, n_sel, pw, keys, kptr, k, out_sum, out_cnt, top_v, top_p = _partner_sum_lists(q_drug, k, rel_ids, partner_w,
+                                                                                           known, n, n_rel, dev)
+    check(lib().tipk_distmult_partner_sum(ptr(z), n, dim, ptr(rel_w), n_rel, ptr(qd), qd.numel(), ptr(rel), n_sel, ptr(pw),
+                                          ptr(keys), ptr(kptr), k, ptr(out_sum), ptr(out_cnt), ptr(top_v), ptr(top_p),
+                                          stream_ptr(dev)), 'tipk_distmult_partner_sum')
+    return out_sum, out_cnt, top_v, top_p
+
+
+def pair_table_partner_sum(s1t, s2t, q_drug, k, rel_ids=None, partner_w=None, known=None):
+    """`distmult_partner_sum` for the NN decoder's RELATION-major tables s1t, s2t [n_rel, n] (row stride free, the same for
+    both), as `NNDecoder.objective` forms them: the logit of partner c of drug u under r is s1t[r, u] + s2t[r, c]."""
+    s1t, s2t = _table_pair(s1t, s2t, 'pair_table_partner_sum', '[n_rel, n]')
+    dev = s1t.device
+    n, n_rel = s1t.shape[1], s1t.shape[0]
+    qd, rel, n_sel, pw, keys, kptr, k, out_sum, out_cnt, top_v, top_p = _partner_sum_lists(q_drug, k, rel_ids, partner_w,
+                                                                                           known, n, n_rel, dev)
+    check(lib().tipk_pair_table_partner_sum(ptr(s1t), ptr(s2t), s1t.stride(0), n, n_rel, ptr(qd), qd.numel(), ptr(rel), n_sel,
+                                            ptr(pw), ptr(keys), ptr(kptr), k, ptr(out_sum), ptr(out_cnt), ptr(top_v),
+                                            ptr(top_p), stream_ptr(dev)), 'tipk_pair_table_partner_sum')
+    return out_sum, out_cnt, top_v, top_p
+
+
 def targets_by_relation(edge_index, edge_type, n_rel):
     """Triples (u, v, r) grouped by the relation query r that ranks the pair {u, v} -- for the screen rank entry
     (include/tipk.h section 4h) -> (q_rel int32 [Q], tgt_ptr int64 [Q + 1], tgt_u int32 [T], tgt_v int32 [T], order int64
