@@ -5,7 +5,7 @@ import torch
 
 from screen_spec import keys_from_pairs
 
-SMALL = [(70, 4), (97, 16), (201, 32), (130, 64), (77, 128), (133, 256)]
+SMALL = [(70, 4), (97, 16), (201, 32), (130, 64), (77, 128), (133, 256), (130, 36)]
 EDGE_N = [1, 2, 63, 64, 65, 128, 129]
 
 

@@ -40,7 +40,7 @@ def _queries(n):
 
 
 @pytest.mark.parametrize('n,dim,k', [(70, 4, 1), (133, 8, 1024), (97, 16, 37), (201, 32, 1024), (130, 64, 5),
-                                     (77, 128, 1024), (301, 16, 1)])
+                                     (77, 128, 1024), (301, 16, 1), (130, 36, 37)])
 def test_screen_small_graphs(n, dim, k):
     z, w, known = _graph(n, dim, seed=1000 * n + dim)
     q = _queries(n)

@@ -11,21 +11,20 @@
 //   3. One pass over v's in-edges, 1024 edges per round, four per thread (positions t, t + 256, ...: four chains in
 //      flight): c_e = (1 / deg) * sum_b att[rel_e][b] * M[src_e][b], b ascending.  The relation-sorted segment makes
 //      neighbouring lanes share att rows.  Every c_e is added to the thread's fp64 partial (positions ascending);
-//      candidates go through the selection of tipk_screen.hip: an LDS buffer (in the place of the staged block of h), a
-//      running k-th-best threshold that drops most edges before they are appended, a bitonic cut when the buffer could
-//      overflow.  The order is total (value descending, position ascending), so the kept set does not depend on the
+//      candidates go through the selection of tipk_wg_topk.h (WgSel): an LDS buffer (in the place of the staged block of
+//      h), a running k-th-best threshold that drops most edges before they are appended, a bitonic cut when the buffer
+//      could overflow.  The order is total (value descending, position ascending), so the kept set does not depend on the
 //      order of the appends.
 //   4. The fp64 partials are added in a fixed tree (lanes by shuffle, 32 .. 1; then the four wavefronts in order) and
 //      rounded once; the buffer is cut a last time and written with the edges' source and relation.
 // Routes: the table lives in LDS where n_nodes x n_bases floats fit beside the rest (tipk_rgcn_attribution_lds_route: 645 x
 // 32 does), else -- or under option "attribution_global" -- in a slice of the caller's workspace owned by the workgroup, and
 // at most 256 workgroups loop over the queries.  The arithmetic is the same code: same bits.
-#include "tipk_common.h"
-#include <math.h>
+#include "tipk_wg_topk.h"
 
 namespace {
 
-constexpr int AT_NT = 256;                 // threads per workgroup: rows of a staged block of h, edges of a round
+constexpr int AT_NT = WG_NT;               // threads per workgroup: rows of a staged block of h, edges of a round
 constexpr int AT_IC = 32;                  // columns of h per staged chunk
 constexpr int AT_LDT = AT_IC + 1;          // LDS row stride of the staged block (floats)
 constexpr int AT_BC = 8;                   // bases a thread keeps in registers
@@ -40,7 +39,6 @@ constexpr int64_t AT_NMAX = 46340;
 constexpr int64_t AT_RMAX = 65536;
 constexpr int64_t AT_LDS_BYTES = 160 * 1024;
 constexpr int AT_GLOBAL_WG = 256;          // workgroups (= workspace slices) of the global route
-constexpr int AT_POS_PAD = 0x7fffffff;
 
 struct AttrArgs {
     const float *h, *basis, *att, *root, *probe;
@@ -54,71 +52,8 @@ struct AttrArgs {
     float* ws;                 // global route: [gridDim.x][n_bases x n]
 };
 
-__device__ __forceinline__ bool better(float sa, int ka, float sb, int kb) {
-    return sa > sb || (sa == sb && ka < kb);
-}
-
-// the selection of tipk_screen.hip with the edge's position in its segment as the key
-struct Sel {
-    float* bs;
-    int* bk;
-    unsigned* ctr;             // [3] rotating append counters (one barrier per round)
-    int k;
-    int c;                     // entries in the buffer (uniform)
-    int rr;                    // round number (uniform)
-    float thr;
-
-    // every lane calls this (uniform control flow): append (s, pos) when ok and not below the threshold; NaN never passes
-    __device__ __forceinline__ void offer(bool ok, float s, int pos) {
-        const bool pass = ok && s >= thr;
-        const unsigned long long mask = __ballot(pass);
-        if (mask == 0ull) return;
-        const int lane = tipk_lane();
-        const int leader = __ffsll((long long)mask) - 1;
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(&ctr[rr % 3], (unsigned)__popcll(mask));
-        base = __shfl(base, leader);
-        if (pass) {
-            const unsigned at = (unsigned)c + base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-            bs[at] = s;
-            bk[at] = pos;
-        }
-    }
-
-    // sort the c entries best first and keep k of them (every thread, uniform)
-    __device__ void flush() {
-        const int t = threadIdx.x;
-        int p = 2;
-        while (p < c) p <<= 1;
-        for (int i = c + t; i < p; i += AT_NT) { bs[i] = -INFINITY; bk[i] = AT_POS_PAD; }
-        __syncthreads();
-        for (int size = 2; size <= p; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int x = t; x < (p >> 1); x += AT_NT) {
-                    const int i = 2 * stride * (x / stride) + (x % stride), j = i + stride;
-                    const float si = bs[i], sj = bs[j];
-                    const int ki = bk[i], kj = bk[j];
-                    const bool up = (i & size) == 0;
-                    if (up ? better(sj, kj, si, ki) : better(si, ki, sj, kj)) {
-                        bs[i] = sj; bk[i] = kj; bs[j] = si; bk[j] = ki;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        c = c < k ? c : k;
-        thr = c == k ? bs[k - 1] : -INFINITY;
-    }
-
-    // end of a round: everything appended is visible; c moves on; the counter of round rr - 1 is cleared for rr + 2
-    __device__ __forceinline__ void end_round() {
-        __syncthreads();
-        c += (int)ctr[rr % 3];
-        if (threadIdx.x == 0) ctr[(rr + 2) % 3] = 0u;
-        ++rr;
-        if (c > AT_CAP - AT_ROUND) flush();
-    }
-};
+// the selection of tipk_wg_topk.h with the edge's position in its segment as the key (no filter)
+using Sel = WgSel<AT_NT, AT_CAP, AT_ROUND>;
 
 // floats of LDS in front of the table: g, root . g, Gt, the staged block of h (later the selection buffer), the reduction cells
 static_assert(2 * AT_CAP <= AT_NT * AT_LDT, "the selection buffer lives in the staged block");
@@ -225,7 +160,7 @@ __global__ void __launch_bounds__(AT_NT) attribution_kernel(AttrArgs a) {
 
         // 3. one pass over the in-edges
         Sel sel;
-        sel.bs = bs; sel.bk = bk; sel.ctr = ctr; sel.k = k; sel.c = 0; sel.rr = 0; sel.thr = -INFINITY;
+        sel.init(bs, bk, ctr, k);
         const float inv = 1.0f / (float)(deg > 0 ? deg : 1);
         double part = 0.0;
         for (int64_t base = 0; base < deg; base += AT_ROUND) {
@@ -268,7 +203,7 @@ __global__ void __launch_bounds__(AT_NT) attribution_kernel(AttrArgs a) {
                 const bool ok = pos < deg;
                 const float c = inv * acc[j];
                 if (ok) part += (double)c;
-                sel.offer(ok, c, (int)pos);
+                sel.append(sel.wants(ok, c), c, (int)pos);
             }
             sel.end_round();
         }

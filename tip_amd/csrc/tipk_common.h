@@ -66,4 +66,8 @@ __device__ __forceinline__ void st4_stream(float* p, float4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(q) : "memory");
 }
 __device__ __forceinline__ int tipk_lane() { return threadIdx.x & (TIPK_WAVE - 1); }
+// THE total order of every ranking and selection kernel: score descending, id ascending (a NaN score is better than nothing)
+__device__ __forceinline__ bool better(float sa, int ka, float sb, int kb) {
+    return sa > sb || (sa == sb && ka < kb);
+}
 #endif

@@ -13,16 +13,14 @@
 // keys).  When the buffer could overflow in the next round it is sorted (bitonic) and cut to k, which raises the
 // threshold.  Dropping a candidate below the threshold is exact: k kept entries are better than it.  The result is a set
 // defined by the total order (logit desc, key asc), so it does not depend on the order of the appends.
-#include "tipk_common.h"
-#include <math.h>
+// The tile deal and scorer, the known-pair filter, the selection and its bitonic network are the shared pieces of
+// tipk_wg_topk.h; this file holds the query loop over tiles and drug blocks, the merge kernel and the workspace layout.
+#include "tipk_wg_topk.h"
 #include <vector>
 
 namespace {
 
-constexpr int SC_NT = 256;                 // threads per workgroup
-constexpr int SC_TILE = 64;                // rows of the A and Z tiles of a relation query
-constexpr int SC_KC = 32;                  // columns of z per staged chunk
-constexpr int SC_LD = SC_TILE + 4;         // LDS row stride of the transposed tiles (floats; keeps float4 alignment)
+constexpr int SC_NT = WG_NT;               // threads per workgroup
 constexpr int SC_DBLK = 256;               // candidates per block of a drug query (one per thread)
 constexpr int SC_CAP = 2048;               // buffer entries (power of two >= k_max + one round)
 constexpr int SC_ROUND = 1024;             // most appends of one round (relation: 256 threads x 4; drug: 256)
@@ -31,9 +29,6 @@ constexpr int SC_DIM_MAX = 256;
 constexpr int64_t SC_NMAX = 46340;         // n^2 < 2^31: a key u*n+v is an int32
 constexpr int SC_BITMAP_BYTES = 65536;     // LDS bitmap route: n^2 bits within this
 constexpr int SC_MERGE_G = 8;              // part lists merged per merge workgroup
-constexpr int SC_SPLIT_MAX = 64;
-constexpr int SC_TARGET_WG = 4096;
-constexpr int SC_KEY_PAD = 0x7fffffff;
 
 struct ScreenArgs {
     const float* z;
@@ -46,95 +41,19 @@ struct ScreenArgs {
     int32_t* part_k;
 };
 
-__device__ __forceinline__ bool better(float sa, int ka, float sb, int kb) {
-    return sa > sb || (sa == sb && ka < kb);
+using Sel = WgSel<SC_NT, SC_CAP, SC_ROUND>;
+
+// every lane calls this (uniform control flow): append (s, u*n+v) when ok, not below the threshold, not known -- the filter
+// is consulted only for a candidate that passed the threshold
+__device__ __forceinline__ void offer(Sel& sel, const WgKnown& known, bool ok, float s, int u, int v) {
+    bool pass = sel.wants(ok, s);
+    if (pass) pass = !known.known(u, v);
+    sel.append(pass, s, u * known.n + v);
 }
-
-__device__ __forceinline__ bool key_in(const int64_t* keys, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int64_t v = keys[mid];
-        if (v == x) return true;
-        if (v < x) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
-struct Sel {
-    float* bs;
-    int* bk;
-    unsigned* ctr;             // [3] rotating append counters (one barrier per round)
-    const uint32_t* bm;        // LDS bitmap or nullptr
-    const int64_t* keys;
-    int64_t klo, khi;
-    int n, k;
-    int c;                     // entries in the buffer (uniform)
-    int rr;                    // round number (uniform)
-    float thr;
-
-    // every lane calls this (uniform control flow): append (s, u*n+v) when ok, not below the threshold, not known
-    __device__ __forceinline__ void offer(bool ok, float s, int u, int v) {
-        bool pass = ok && s >= thr;
-        if (pass) {
-            if (bm) {
-                const uint32_t b = (uint32_t)(u * n + v);
-                pass = !((bm[b >> 5] >> (b & 31)) & 1u);
-            } else if (keys) {
-                pass = !key_in(keys, klo, khi, (int64_t)u * n + v) && !key_in(keys, klo, khi, (int64_t)v * n + u);
-            }
-        }
-        const unsigned long long mask = __ballot(pass);
-        if (mask == 0ull) return;
-        const int lane = tipk_lane();
-        const int leader = __ffsll((long long)mask) - 1;
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(&ctr[rr % 3], (unsigned)__popcll(mask));
-        base = __shfl(base, leader);
-        if (pass) {
-            const unsigned pos = (unsigned)c + base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-            bs[pos] = s;
-            bk[pos] = u * n + v;
-        }
-    }
-
-    // sort the c entries best first and keep k of them (every thread, uniform)
-    __device__ void flush() {
-        const int t = threadIdx.x;
-        int p = 2;
-        while (p < c) p <<= 1;
-        for (int i = c + t; i < p; i += SC_NT) { bs[i] = -INFINITY; bk[i] = SC_KEY_PAD; }
-        __syncthreads();
-        for (int size = 2; size <= p; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int x = t; x < (p >> 1); x += SC_NT) {
-                    const int i = 2 * stride * (x / stride) + (x % stride), j = i + stride;
-                    const float si = bs[i], sj = bs[j];
-                    const int ki = bk[i], kj = bk[j];
-                    const bool up = (i & size) == 0;
-                    if (up ? better(sj, kj, si, ki) : better(si, ki, sj, kj)) {
-                        bs[i] = sj; bk[i] = kj; bs[j] = si; bk[j] = ki;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        c = c < k ? c : k;
-        thr = c == k ? bs[k - 1] : -INFINITY;
-    }
-
-    // end of a round: everything appended is visible; c moves on; the counter of round rr - 1 is cleared for rr + 2
-    __device__ __forceinline__ void end_round() {
-        __syncthreads();
-        c += (int)ctr[rr % 3];
-        if (threadIdx.x == 0) ctr[(rr + 2) % 3] = 0u;
-        ++rr;
-        if (c > SC_CAP - SC_ROUND) flush();
-    }
-};
 
 __global__ void __launch_bounds__(SC_NT) screen_kernel(ScreenArgs a) {
-    __shared__ float As[SC_KC * SC_LD];
-    __shared__ float Zs[SC_KC * SC_LD];
+    __shared__ float As[WG_KC * WG_LD];
+    __shared__ float Zs[WG_KC * WG_LD];
     __shared__ float bs[SC_CAP];
     __shared__ int bk[SC_CAP];
     __shared__ float wl[SC_DIM_MAX];
@@ -148,8 +67,8 @@ __global__ void __launch_bounds__(SC_NT) screen_kernel(ScreenArgs a) {
     const int n = a.n, dim = a.dim;
 
     Sel sel;
-    sel.bs = bs; sel.bk = bk; sel.ctr = ctr; sel.bm = nullptr; sel.keys = nullptr; sel.klo = sel.khi = 0;
-    sel.n = n; sel.k = a.k; sel.c = 0; sel.rr = 0; sel.thr = -INFINITY;
+    sel.init(bs, bk, ctr, a.k);
+    WgKnown known;
 
     if (t < 3) ctr[t] = 0u;
     for (int i = t; i < dim; i += SC_NT) {
@@ -157,88 +76,31 @@ __global__ void __launch_bounds__(SC_NT) screen_kernel(ScreenArgs a) {
         wl[i] = wv;
         if (du >= 0) al[i] = a.z[(int64_t)du * dim + i] * wv;
     }
-    if (a.keys) {
-        sel.klo = a.kptr[r];
-        sel.khi = a.kptr[r + 1];
-        if (a.bitmap) {
-            const int words = (int)(((int64_t)n * n + 31) / 32);
-            for (int i = t; i < words; i += SC_NT) bm[i] = 0u;
-            __syncthreads();                                   // cleared before any bit is set
-            const int64_t nn = (int64_t)n * n;
-            for (int64_t e = sel.klo + t; e < sel.khi; e += SC_NT) {
-                const int64_t key = a.keys[e];
-                if (key < 0 || key >= nn) continue;
-                const int x = (int)(key / n), y = (int)(key % n);
-                const uint32_t b0 = (uint32_t)(x * n + y), b1 = (uint32_t)(y * n + x);
-                atomicOr(&bm[b0 >> 5], 1u << (b0 & 31));
-                atomicOr(&bm[b1 >> 5], 1u << (b1 & 31));
-            }
-            sel.bm = bm;
-        } else {
-            sel.keys = a.keys;
-        }
-    }
+    known.build<SC_NT>(bm, a.keys, a.kptr, r, n, a.bitmap);
     __syncthreads();                                           // counters, w, a and the bitmap are in place
 
     if (du < 0) {
-        // relation query: tiles (bu <= bv) of the upper triangle in row-major order, this part's share of them
-        const int nb = (n + SC_TILE - 1) / SC_TILE;
-        const int64_t n_tiles = (int64_t)nb * (nb + 1) / 2;
-        const int64_t t0 = n_tiles * part / a.splits, t1 = n_tiles * (part + 1) / a.splits;
-        int bu = 0;
-        int64_t row_start = 0;                                  // linear index of tile (bu, bu)
-        while (t0 < t1 && t0 >= row_start + (nb - bu)) { row_start += nb - bu; ++bu; }
-        int bv = bu + (int)(t0 - row_start);
+        // relation query: this part's share of the tiles of the upper triangle
+        WgDeal deal(n, part, a.splits);
         const int ty = t >> 4, tx = t & 15;
-        for (int64_t tile = t0; tile < t1; ++tile) {
+        for (int64_t tile = deal.t0; tile < deal.t1; ++tile) {
             float acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-            for (int k0 = 0; k0 < dim; k0 += SC_KC) {
-                const int kc = dim - k0 < SC_KC ? dim - k0 : SC_KC;
-                __syncthreads();                                 // the previous chunk has been read
-                for (int idx = t; idx < 2 * SC_TILE * (SC_KC / 4); idx += SC_NT) {
-                    const int which = idx / (SC_TILE * (SC_KC / 4));
-                    const int rem = idx % (SC_TILE * (SC_KC / 4));
-                    const int row = rem >> 3, qd = rem & 7;
-                    if (4 * qd >= kc) continue;
-                    const int node = (which == 0 ? bu : bv) * SC_TILE + row;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (node < n) v = tipk_ld4(a.z + (int64_t)node * dim + k0 + 4 * qd);
-                    float* dst = which == 0 ? As : Zs;
-                    if (which == 0) {
-                        const int kk = k0 + 4 * qd;
-                        v.x *= wl[kk]; v.y *= wl[kk + 1]; v.z *= wl[kk + 2]; v.w *= wl[kk + 3];
-                    }
-                    dst[(4 * qd + 0) * SC_LD + row] = v.x;
-                    dst[(4 * qd + 1) * SC_LD + row] = v.y;
-                    dst[(4 * qd + 2) * SC_LD + row] = v.z;
-                    dst[(4 * qd + 3) * SC_LD + row] = v.w;
-                }
-                __syncthreads();
-                for (int kk = 0; kk < kc; ++kk) {
-                    const float4 av = *reinterpret_cast<const float4*>(&As[kk * SC_LD + 4 * ty]);
-                    const float4 zv = *reinterpret_cast<const float4*>(&Zs[kk * SC_LD + 4 * tx]);
-                    const float ar[4] = {av.x, av.y, av.z, av.w}, zr[4] = {zv.x, zv.y, zv.z, zv.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(ar[i], zr[j], acc[i][j]);
-                }
-            }
-            const int u0 = bu * SC_TILE + 4 * ty, v0 = bv * SC_TILE + 4 * tx;
+            wg_score_tile(As, Zs, a.z, wl, n, dim, deal.bu, deal.bv, acc);
+            const int u0 = deal.bu * WG_TILE + 4 * ty, v0 = deal.bv * WG_TILE + 4 * tx;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int u = u0 + i, v = v0 + j;
-                    sel.offer(u < v && v < n, acc[i][j], u, v);
+                    offer(sel, known, u < v && v < n, acc[i][j], u, v);
                 }
                 sel.end_round();
             }
-            if (++bv == nb) { ++bu; bv = bu; }
+            deal.next();
         }
     } else {
         // drug query (r, du): blocks of 256 partners v != du
@@ -257,7 +119,7 @@ __global__ void __launch_bounds__(SC_NT) screen_kernel(ScreenArgs a) {
                     acc = fmaf(al[k0 + 3], x.w, acc);
                 }
             }
-            sel.offer(v < n && v != du, acc, du, v);
+            offer(sel, known, v < n && v != du, acc, du, v);
             sel.end_round();
         }
     }
@@ -329,21 +191,6 @@ __global__ void __launch_bounds__(SC_NT) screen_merge_kernel(const float* in_s, 
     }
 }
 
-int64_t screen_tiles(int64_t n) {
-    const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
-    return nb * (nb + 1) / 2;
-}
-
-// parts per query: enough workgroups to fill the chip for few queries, one part per query for thousands of them
-int screen_splits(int64_t n, int64_t n_q) {
-    int64_t s = n_q > 0 ? SC_TARGET_WG / n_q : 1;
-    if (s < 1) s = 1;
-    if (s > SC_SPLIT_MAX) s = SC_SPLIT_MAX;
-    const int64_t tiles = screen_tiles(n);
-    if (s > tiles) s = tiles;
-    return (int)s;
-}
-
 int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 struct Layout {
@@ -353,7 +200,7 @@ struct Layout {
 
 Layout screen_layout(int64_t n, int64_t n_q, int k) {
     Layout L;
-    L.splits = screen_splits(n, n_q);
+    L.splits = wg_splits(n, n_q);
     L.splits2 = L.splits > SC_MERGE_G ? (L.splits + SC_MERGE_G - 1) / SC_MERGE_G : 0;
     L.q_off = 0;
     int64_t off = align256(n_q * 8);

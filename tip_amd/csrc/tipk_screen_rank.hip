@@ -4,36 +4,29 @@
 // Two launches, nothing on the host.
 // screen_rank_init_kernel (a workgroup per query): every target's logit and whether it is ranked; writes out_logit and
 //   out_rank = 1 (ranked) or 0 (not ranked: the final value).
-// screen_rank_kernel (n_q x S workgroups of 256 threads, S and the deal of the 64 x 64 tiles of the upper triangle as in
-//   tipk_screen.hip): per chunk of SR_CHUNK targets of its query the workgroup
+// screen_rank_kernel (n_q x S workgroups of 256 threads, S and the deal of the 64 x 64 tiles of the upper triangle are
+//   wg_splits and WgDeal of tipk_wg_topk.h, the screen's): per chunk of SR_CHUNK targets of its query the workgroup
 //     1. computes the chunk's target logits (the init kernel's function: same bits) and sorts them best first in LDS
-//        under the total order of 4c (logit desc, key asc; bitonic network); targets that are not ranked sort last;
-//     2. streams its tiles with the screen's staging and 4 x 4-per-thread fmaf loop -- the same arithmetic in the same
-//        order, so a candidate's logit is the screen's, and a target's logit is its own candidate's;
+//        under the total order of 4c (logit desc, key asc; wg_bitonic); targets that are not ranked sort last;
+//     2. streams its tiles through wg_score_tile, the screen's staging and 4 x 4-per-thread fmaf loop -- one function,
+//        so a candidate's logit is the screen's, and a target's logit is its own candidate's;
 //     3. for a candidate that beats the chunk's WEAKEST target (the order is total: one that does not beats none) and is
-//        not a known pair (LDS bitmap or binary search, consulted only now) finds by binary search the first sorted target
-//        it beats and adds 1 to that position's LDS bucket;
+//        not a known pair (WgKnown: LDS bitmap or binary search, consulted only now) finds by binary search the first
+//        sorted target it beats and adds 1 to that position's LDS bucket;
 //     4. turns the buckets into an inclusive prefix sum -- the target at sorted position j is beaten by sum_{p <= j} of them
 //        in this part -- and adds it to out_rank with an integer atomic.
 //   The order is irreflexive: a target never counts itself or its repeats, listed or not.  A NaN candidate beats nothing.
 //   The counts are integers, so the sum over parts and chunks does not depend on the order of the atomics.
-#include "tipk_common.h"
-#include <math.h>
+#include "tipk_wg_topk.h"
 
 namespace {
 
-constexpr int SR_NT = 256;                 // threads per workgroup
-constexpr int SR_TILE = 64;                // rows of the A and Z tiles
-constexpr int SR_KC = 32;                  // columns of z per staged chunk
-constexpr int SR_LD = SR_TILE + 4;         // LDS row stride of the transposed tiles (floats; keeps float4 alignment)
+constexpr int SR_NT = WG_NT;               // threads per workgroup
 constexpr int SR_CHUNK = 2048;             // targets of one query ranked per pass (power of two)
 constexpr int SR_PER = SR_CHUNK / SR_NT;   // buckets a thread sums in the prefix step
 constexpr int SR_DIM_MAX = 256;
 constexpr int64_t SR_NMAX = 46340;         // n^2 < 2^31: a key a*n+b is an int32
 constexpr int64_t SR_RMAX = 65536;
-constexpr int SR_SPLIT_MAX = 64;
-constexpr int SR_TARGET_WG = 4096;
-constexpr int SR_KEY_PAD = 0x7fffffff;     // key of a slot that holds no ranked target (sorts last)
 
 struct ScreenRankArgs {
     const float* z;
@@ -50,20 +43,6 @@ struct ScreenRankArgs {
     float* out_logit;          // nullable
 };
 
-__device__ __forceinline__ bool better(float sa, int ka, float sb, int kb) {
-    return sa > sb || (sa == sb && ka < kb);
-}
-
-__device__ __forceinline__ bool key_in(const int64_t* keys, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int64_t v = keys[mid];
-        if (v == x) return true;
-        if (v < x) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
 // query qi's targets [tb, te), clamped to [0, n_tgt]
 __device__ __forceinline__ bool target_range(const int64_t* tptr, int64_t qi, int64_t n_tgt, int64_t& tb, int64_t& te) {
     tb = tptr[qi];
@@ -78,7 +57,7 @@ __device__ __forceinline__ bool target_range(const int64_t* tptr, int64_t qi, in
 // (an id outside [0, n), a self pair, a NaN logit).
 __device__ __forceinline__ bool target_logit(const float* z, const float* w, int n, int dim, int u, int v, float& s, int& key) {
     s = NAN;
-    key = SR_KEY_PAD;
+    key = WG_KEY_PAD;
     if (u < 0 || v < 0 || u >= n || v >= n || u == v) return false;
     const int a = u < v ? u : v, b = u < v ? v : u;
     const float* za = z + (int64_t)a * dim;
@@ -115,8 +94,8 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_init_kernel(ScreenRankArgs 
 }
 
 __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
-    __shared__ float As[SR_KC * SR_LD];
-    __shared__ float Zs[SR_KC * SR_LD];
+    __shared__ float As[WG_KC * WG_LD];
+    __shared__ float Zs[WG_KC * WG_LD];
     __shared__ float ts[SR_CHUNK];             // the chunk's targets, best first: logit, key, position in the chunk
     __shared__ int tk[SR_CHUNK];
     __shared__ int ti[SR_CHUNK];
@@ -135,41 +114,13 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
     int64_t tb, te;
     if (!target_range(a.tptr, qi, a.n_tgt, tb, te)) return;
 
-    // this part's share of the tiles (bu <= bv) of the upper triangle in row-major order
-    const int nb = (n + SR_TILE - 1) / SR_TILE;
-    const int64_t n_tiles = (int64_t)nb * (nb + 1) / 2;
-    const int64_t t0 = n_tiles * part / a.splits, t1 = n_tiles * (part + 1) / a.splits;
-    if (t0 >= t1) return;
-    int bu0 = 0;
-    int64_t row_start = 0;                                      // linear index of tile (bu0, bu0)
-    while (t0 >= row_start + (nb - bu0)) { row_start += nb - bu0; ++bu0; }
-    const int bv0 = bu0 + (int)(t0 - row_start);
+    // this part's share of the tiles of the upper triangle
+    const WgDeal deal0(n, part, a.splits);
+    if (deal0.t0 >= deal0.t1) return;
 
     for (int i = t; i < dim; i += SR_NT) wl[i] = a.w[(int64_t)r * dim + i];
-    const uint32_t* bits = nullptr;
-    const int64_t* keys = nullptr;
-    int64_t klo = 0, khi = 0;
-    if (a.keys) {
-        klo = a.kptr[r];
-        khi = a.kptr[r + 1];
-        if (a.bitmap) {
-            const int words = (int)(((int64_t)n * n + 31) / 32);
-            for (int i = t; i < words; i += SR_NT) bm[i] = 0u;
-            __syncthreads();                                   // cleared before any bit is set
-            const int64_t nn = (int64_t)n * n;
-            for (int64_t e = klo + t; e < khi; e += SR_NT) {
-                const int64_t key = a.keys[e];
-                if (key < 0 || key >= nn) continue;
-                const int x = (int)(key / n), y = (int)(key % n);
-                const uint32_t b0 = (uint32_t)(x * n + y), b1 = (uint32_t)(y * n + x);
-                atomicOr(&bm[b0 >> 5], 1u << (b0 & 31));
-                atomicOr(&bm[b1 >> 5], 1u << (b1 & 31));
-            }
-            bits = bm;
-        } else {
-            keys = a.keys;
-        }
-    }
+    WgKnown known;
+    known.build<SR_NT>(bm, a.keys, a.kptr, r, n, a.bitmap);
     const int ty = t >> 4, tx = t & 15;
 
     for (int64_t ch = tb; ch < te; ch += SR_CHUNK) {
@@ -182,7 +133,7 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
             hist[i] = 0u;
             if (i >= p) continue;
             float s = NAN;
-            int key = SR_KEY_PAD;
+            int key = WG_KEY_PAD;
             const bool ok = i < cnt && target_logit(a.z, wl, n, dim, a.tu[ch + i], a.tv[ch + i], s, key);
             ts[i] = ok ? s : -INFINITY;
             tk[i] = key;
@@ -190,68 +141,22 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
             if (ok) atomicAdd(&n_ranked, 1);
         }
         __syncthreads();
-        for (int size = 2; size <= p; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int x = t; x < (p >> 1); x += SR_NT) {
-                    const int i = 2 * stride * (x / stride) + (x % stride), j = i + stride;
-                    const float si = ts[i], sj = ts[j];
-                    const int ki = tk[i], kj = tk[j];
-                    const bool up = (i & size) == 0;
-                    if (up ? better(sj, kj, si, ki) : better(si, ki, sj, kj)) {
-                        const int ii = ti[i];
-                        ts[i] = sj; tk[i] = kj; ti[i] = ti[j];
-                        ts[j] = si; tk[j] = ki; ti[j] = ii;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        wg_bitonic<SR_NT, true>(ts, tk, ti, p);
         const int m = n_ranked;                                // ranked targets: sorted positions [0, m)
         __syncthreads();                                       // everyone has read it before the next chunk clears it
         if (m == 0) continue;
         const float weak_s = ts[m - 1];
         const int weak_k = tk[m - 1];
 
-        int bu = bu0, bv = bv0;
-        for (int64_t tile = t0; tile < t1; ++tile) {
+        WgDeal deal = deal0;
+        for (int64_t tile = deal.t0; tile < deal.t1; ++tile) {
             float acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-            for (int k0 = 0; k0 < dim; k0 += SR_KC) {
-                const int kc = dim - k0 < SR_KC ? dim - k0 : SR_KC;
-                __syncthreads();                                 // the previous chunk of columns has been read
-                for (int idx = t; idx < 2 * SR_TILE * (SR_KC / 4); idx += SR_NT) {
-                    const int which = idx / (SR_TILE * (SR_KC / 4));
-                    const int rem = idx % (SR_TILE * (SR_KC / 4));
-                    const int row = rem >> 3, qd = rem & 7;
-                    if (4 * qd >= kc) continue;
-                    const int node = (which == 0 ? bu : bv) * SR_TILE + row;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (node < n) v = tipk_ld4(a.z + (int64_t)node * dim + k0 + 4 * qd);
-                    float* dst = which == 0 ? As : Zs;
-                    if (which == 0) {
-                        const int kk = k0 + 4 * qd;
-                        v.x *= wl[kk]; v.y *= wl[kk + 1]; v.z *= wl[kk + 2]; v.w *= wl[kk + 3];
-                    }
-                    dst[(4 * qd + 0) * SR_LD + row] = v.x;
-                    dst[(4 * qd + 1) * SR_LD + row] = v.y;
-                    dst[(4 * qd + 2) * SR_LD + row] = v.z;
-                    dst[(4 * qd + 3) * SR_LD + row] = v.w;
-                }
-                __syncthreads();
-                for (int kk = 0; kk < kc; ++kk) {
-                    const float4 av = *reinterpret_cast<const float4*>(&As[kk * SR_LD + 4 * ty]);
-                    const float4 zv = *reinterpret_cast<const float4*>(&Zs[kk * SR_LD + 4 * tx]);
-                    const float ar[4] = {av.x, av.y, av.z, av.w}, zr[4] = {zv.x, zv.y, zv.z, zv.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(ar[i], zr[j], acc[i][j]);
-                }
-            }
-            const int u0 = bu * SR_TILE + 4 * ty, v0 = bv * SR_TILE + 4 * tx;
+            wg_score_tile(As, Zs, a.z, wl, n, dim, deal.bu, deal.bv, acc);
+            const int u0 = deal.bu * WG_TILE + 4 * ty, v0 = deal.bv * WG_TILE + 4 * tx;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -261,11 +166,7 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
                     const float s = acc[i][j];
                     const int key = u * n + v;
                     if (!better(s, key, weak_s, weak_k)) continue;
-                    if (bits) {
-                        if ((bits[(uint32_t)key >> 5] >> ((uint32_t)key & 31)) & 1u) continue;
-                    } else if (keys) {
-                        if (key_in(keys, klo, khi, (int64_t)u * n + v) || key_in(keys, klo, khi, (int64_t)v * n + u)) continue;
-                    }
+                    if (known.known(u, v)) continue;
                     int lo = 0, hi = m - 1;                      // it beats position m - 1: the first beaten one is in [0, m)
                     while (lo < hi) {
                         const int mid = (lo + hi) >> 1;
@@ -274,7 +175,7 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
                     atomicAdd(&hist[lo], 1u);
                 }
             }
-            if (++bv == nb) { ++bu; bv = bu; }
+            deal.next();
         }
         __syncthreads();                                       // every bucket is final
 
@@ -297,21 +198,6 @@ __global__ void __launch_bounds__(SR_NT) screen_rank_kernel(ScreenRankArgs a) {
             if (j < m && run > 0u) atomicAdd(&a.out_rank[ch + ti[j]], (int)run);
         }
     }
-}
-
-int64_t screen_rank_tiles(int64_t n) {
-    const int64_t nb = (n + SR_TILE - 1) / SR_TILE;
-    return nb * (nb + 1) / 2;
-}
-
-// parts per query, as the screen's: enough workgroups to fill the chip for few queries, one part per query for thousands
-int screen_rank_splits(int64_t n, int64_t n_q) {
-    int64_t s = n_q > 0 ? SR_TARGET_WG / n_q : 1;
-    if (s < 1) s = 1;
-    if (s > SR_SPLIT_MAX) s = SR_SPLIT_MAX;
-    const int64_t tiles = screen_rank_tiles(n);
-    if (s > tiles) s = tiles;
-    return (int)s;
 }
 
 }  // namespace
@@ -346,7 +232,7 @@ extern "C" int tipk_distmult_screen_rank(const float* z, int64_t n_nodes, int di
     a.keys = known_keys; a.kptr = known_ptr;
     a.n_q = n_q; a.n_tgt = n_tgt;
     a.n = (int)n_nodes; a.dim = dim; a.n_rel = (int)n_rel;
-    a.splits = screen_rank_splits(n_nodes, n_q);
+    a.splits = wg_splits(n_nodes, n_q);
     a.bitmap = known_keys && tipk_distmult_screen_bitmap_route(n_nodes);
     a.out_rank = out_rank; a.out_logit = out_logit;
     if (n_q * a.splits > 0x7fffffffLL) return TIPK_EUNSUPPORTED;

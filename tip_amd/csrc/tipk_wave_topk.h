@@ -4,7 +4,7 @@
 //   logits     wt_stage_rows (LDS image, bank-spreading stride wt_stride), wt_write_row / wt_row16 (the wave's product row
 //              and its dim-16 register copy), wt_dot (THE fma chain, k ascending), wt_softplus (the noisy-or term)
 //   known      find_key, wt_lower_bound (64-ary searches), wt_merge_window (ids of a window -> bits), wt_bit
-//   rank       wt_target_range, wt_count_beaten, wt_write_rank, under the total order `better`
+//   rank       wt_target_range, wt_count_beaten, wt_write_rank, under the total order `better` (tipk_common.h)
 //   top-k      wt_flush_at, flush (bitonic cut to k); the ballot append and the padded write-out stay written out in the two
 //              top-k kernels, where as helpers (and with wt_bit) they cost the table variants 1 % (see
 //              profiles/wave_rows_refactor.md)
@@ -78,10 +78,6 @@ __device__ __forceinline__ void wave_sync() {                  // LDS written by
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool better(float sa, int ra, float sb, int rb) {
-    return sa > sb || (sa == sb && ra < rb);
 }
 
 // rows [row0, row0 + rows) of src [. x dim] into the LDS image Ws (row stride `stride` floats), by the whole workgroup of
