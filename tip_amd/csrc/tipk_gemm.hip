@@ -650,7 +650,19 @@ __global__ __launch_bounds__(1024) void sum_slabs_group_kernel(SlabGroupArgs sa)
 // the partial tiles are added through LDS in wave order (deterministic) and the epilogue (alpha, c_in, ReLU, gate) is
 // applied once.  Ordered slab sums that are ready at the same point (the d att slabs of tipk_rgcn_node_products) ride in
 // the same launch as further workgroups.
+//
+// Two refinements keep such a launch off one CU's four matrix pipes while the rest of the chip idles:
+//   * QUARTER TILES.  A job with few output tiles (4 mt nt batch <= WGK_QUARTER_MAX, a constant of the job's shape alone, so
+//     a product computes the same bits alone and in any group) gives one workgroup to each 16 x 16 tile instead:
+//     v_mfma_f32_16x16x4_f32, 8 operand registers per K tile and side, so ALL (<= 4) tiles of a wave's run are requested
+//     before the first MFMA.  dX of layer 2 (645 x 32) is 82 workgroups instead of 21.
+//   * PACKED K.  Batch terms of k <= 16 on the 16-byte path (dX of layer 2: k = d_out = 16) would fill half a K tile with
+//     masked zeros; two consecutive terms share one tile instead (lanes of the lower k half: term 2t, upper: term 2t + 1).
+// The epilogue's c_in and gate values are requested before the K loop by the thread that will use them.
 constexpr int WGK_MAX = 4, WGK_SUMS = 3, WGK_WAVES = 16;
+// 192 would take dX of layer 1 (168) as well: 7.3 us alone instead of 12.6, but 236 product workgroups in the launch that
+// also carries both d att slab sums (9.7 us alone, 18 workgroups) ran 18.5 us against 16.4 (profiles/wg_tail.md)
+constexpr int WGK_QUARTER_MAX = 128;
 
 struct WgkJob {
     const float* a; int64_t a_sm, a_sk, a_sq, a_sz;
@@ -661,17 +673,174 @@ struct WgkJob {
     const float* c_in; int64_t cin_sm, cin_sz;
     const float* gate; int64_t gate_sm, gate_sz;        // nullable: out = gate > 0 ? value : 0
     int m, n, k, k2, kbatch;
-    int mt, nt;                                         // output tiles
-    int tiles_q, n_kt, per, nw;                         // K tiles per batch term, in all, per wave; waves with work
-    int vec1, vec2;                                     // both operands of the (first / second) product are contiguous in k
+    int mt, nt;                                         // output tiles of the job's body (32 x 32, quarter: 16 x 16)
+    int tiles_q, n_first, n_kt, per, nw;                // K tiles per batch term, of the first product, in all, per wave; waves with work
+    int vec;                                            // 16-byte loads: the operands of every product of the job are contiguous in k
+    int quarter, pack;                                  // 16 x 16 tiles; two batch terms of k <= 16 per K tile (vec only)
     float alpha; int relu;
 };
 struct WgkArgs {
     int n_gemm, n_sum;
+    int dbg;                                            // debug builds ("dp_debug"): 4096 no MFMAs, 8192 no operand loads, 16384 no epilogue
+                                                        // loads, 32768 (host) every job on 32 x 32 tiles with unpacked K
     int first[WGK_MAX + WGK_SUMS + 1];
     WgkJob g[WGK_MAX];
     SlabArgs s[WGK_SUMS];
 };
+
+// One workgroup of a product: output tile `local` of job g.  QT: the 16 x 16 body (v_mfma_f32_16x16x4_f32, lane = row + 16 x
+// k quarter), else the 32 x 32 body (v_mfma_f32_32x32x2_f32, lane = row + 32 x k half).  Per K tile of 32 and operand a lane
+// holds L = 8 / 16 registers; the 16 x 16 body keeps every tile of its run (NB = 4: n_kt <= 64) in flight, the 32 x 32 body two.
+// VEC: 16-byte operand loads, a property of the JOB (every product of it is contiguous in k) and not a branch per tile: with
+// both layouts behind one runtime flag hipcc merged the tails of the two branches -- the 16-byte loads of B were split into
+// the dwords of the other layout (dX of layer 1 alone 13.1 us, 7.9 us with the layouts apart).
+template <bool QT, bool VEC>
+__device__ __forceinline__ void wgk_body(const WgkJob& g, int local, float* red, int dbg) {
+    constexpr int T = QT ? 16 : 32, L = QT ? 8 : 16, G = 32 / L, NACC = QT ? 4 : 16, NB = QT ? 4 : 2;
+    typedef float acc_t __attribute__((ext_vector_type(NACC)));
+    const int nt_i = local % g.nt, mt_i = (local / g.nt) % g.mt, z = local / (g.nt * g.mt);
+    const int t = threadIdx.x, lane = t & 63, row = lane & (T - 1), kg = lane / T;
+    const int w = uniform(t >> 6);
+    const int m0 = mt_i * T, n0 = nt_i * T;
+    const u32 am = (u32)(m0 + row < g.m ? m0 + row : g.m - 1), bn = (u32)(n0 + row < g.n ? n0 + row : g.n - 1);
+    const u32 m_mask = m0 + row < g.m ? 0xffffffffu : 0u;
+
+    // the element this thread finishes after the cross-wave sum (the accumulator layout, register er of lane el), and what its
+    // epilogue reads: requested here, in front of the K loop, not as one more dependent round trip behind the barrier
+    const int er = t >> 6, el = t & 63;
+    const int rr = QT ? m0 + 4 * (el >> 4) + er : m0 + (er & 3) + 8 * (er >> 2) + 4 * (el >> 5), cc = n0 + (el & (T - 1));
+    const bool mine = t < 64 * NACC && rr < g.m && cc < g.n;
+    float cin_v = 0.f, gate_v = 1.f;
+    if (mine && !TIPK_DBG(dbg & 16384)) {
+        if (g.c_in) cin_v = g.c_in[(int64_t)z * g.cin_sz + (int64_t)rr * g.cin_sm + cc];
+        if (g.gate) gate_v = g.gate[(int64_t)z * g.gate_sz + (int64_t)rr * g.gate_sm + cc];
+    }
+
+    acc_t acc;
+#pragma unroll
+    for (int r = 0; r < NACC; ++r) acc[r] = 0.f;
+    // What a tile of the first or of the second product reads, as copies captured by value and (in `load`) chosen with a mask:
+    // hipcc turned `second ? g.a2_sk : g.a_sk` into a load from a selected ADDRESS inside a copy of g in scratch memory, and
+    // the wait for that load (loads return in order) drains every operand load in flight: tiles were fetched one by one.
+    const float* const a_1 = g.a + (int64_t)z * g.a_sz, * const b_1 = g.b + (int64_t)z * g.b_sz, * const a_2 = g.a2, * const b_2 = g.b2;
+    const int64_t a_sq = g.a_sq, b_sq = g.b_sq;
+    const u32 am_1 = (u32)g.a_sm, ak_1 = (u32)g.a_sk, bk_1 = (u32)g.b_sk, bn_1 = (u32)g.b_sn;
+    const u32 am_2 = (u32)g.a2_sm, ak_2 = (u32)g.a2_sk, bk_2 = (u32)g.b2_sk, bn_2 = (u32)g.b2_sn;
+    const int k_1 = g.k, k_2 = g.k2, n_first = g.n_first, tiles_q = g.tiles_q, kbatch = g.kbatch, pack = g.pack;
+    // Which k a lane's register kk holds is free as long as both operands agree: when ALL are contiguous in k (dX: rows of
+    // dXB against rows of basis, rows of g against rows of root) lane group kg takes k0 + L kg .. + L - 1 as 16-byte loads -- a dword per (row, k) made
+    // every load touch 32 lines for 4 useful bytes each: 31.7 us for the dX product alone (tools/bench_wg_gemm.py).
+    // lim: register kk holds a term of the sum iff kk < lim.
+    auto load = [=](int tile, float (&av)[L], float (&bv)[L], int& lim) __attribute__((always_inline)) {
+        if (TIPK_DBG(dbg & 8192)) {
+#pragma unroll
+            for (int kk = 0; kk < L; ++kk) av[kk] = bv[kk] = (float)(lane + kk);
+            lim = L;
+            return;
+        }
+        const bool second = tile >= n_first;
+        const bool packed = !second && pack;
+        const int tq = second ? tile - n_first : tile;
+        const int q = second ? 0 : packed ? 2 * tq : tq / tiles_q;
+        const int k0 = (second ? tq : packed ? 0 : tq - q * tiles_q) * 32;
+        // first or second product: a mask the compiler cannot see through (as plain selects on `second` some of these
+        // still went through a two-entry table in scratch memory)
+        u32 pick = (u32)uniform(second ? -1 : 0);
+        asm volatile("" : "+s"(pick));
+        const auto sel = [pick](u32 x1, u32 x2) { return (x2 & pick) | (x1 & ~pick); };
+        const auto selp = [pick](const float* p1, const float* p2) {
+            const uint64_t m = ((uint64_t)pick << 32) | pick;
+            typedef const __attribute__((address_space(1))) float* global_ptr;       // (global, not flat, loads)
+            return (const float*)reinterpret_cast<global_ptr>((reinterpret_cast<uint64_t>(p2) & m) | (reinterpret_cast<uint64_t>(p1) & ~m));
+        };
+        const int kk_total = (int)sel((u32)k_1, (u32)k_2);
+        const float* ap = selp(a_1 + (int64_t)q * a_sq, a_2);
+        const float* bp = selp(b_1 + (int64_t)q * b_sq, b_2);
+        const u32 s_am = sel(am_1, am_2), s_ak = sel(ak_1, ak_2), s_bk = sel(bk_1, bk_2), s_bn = sel(bn_1, bn_2);
+        u32 ao = am * s_am, bo = bn * s_bn;
+        if constexpr (VEC) {
+            int kofs = k0 + L * kg;                     // the lane's run of k inside its term
+            lim = kk_total - kofs;
+            if (packed) {                               // k <= 16: the upper half of the tile is batch term q + 1 (past the last: masked)
+                const int up = (L * kg) >> 4;
+                const bool there = q + up < kbatch;
+                kofs &= 15;
+                lim = there ? kk_total - kofs : 0;
+                if (up && there) { ao += (u32)a_sq; bo += (u32)b_sq; }
+            }
+#pragma unroll
+            for (int j = 0; j < L / 4; ++j) {
+                const int kb = kofs + 4 * j;
+                const u32 kc = (u32)(kb < kk_total ? kb : kk_total - 4);
+                const float4 xa = ldg4(ap, (ao + kc) * 4u), xb = ldg4(bp, (bo + kc) * 4u);
+                av[4 * j] = xa.x; av[4 * j + 1] = xa.y; av[4 * j + 2] = xa.z; av[4 * j + 3] = xa.w;
+                bv[4 * j] = xb.x; bv[4 * j + 1] = xb.y; bv[4 * j + 2] = xb.z; bv[4 * j + 3] = xb.w;
+            }
+            return;
+        }
+        const int left = kk_total - k0;                 // >= 1; register kk holds k0 + G kk + kg
+        lim = (left - kg + G - 1) / G;
+#pragma unroll
+        for (int kk = 0; kk < L; ++kk) {
+            const int kl = G * kk + kg;
+            const u32 kc = (u32)(k0 + (kl < left ? kl : left - 1));
+            av[kk] = ldg(ap, (ao + kc * s_ak) * 4u);
+            bv[kk] = ldg(bp, (kc * s_bk + bo) * 4u);
+        }
+    };
+    auto mma = [&](const float (&av)[L], const float (&bv)[L], int lim) __attribute__((always_inline)) {
+#pragma unroll
+        for (int kk = 0; kk < L; ++kk) {
+            if (TIPK_DBG(dbg & 4096)) {                 // the loads are still waited for
+                asm volatile("" : : "v"(av[kk]), "v"(bv[kk]));
+                continue;
+            }
+            const float x = and_mask(av[kk], kk < lim ? m_mask : 0u), y = and_mask(bv[kk], kk < lim ? 0xffffffffu : 0u);
+            if constexpr (QT) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, acc, 0, 0, 0);
+            else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, acc, 0, 0, 0);
+        }
+    };
+    const int t_lo = w * g.per, t_hi = t_lo + g.per < g.n_kt ? t_lo + g.per : g.n_kt;
+    if (t_lo < t_hi) {
+        float av[NB][L], bv[NB][L];
+        int lim[NB] = {};
+        if constexpr (QT) {
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+                if (t_lo + i < t_hi) load(t_lo + i, av[i], bv[i], lim[i]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+                if (t_lo + i < t_hi) mma(av[i], bv[i], lim[i]);
+        } else {
+            load(t_lo, av[0], bv[0], lim[0]);
+#pragma unroll 1
+            for (int tile = t_lo; tile < t_hi; tile += 2) {
+                if (tile + 1 < t_hi) load(tile + 1, av[1], bv[1], lim[1]);
+                __builtin_amdgcn_sched_barrier(0);
+                mma(av[0], bv[0], lim[0]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (tile + 1 < t_hi) {
+                    if (tile + 2 < t_hi) load(tile + 2, av[0], bv[0], lim[0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(av[1], bv[1], lim[1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < NACC; ++r) red[w * (64 * NACC) + r * 64 + lane] = acc[r];
+    }
+    __syncthreads();
+    if (!mine) return;
+    float s = g.nw > 0 ? red[t] : 0.f;
+    for (int q = 1; q < g.nw; ++q) s += red[q * (64 * NACC) + t];
+    s *= g.alpha;
+    if (g.c_in) s += cin_v;
+    if (g.relu) s = fmaxf(s, 0.f);
+    if (g.gate && !(gate_v > 0.f)) s = 0.f;
+    g.c[(int64_t)z * g.c_sz + (int64_t)rr * g.c_sm + cc] = s;
+}
 
 __global__ __launch_bounds__(1024) void gemm_wgk_group_kernel(WgkArgs wa) {
     __shared__ __attribute__((aligned(16))) float red[WGK_WAVES * 1024];
@@ -690,94 +859,12 @@ __global__ __launch_bounds__(1024) void gemm_wgk_group_kernel(WgkArgs wa) {
 #pragma unroll
     for (int q = 1; q < WGK_MAX; ++q)
         if (q < wa.n_gemm && blk >= wa.first[q]) { g = wa.g[q]; first = wa.first[q]; }
-    const int local = blk - first;
-    const int nt_i = local % g.nt, mt_i = (local / g.nt) % g.mt, z = local / (g.nt * g.mt);
-    const int t = threadIdx.x, lane = t & 63, row = lane & 31, kh = lane >> 5;
-    const int w = uniform(t >> 6);
-    const int m0 = mt_i * 32, n0 = nt_i * 32;
-    const int n_first = g.kbatch * g.tiles_q;           // K tiles of the first product
-    const u32 am = (u32)(m0 + row < g.m ? m0 + row : g.m - 1), bn = (u32)(n0 + row < g.n ? n0 + row : g.n - 1);
-    const u32 m_mask = m0 + row < g.m ? 0xffffffffu : 0u;
-
-    f32x16 acc = zero16();
-    float a0[16], b0[16], a1[16], b1[16];
-    int left0 = 0, left1 = 0;                           // valid k of the tile in each buffer (negative: the vector layout)
-    // Which k a lane's register kk holds is free as long as both operands agree: when BOTH are contiguous in k (dX: rows of
-    // dXB against rows of basis) lane half kh takes k0 + 16 kh .. + 15 as four 16-byte loads -- a dword per (row, k) made
-    // every load touch 32 lines for 4 useful bytes each: 31.7 us for the dX product alone (tools/bench_wg_gemm.py)
-    auto load = [&](int tile, float (&av)[16], float (&bv)[16], int& left) {
-        const bool second = tile >= n_first;
-        const int tq = second ? tile - n_first : tile;
-        const int q = second ? 0 : tq / g.tiles_q;
-        const int kt = second ? tq : tq - q * g.tiles_q;
-        const int kk_total = second ? g.k2 : g.k;
-        const int k0 = kt * 32;
-        left = kk_total - k0 < 32 ? kk_total - k0 : 32;
-        const float* ap = second ? g.a2 : g.a + (int64_t)z * g.a_sz + (int64_t)q * g.a_sq;
-        const float* bp = second ? g.b2 : g.b + (int64_t)z * g.b_sz + (int64_t)q * g.b_sq;
-        const u32 s_am = (u32)(second ? g.a2_sm : g.a_sm), s_ak = (u32)(second ? g.a2_sk : g.a_sk);
-        const u32 s_bk = (u32)(second ? g.b2_sk : g.b_sk), s_bn = (u32)(second ? g.b2_sn : g.b_sn);
-        const u32 ao = am * s_am, bo = bn * s_bn;
-        if (second ? g.vec2 : g.vec1) {                 // (uniform)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int kb = 16 * kh + 4 * j;
-                const u32 kc = (u32)(k0 + (kb < left ? kb : left - 4));
-                const float4 xa = ldg4(ap, (ao + kc) * 4u), xb = ldg4(bp, (bo + kc) * 4u);
-                av[4 * j] = xa.x; av[4 * j + 1] = xa.y; av[4 * j + 2] = xa.z; av[4 * j + 3] = xa.w;
-                bv[4 * j] = xb.x; bv[4 * j + 1] = xb.y; bv[4 * j + 2] = xb.z; bv[4 * j + 3] = xb.w;
-            }
-            left = -left;
-            return;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            const int kl = 2 * kk + kh;
-            const u32 kc = (u32)(k0 + (kl < left ? kl : left - 1));
-            av[kk] = ldg(ap, (ao + kc * s_ak) * 4u);
-            bv[kk] = ldg(bp, (kc * s_bk + bo) * 4u);
-        }
-    };
-    auto mma = [&](const float (&av)[16], const float (&bv)[16], int left) {
-        const int lim = left < 0 ? -left - 16 * kh : left - kh;     // register kk is valid: kk < lim (vector) / 2 kk < lim
-        const int step = left < 0 ? 1 : 2;
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(and_mask(av[kk], step * kk < lim ? m_mask : 0u),
-                                                       and_mask(bv[kk], step * kk < lim ? 0xffffffffu : 0u), acc, 0, 0, 0);
-    };
-    const int t_lo = w * g.per, t_hi = t_lo + g.per < g.n_kt ? t_lo + g.per : g.n_kt;
-    if (t_lo < t_hi) {
-        load(t_lo, a0, b0, left0);
-#pragma unroll 1
-        for (int tile = t_lo; tile < t_hi; tile += 2) {
-            if (tile + 1 < t_hi) load(tile + 1, a1, b1, left1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(a0, b0, left0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (tile + 1 < t_hi) {
-                if (tile + 2 < t_hi) load(tile + 2, a0, b0, left0);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a1, b1, left1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[w * 1024 + r * 64 + lane] = acc[r];
-    }
-    __syncthreads();
-    {
-        float s = g.nw > 0 ? red[t] : 0.f;
-        for (int q = 1; q < g.nw; ++q) s += red[q * 1024 + t];
-        const int r = t >> 6, l = t & 63;
-        const int rr = m0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), cc = n0 + (l & 31);
-        if (rr < g.m && cc < g.n) {
-            s *= g.alpha;
-            if (g.c_in) s += g.c_in[(int64_t)z * g.cin_sz + (int64_t)rr * g.cin_sm + cc];
-            if (g.relu) s = fmaxf(s, 0.f);
-            if (g.gate && !(g.gate[(int64_t)z * g.gate_sz + (int64_t)rr * g.gate_sm + cc] > 0.f)) s = 0.f;
-            g.c[(int64_t)z * g.c_sz + (int64_t)rr * g.c_sm + cc] = s;
-        }
+    if (g.quarter) {                                    // (uniform, as is g.vec)
+        if (g.vec) wgk_body<true, true>(g, blk - first, red, wa.dbg);
+        else wgk_body<true, false>(g, blk - first, red, wa.dbg);
+    } else {
+        if (g.vec) wgk_body<false, true>(g, blk - first, red, wa.dbg);
+        else wgk_body<false, false>(g, blk - first, red, wa.dbg);
     }
 }
 
@@ -957,14 +1044,25 @@ static int fill_wgk(const tipk_wg_gemm_desc& d, WgkJob& j) {
     j.c_in = p.c_in; j.cin_sm = p.cin_sm; j.cin_sz = p.cin_sz;
     j.gate = d.gate; j.gate_sm = d.gate_sm; j.gate_sz = d.gate_sz;
     j.m = (int)p.m; j.n = (int)p.n; j.k = (int)p.k; j.k2 = second ? (int)d.k2 : 0; j.kbatch = (int)p.kbatch;
-    j.mt = (int)mt; j.nt = (int)nt;
-    j.tiles_q = (int)tiles_q; j.n_kt = (int)n_kt;
-    j.per = (int)tipk_ceil_div(n_kt, WGK_WAVES);
-    j.nw = (int)tipk_ceil_div(n_kt, j.per);
     j.alpha = p.alpha; j.relu = p.relu;
     const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    j.vec1 = p.a_sk == 1 && p.b_sk == 1 && p.k % 4 == 0 && ((p.a_sm | p.b_sn | p.a_sq | p.b_sq | p.a_sz | p.b_sz) & 3) == 0 && al16(p.a) && al16(p.b);
-    j.vec2 = second && d.a2_sk == 1 && d.b2_sk == 1 && d.k2 % 4 == 0 && ((d.a2_sm | d.b2_sn) & 3) == 0 && al16(d.a2) && al16(d.b2);
+    const bool vec1 = p.a_sk == 1 && p.b_sk == 1 && p.k % 4 == 0 && ((p.a_sm | p.b_sn | p.a_sq | p.b_sq | p.a_sz | p.b_sz) & 3) == 0 && al16(p.a) && al16(p.b);
+    const bool vec2 = second && d.a2_sk == 1 && d.b2_sk == 1 && d.k2 % 4 == 0 && ((d.a2_sm | d.b2_sn) & 3) == 0 && al16(d.a2) && al16(d.b2);
+    // Which body and which K layout: a rule of the job's own shape and strides (never of the group it is launched in), so that a
+    // product gives the same bits wherever it runs.  The limits above keep counting 32 x 32 tiles and unpacked K tiles.
+    const bool legacy = TIPK_DBG(tipk_option(TIPK_OPT_DP_DEBUG) & 32768) != 0;
+    j.quarter = !legacy && 4 * mt * nt * p.batch <= WGK_QUARTER_MAX;
+    // the upper half of a packed tile is addressed as a 32-bit offset from the lower half's term
+    j.vec = (vec1 || p.k == 0) && (vec2 || !second);
+    j.pack = !legacy && j.vec && p.k > 0 && p.k <= 16 && p.kbatch > 1 && p.a_sq >= 0 && p.b_sq >= 0 &&
+             p.a_sq + p.m * p.a_sm + p.k < lim && p.b_sq + p.n * p.b_sn + p.k < lim;
+    const int64_t n_first = j.pack ? tipk_ceil_div(p.kbatch, 2) : p.kbatch * tiles_q;
+    const int64_t n_run = n_first + (n_kt - p.kbatch * tiles_q);           // K tiles as the kernel walks them
+    const int edge = j.quarter ? 16 : 32;
+    j.mt = (int)tipk_ceil_div(p.m, edge); j.nt = (int)tipk_ceil_div(p.n, edge);
+    j.tiles_q = (int)tiles_q; j.n_first = (int)n_first; j.n_kt = (int)n_run;
+    j.per = (int)tipk_ceil_div(n_run, WGK_WAVES);
+    j.nw = (int)tipk_ceil_div(n_run, j.per);
     return TIPK_OK;
 }
 
@@ -978,6 +1076,7 @@ extern "C" int tipk_gemm_wg_group(const tipk_wg_gemm_desc* descs, int32_t count,
     if (count < 0 || count > WGK_MAX || n_sums < 0 || n_sums > WGK_SUMS || (count > 0 && !descs) || (n_sums > 0 && !sums)) return TIPK_EINVAL;
     WgkArgs wa;
     wa.n_gemm = count; wa.n_sum = 0;
+    wa.dbg = TIPK_DBG(tipk_option(TIPK_OPT_DP_DEBUG));
     int64_t blocks = 0;
     for (int i = 0; i < count; ++i) {
         const int rc = fill_wgk(descs[i], wa.g[i]);
