@@ -1383,6 +1383,99 @@ int     tipk_pair_table_partner_sum(const float* s1t, const float* s2t, int64_t 
                                     int k, float* out_sum, int32_t* out_count, float* out_top_val /* nullable with k == 0 */,
                                     int32_t* out_top_pos /* nullable with k == 0 */, tipk_stream_t stream);
 
+/* 4m. Fit of decoder rows for NEW side effects with the trained model frozen (serving; no reference call site): the
+ *     missing row of the DistMult decoder of 4a for a side effect the model was not trained on, from its recorded pairs.
+ *
+ *   Objective of new side effect b with row w, s(u,v) = sum_k z[u,k] z[v,k] w[k] -- the expectation of the training
+ *   objective over its one uniform negative per positive (tip_amd/neg_sampling.py), with the exact softplus:
+ *     L_b(w) = sum_{distinct recorded p} wpos_p softplus(-s_p)
+ *            + dense_w[b] * sum_{ordered (u,v) in [0,n)^2 NOT recorded} softplus(s)  +  l2/2 |w|^2
+ *   evaluated as  dense_w[b] * sum over ALL unordered u <= v of m softplus(s), m = 2 (1 for u == v)  -- a mask-free stream --
+ *   plus, per distinct recorded unordered pair, wpos_p softplus(-s_p) - wneg_p softplus(s_p): wpos = multiplicity / P_b,
+ *   wneg = dense_w[b] * (ordered multiplicity 2 | 1), dense_w[b] = neg_weight / N_b (tip_amd.ops.fit_pairs_csr builds them).
+ *
+ *   tipk_distmult_fit_stats.  Input, DEVICE: z [n_nodes x dim] dense, 16-byte aligned; the trial rows w [n_fit x dim];
+ *   dense_w fp32 [n_fit]; the distinct recorded pairs as CSR: pair_ptr int64 [n_fit + 1], pair_u / pair_v int32 [n_pairs] in
+ *   [0, n_nodes) (the caller's contract; an id outside is clamped, nothing is read out of bounds), pair_wpos / pair_wneg
+ *   fp32 [n_pairs]; l2 >= 0; active int32 [n_fit], nullable (NULL: every relation).  Output: loss [n_fit], grad
+ *   [n_fit x dim], hess [n_fit x dim x dim] (row-major, both triangles), the l2 terms included.  Rows of an inactive
+ *   relation are NOT touched.
+ *   Arithmetic, fp32.  Feature f_k = z[u,k] * z[v,k] rounded once; logit: acc = fmaf(f_k, w[k], acc), k ascending from
+ *   +0.0f; e = expf(-|s|), r = 1.0f / (1.0f + e): softplus(s) = fmaxf(s, 0) + log1pf(e), sigma(s) = r (s >= 0) | e r,
+ *   sigma'(s) = e r r.  Terms: loss c softplus, gradient c sigma f_i, Hessian c sigma' f_i f_j with c = m dense_w[b].
+ *   Summation order.  Tiles of 64 x 64 pairs (u-block, v-block >= u-block) are numbered u-block major; the tiles are cut
+ *   into tipk_distmult_fit_slabs(n_nodes, dim, n_fit) SLABS of equal length (the last may be shorter).  In a tile wavefront
+ *   q of 4 owns the rows u = 16 q .. 16 q + 15, in ascending order; within a row the gradient and Hessian entries take the
+ *   64 pairs in v order on v_mfma_f32_16x16x4_f32 with the pairs as K (an exact fmaf chain), the loss lane v adds its own
+ *   term and the 64 lanes are summed at the end of the slab by the halving tree.  One accumulator per (slab, wavefront)
+ *   runs through the slab: at most 1 024 terms per tile.  Then, per output, the 4 * slabs partials are added in ascending
+ *   (slab, wavefront) order from +0.0f; the recorded pairs are summed in chunks of 256 (a chain from +0.0f in list order,
+ *   the chunk totals added in ascending order from +0.0f); result = dense + sparse, then + l2 term (loss: l2/2 times the
+ *   fmaf chain of w_k^2; gradient: + l2 w_i; Hessian diagonal: + l2).
+ *   tipk_distmult_fit_max_chain(n_nodes, dim, n_fit) = D, the largest number of fp32 additions a term passes through:
+ *     max(1 024 * tiles per slab + 6 + 4 * slabs,  256 + ceil(n (n + 1) / 2 / 256)) + 2.
+ *   Slabs and D depend on (n_nodes, dim, n_fit) alone.  No floating-point atomics, no workgroup waits for another: the
+ *   results are BITWISE repeatable call to call.
+ *   A NaN logit makes every statistic of ITS relation NaN and touches no other relation (a NaN row of z reaches every
+ *   relation; a NaN in one trial row only that relation).
+ *   An INFINITE z[u,k] (no NaN logit; w[k] != 0, the other entries of column k != 0) gives logits of +-inf on row u: for
+ *   every relation that sees the row -- dense_w[b] > 0, or a recorded pair on u -- grad[k] and row k and column k of hess
+ *   are non-finite (+inf or NaN: sigma' = 0 meets an infinite feature), so tipk_newton_step ends that relation with
+ *   status 3; the loss is +inf or NaN as soon as one unrecorded pair has the logit +inf or one recorded pair -inf; every
+ *   other entry of grad and hess stays finite.  Nothing finite is invented.
+ *   Work: a dense launch of slabs x ceil(n_fit / 4) workgroups -- the feature of a pair is computed once for the 4 relations
+ *   of the block; both row blocks of a tile are staged in LDS (rows 16-byte aligned, stride width + 4 floats) -- then a
+ *   finishing launch of one workgroup per relation.  A workgroup whose relations are all inactive returns at once.
+ *   workspace: tipk_distmult_fit_workspace_bytes(n_nodes, dim, n_fit) bytes (-1: unsupported; n_fit == 0: 0), which also
+ *   holds the state of tipk_distmult_fit; the statistics entry uses its head.
+ *
+ *   tipk_newton_step.  One wavefront per relation; all state in caller-provided DEVICE arrays: the accepted row w
+ *   [n_fit x dim], its loss [n_fit] and grad [n_fit x dim], the direction p [n_fit x dim], the step t [n_fit], info int32
+ *   [n_fit x 4] = (status, evaluations, accepted, rejected), the trial row w_trial [n_fit x dim] and active int32 [n_fit].
+ *   Before the first call: info = 0, t = 1, w = w_trial = the start.  Given the statistics at w_trial:
+ *     a relation whose status is not 0: active = 0, nothing else.
+ *     evaluations == 0:  the trial is taken as accepted (it is the start).
+ *     else accept iff  loss_trial <= loss + 1e-4f * t * (g . p) + 16 * 2^-24 * |loss|   (g . p: xor-butterfly sum).
+ *     accepted: (w, loss, grad) <- trial;  p <- -H^-1 g by Cholesky (column order; a pivot that is not > 0, or not finite:
+ *               p <- -g / max_i H_ii, or -g when that maximum is not > 0);  t <- 1.     rejected: t <- t / 2.
+ *     a non-finite statistic: status 3; the accepted row is kept and the trial counts as rejected (at the first call the
+ *               trial is the start: it is kept and nothing is counted).
+ *     then status 1 if max_i |grad_i| <= gtol, else 2 if t < 2^-20, else 0; evaluations += 1.
+ *     status 0: w_trial <- fmaf(t, p, w) and active = 1; otherwise active = 0.
+ *   evaluations = accepted + rejected + 1 at all times after the first call.
+ *
+ *   tipk_distmult_fit.  Enqueues one initialising launch (start = init [n_fit x dim], NULL: zeros) and max_iter + 1
+ *   (statistics, step) pairs on `stream`; the active mask makes a finished relation's workgroups return at once.  Output:
+ *   out_w [n_fit x dim], out_loss [n_fit], out_grad [n_fit x dim] = the accepted row and its statistics, out_info int32
+ *   [n_fit x 4] as above (status 0 after max_iter + 1 evaluations: not converged).
+ *   Supported: 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..32 (widths below 16 | 32 zero-padded on chip), 1 <= n_fit <=
+ *   65 536; z 16-byte aligned.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes or dim < 1, l2 < 0 or NaN,
+ *   gtol < 0 or NaN, max_iter < 0, a NULL required pointer (with n_fit > 0: everything but `active`, `init` and, with
+ *   n_pairs == 0, the four pair arrays); then TIPK_EUNSUPPORTED outside the supported range; n_fit == 0 is TIPK_OK with no
+ *   launch and nothing written.
+ *   Nothing lives in host memory: the entries do NOT synchronise or allocate and may be captured into a hipGraph
+ *   (sequential launches, no parallel branches).
+ */
+int     tipk_distmult_fit_supported(int64_t n_nodes, int dim, int64_t n_fit);
+int64_t tipk_distmult_fit_slabs(int64_t n_nodes, int dim, int64_t n_fit);            /* -1 unsupported */
+int64_t tipk_distmult_fit_max_chain(int64_t n_nodes, int dim, int64_t n_fit);        /* -1 unsupported */
+int64_t tipk_distmult_fit_workspace_bytes(int64_t n_nodes, int dim, int64_t n_fit);  /* -1 unsupported */
+int     tipk_distmult_fit_stats(const float* z, int64_t n_nodes, int dim, const float* w, int64_t n_fit,
+                                const float* dense_w, const int64_t* pair_ptr /* [n_fit+1] */, const int32_t* pair_u,
+                                const int32_t* pair_v, const float* pair_wpos, const float* pair_wneg, int64_t n_pairs,
+                                float l2, const int32_t* active /* nullable */, float* loss, float* grad, float* hess,
+                                void* workspace, tipk_stream_t stream);
+int     tipk_newton_step(int dim, int64_t n_fit, const float* stat_loss, const float* stat_grad, const float* stat_hess,
+                         float gtol, float* w, float* loss, float* grad, float* p, float* t, int32_t* info,
+                         float* w_trial, int32_t* active, tipk_stream_t stream);
+int     tipk_distmult_fit(const float* z, int64_t n_nodes, int dim, int64_t n_fit, const float* dense_w,
+                          const int64_t* pair_ptr /* [n_fit+1] */, const int32_t* pair_u, const int32_t* pair_v,
+                          const float* pair_wpos, const float* pair_wneg, int64_t n_pairs, float l2,
+                          const float* init /* nullable: zeros */, int max_iter, float gtol,
+                          float* out_w, float* out_loss, float* out_grad, int32_t* out_info, void* workspace,
+                          tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

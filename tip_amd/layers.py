@@ -35,6 +35,8 @@ ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 Explanation = namedtuple('Explanation', ['logit', 'offset', 'own', 'neighbours', 'contribution', 'partner', 'relation', 'degree'])
 NewDrugs = namedtuple('NewDrugs', ['x0', 'h', 'z', 'degree', 'n_targets'])
+# TIP.fit_side_effects' result: per new side effect its fitted DistMult row and how the fit ended
+NewSideEffects = namedtuple('NewSideEffects', ['weight', 'loss', 'grad_norm', 'evaluations', 'status', 'n_pairs', 'decoder', 'known'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
 # TIP.drug_profile's result: per queried drug the expected number of unrecorded partners for every side effect column
@@ -42,7 +44,7 @@ DrugProfile = namedtuple('DrugProfile', ['expected', 'candidates', 'top_expected
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
-           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP']
+           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects']
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1757,6 +1759,62 @@ class TIP(nn.Module):
                                            (r1.basis.detach(), r1.att.detach(), r1.root.detach()),
                                            (r2.basis.detach(), r2.att.detach(), r2.root.detach()), xd.contiguous(), tgt, inter, cat)
             return NewDrugs(x0n, hn, zn, inter[0][1:] - inter[0][:-1], tgt[0][1:] - tgt[0][:-1])
+
+    def fit_side_effects(self, pairs, l2=1e-4, neg_weight=1.0, init=None, max_iter=16, gtol=1e-5, new=None):
+        """Learn side effects the model was NOT trained on (extension): one row of the DistMult decoder per new side effect
+        from its recorded drug pairs, with the embeddings frozen (`ops.distmult_fit`: one `tipk_distmult_fit` call enqueues
+        every Newton step for all B rows; under no_grad on `self.embeddings`).
+        pairs: a list of B lists of (u, v), or (edge_index [2, P], ptr [B + 1]) (`ops.fit_pairs_csr`): unordered, duplicates
+        count.  The row minimises the expectation of the training objective over its negative draw,
+            1/P_b sum_listed softplus(-s) + neg_weight/N_b sum_{ordered (u, v) not recorded} softplus(s) + l2/2 |w|^2,
+        a convex problem in dim unknowns.  init: None (zeros) or [B, dim], e.g. the row of a related side effect.
+        new: the `NewDrugs` of `embed_new_drugs`; ids n_drug + i are then allowed and the fit runs on
+        torch.cat([self.embeddings, new.z]) -- every drug of the wider set is a negative partner too.
+        -> NewSideEffects(weight [B, dim], loss [B], grad_norm [B] (max |gradient|), evaluations int64 [B], status int64 [B]
+        (1 converged, 2 step underflow, 3 non-finite statistic, 0 not converged in max_iter + 1 evaluations), n_pairs int64
+        [B], decoder, known).  decoder: a detached `MultiInnerProductDecoder` of the B rows alone -- its relation i is new side
+        effect i; it is not registered in the model -- and known: the (keys, ptr) lists of the given pairs, both directions,
+        so that decoder.screen(z, k, known=known) lists the most likely UNRECORDED pairs of each new side effect and
+        decoder.partner_sums(...) gives its liability column.
+        NotImplementedError for the NN decoder (the rows fitted are DistMult rows), a relation-sharded model, or widths
+        `tipk_distmult_fit_supported` refuses; ValueError for l2 < 0, neg_weight <= 0, max_iter < 0, an id out of range or an
+        `init` of the wrong shape."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('fit_side_effects fits DistMult rows; this model scores with the NN decoder')
+        _refuse_sharded(self.shard, 'new side effects')
+        if not float(l2) >= 0:
+            raise ValueError('l2 must be >= 0, not %r' % (l2,))
+        if not float(neg_weight) > 0:
+            raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
+        if int(max_iter) < 0:
+            raise ValueError('max_iter must be >= 0, not %r' % (max_iter,))
+        if not float(gtol) >= 0:
+            raise ValueError('gtol must be >= 0, not %r' % (gtol,))
+        n_all = self.data.n_drug + (0 if new is None else int(new.z.shape[0]))
+        fp = ops.fit_pairs_csr(pairs, n_all, neg_weight)
+        b, dim = fp.dense_w.numel(), self.decoder.in_dim
+        if init is not None:
+            init = torch.as_tensor(init)
+            if tuple(init.shape) != (b, dim):
+                raise ValueError('init: [%d, %d] expected, got %s' % (b, dim, tuple(init.shape)))
+        if not ops.distmult_fit_supported(n_all, dim, max(b, 1)):
+            raise NotImplementedError('fit_side_effects: tipk_distmult_fit does not take n = %d, dim = %d, %d side effects '
+                                      '(include/tipk.h 4m)' % (n_all, dim, b))
+        with torch.no_grad():
+            z = self.embeddings.detach()
+            dev = z.device
+            if new is not None:
+                z = torch.cat([z, new.z.detach().to(dev)])
+            if init is not None:
+                init = init.detach().to(dev, torch.float32)
+            w, loss, grad, info = ops.distmult_fit(z, fp, l2, init, int(max_iter), float(gtol))
+            dec = MultiInnerProductDecoder(dim, b).to(dev)
+            dec.weight.data.copy_(w)
+            dec.weight.requires_grad_(False)
+            info = info.to(torch.int64)
+            gn = grad.abs().amax(dim=1) if b else grad.new_zeros(0)
+            return NewSideEffects(w, loss, gn, info[:, 1], info[:, 0], fp.n_pairs.to(dev), dec,
+                                  tuple(t.to(dev) for t in fp.known))
 
     def drug_profile(self, drugs=None, k=10, exclude='all', relations=None, partner_weights=None, new=None):
         """Serving (extension): the liability profile of single drugs -- for every side effect, with how many OTHER drugs the

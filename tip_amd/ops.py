@@ -1485,6 +1485,146 @@ def pair_table_partner_sum(s1t, s2t, q_drug, k, rel_ids=None, partner_w=None, kn
     return out_sum, out_cnt, top_v, top_p
 
 
+# what `fit_pairs_csr` returns: the distinct recorded pairs of B new side effects and their weights (include/tipk.h 4m)
+FitPairs = collections.namedtuple('FitPairs', ['ptr', 'u', 'v', 'wpos', 'wneg', 'dense_w', 'n_pairs', 'known'])
+
+
+def fit_pairs_csr(pairs, n_nodes, neg_weight=1.0):
+    """The recorded pairs of B new side effects in the form the fit entries read (host function, CPU tensors).
+
+    pairs: a list of B lists of (u, v), or (edge_index int [2, P], ptr int [B + 1]): relation b owns the columns
+    ptr[b]:ptr[b + 1].  A pair is unordered -- (u, v), (v, u) and repeats are ONE distinct pair whose multiplicity is the number
+    of times it is listed; self pairs are allowed.
+    -> FitPairs(ptr int64 [B + 1], u, v int32 [D] with u <= v, sorted by (u, v) inside a relation, wpos fp32 [D] =
+    multiplicity / P_b, wneg fp32 [D] = neg_weight * ordered multiplicity (2, or 1 for u == v) / N_b, dense_w fp32 [B] =
+    neg_weight / N_b, n_pairs int64 [B] = P_b (duplicates count), known = (keys int64 u * n + v, ptr int64 [B + 1]): both
+    directions of every distinct pair, sorted inside each relation -- the lists `distmult_screen` and `distmult_partner_sum`
+    take).  N_b = n^2 minus the ordered recorded pairs; N_b == 0 gives dense_w = wneg = 0.
+    ValueError for an id outside [0, n_nodes) or a malformed list."""
+    n = int(n_nodes)
+    if n < 1:
+        raise ValueError('n_nodes must be >= 1, not %d' % n)
+    if not float(neg_weight) > 0:
+        raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
+    if isinstance(pairs, tuple) and len(pairs) == 2 and torch.is_tensor(pairs[0]):
+        idx, lptr = torch.as_tensor(pairs[0]).to('cpu'), torch.as_tensor(pairs[1]).to('cpu')
+        if idx.dtype.is_floating_point or lptr.dtype.is_floating_point or idx.dim() != 2 or idx.shape[0] != 2 or lptr.dim() != 1 \
+                or lptr.numel() < 1:
+            raise ValueError('pairs: (edge_index int [2, P], ptr int [B + 1]) expected')
+        idx, lptr = idx.to(torch.int64), lptr.to(torch.int64)
+        if int(lptr[0]) != 0 or int(lptr[-1]) != idx.shape[1] or bool((lptr[1:] < lptr[:-1]).any()):
+            raise ValueError('pairs: ptr must rise from 0 to P = %d' % idx.shape[1])
+    else:
+        try:
+            rows = [[(int(u), int(v)) for u, v in lst] for lst in pairs]
+        except (TypeError, ValueError):
+            raise ValueError('pairs: a list of lists of (u, v) expected') from None
+        lptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
+        if rows:
+            lptr[1:] = torch.cumsum(torch.tensor([len(r) for r in rows], dtype=torch.int64), 0)
+        flat = [p for r in rows for p in r]
+        idx = torch.tensor(flat, dtype=torch.int64).reshape(-1, 2).t() if flat else torch.zeros((2, 0), dtype=torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (int(idx.min()), int(idx.max()), n))
+    b = lptr.numel() - 1
+    n_pairs = lptr[1:] - lptr[:-1]
+    rel = torch.repeat_interleave(torch.arange(b, dtype=torch.int64), n_pairs)
+    lo, hi = torch.minimum(idx[0], idx[1]), torch.maximum(idx[0], idx[1])
+    key, count = torch.unique(rel * (n * n) + lo * n + hi, return_counts=True)         # sorted by (relation, u, v)
+    drel, dkey = torch.div(key, n * n, rounding_mode='floor'), key % (n * n)
+    du, dv = torch.div(dkey, n, rounding_mode='floor'), dkey % n
+    ordered = torch.where(du == dv, 1, 2).to(torch.float64)
+    recorded = torch.zeros(b, dtype=torch.float64).index_add_(0, drel, ordered)
+    n_neg = float(n) * n - recorded
+    dense = torch.where(n_neg > 0, float(neg_weight) / n_neg.clamp(min=1.0), torch.zeros_like(n_neg))
+    dptr = torch.zeros(b + 1, dtype=torch.int64)
+    dptr[1:] = torch.cumsum(torch.bincount(drel, minlength=b), 0)
+    wpos = count.to(torch.float64) / n_pairs.to(torch.float64)[drel]
+    both = torch.unique(torch.cat([key, drel * (n * n) + dv * n + du]))
+    kptr = torch.zeros(b + 1, dtype=torch.int64)
+    kptr[1:] = torch.cumsum(torch.bincount(torch.div(both, n * n, rounding_mode='floor'), minlength=b), 0)
+    return FitPairs(dptr, du.to(torch.int32), dv.to(torch.int32), wpos.to(torch.float32),
+                    (dense[drel] * ordered).to(torch.float32), dense.to(torch.float32), n_pairs,
+                    ((both % (n * n)).contiguous(), kptr))
+
+
+def _fit_operands(z, fp, l2, who):
+    """z as the fit entries read it and the lists of `fp` (a `FitPairs`) on its device."""
+    z = _f32c(z).contiguous()
+    require_device(z)
+    if z.dim() != 2:
+        raise _lib.TipkError('%s: z [n, dim] expected, got %s' % (who, tuple(z.shape)))
+    if not float(l2) >= 0:
+        raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
+    dev = z.device
+    lists = (fp.ptr.to(dev, torch.int64), fp.u.to(dev, torch.int32), fp.v.to(dev, torch.int32), fp.wpos.to(dev, torch.float32),
+             fp.wneg.to(dev, torch.float32), fp.dense_w.to(dev, torch.float32))
+    n_fit = lists[0].numel() - 1
+    if lists[5].numel() != n_fit or any(t.numel() != lists[1].numel() for t in lists[2:5]):
+        raise _lib.TipkError('%s: the pair lists do not belong together' % who)
+    nbytes = lib().tipk_distmult_fit_workspace_bytes(z.shape[0], z.shape[1], n_fit)
+    if nbytes < 0:
+        raise _lib.TipkError('%s: unsupported shape n = %d, dim = %d, n_fit = %d (include/tipk.h section 4m)'
+                             % (who, z.shape[0], z.shape[1], n_fit))
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    return z, tuple(t.contiguous() for t in lists), n_fit, ws
+
+
+def distmult_fit_supported(n_nodes, dim, n_fit=1):
+    return bool(lib().tipk_distmult_fit_supported(n_nodes, dim, n_fit))
+
+
+def distmult_fit_stats(z, w, fp, l2=1e-4, active=None, out=None):
+    """Loss, gradient and Hessian of the new side effects' objective at the trial rows w [B, dim] (include/tipk.h section 4m).
+    fp: the `FitPairs` of `fit_pairs_csr` (moved to z's device); active: None or int [B], 0 = leave that relation's rows of
+    `out` untouched; out: None or (loss [B], grad [B, dim], hess [B, dim, dim]) to write into.
+    -> (loss, grad, hess), fp32, the l2 terms included.  Does not synchronise."""
+    z, (pptr, pu, pv, wpos, wneg, dense), n_fit, ws = _fit_operands(z, fp, l2, 'distmult_fit_stats')
+    w = _f32c(w).contiguous()
+    require_device(w, active)
+    dim = z.shape[1]
+    if tuple(w.shape) != (n_fit, dim):
+        raise _lib.TipkError('distmult_fit_stats: w [%d, %d] expected, got %s' % (n_fit, dim, tuple(w.shape)))
+    if active is not None:
+        active = active.to(torch.int32).contiguous()
+        if tuple(active.shape) != (n_fit,):
+            raise _lib.TipkError('distmult_fit_stats: active [%d] expected, got %s' % (n_fit, tuple(active.shape)))
+    if out is None:
+        out = (torch.empty(n_fit, dtype=torch.float32, device=z.device),
+               torch.empty((n_fit, dim), dtype=torch.float32, device=z.device),
+               torch.empty((n_fit, dim, dim), dtype=torch.float32, device=z.device))
+    loss, grad, hess = out
+    check(lib().tipk_distmult_fit_stats(ptr(z), z.shape[0], dim, ptr(w), n_fit, ptr(dense), ptr(pptr), ptr(pu), ptr(pv),
+                                        ptr(wpos), ptr(wneg), pu.numel(), float(l2), ptr(active), ptr(loss), ptr(grad),
+                                        ptr(hess), ptr(ws), stream_ptr(z.device)), 'tipk_distmult_fit_stats')
+    return loss, grad, hess
+
+
+def distmult_fit(z, fp, l2=1e-4, init=None, max_iter=16, gtol=1e-5):
+    """Fit the DistMult rows of B new side effects on the frozen z by damped Newton steps: max_iter + 1 (statistics, step)
+    launches enqueued by ONE `tipk_distmult_fit` call (include/tipk.h section 4m).  init: None (zeros) or [B, dim].
+    -> (w [B, dim], loss [B], grad [B, dim], info int32 [B, 4] = (status, evaluations, accepted, rejected)); status 1
+    converged (max |grad| <= gtol), 2 step below 2^-20, 3 non-finite statistic, 0 still running after max_iter + 1
+    evaluations.  Does not synchronise."""
+    z, (pptr, pu, pv, wpos, wneg, dense), n_fit, ws = _fit_operands(z, fp, l2, 'distmult_fit')
+    dim, dev = z.shape[1], z.device
+    if int(max_iter) < 0 or not float(gtol) >= 0:
+        raise _lib.TipkError('distmult_fit: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
+    if init is not None:
+        init = _f32c(init).contiguous()
+        require_device(init)
+        if tuple(init.shape) != (n_fit, dim):
+            raise _lib.TipkError('distmult_fit: init [%d, %d] expected, got %s' % (n_fit, dim, tuple(init.shape)))
+    w = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
+    loss = torch.empty(n_fit, dtype=torch.float32, device=dev)
+    grad = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
+    info = torch.zeros((n_fit, 4), dtype=torch.int32, device=dev)
+    check(lib().tipk_distmult_fit(ptr(z), z.shape[0], dim, n_fit, ptr(dense), ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg),
+                                  pu.numel(), float(l2), ptr(init), int(max_iter), float(gtol), ptr(w), ptr(loss), ptr(grad),
+                                  ptr(info), ptr(ws), stream_ptr(dev)), 'tipk_distmult_fit')
+    return w, loss, grad, info
+
+
 def targets_by_relation(edge_index, edge_type, n_rel):
     """Triples (u, v, r) grouped by the relation query r that ranks the pair {u, v} -- for the screen rank entry
     (include/tipk.h section 4h) -> (q_rel int32 [Q], tgt_ptr int64 [Q + 1], tgt_u int32 [T], tgt_v int32 [T], order int64
