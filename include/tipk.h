@@ -713,6 +713,20 @@ int tipk_pd_stage_bwd(const float* g, int64_t ld_g, const float* d_norm, const f
                       const float* agg, int64_t ld_agg, int c1, const float* w2, int64_t w2_sk, int64_t w2_sn,
                       const float* row_scale, float* gw, int64_t ld_gw, float* dw2_slabs, float* db2_slabs,
                       tipk_stream_t stream);
+/* The same launch with up to 3 ordered slab sums (section 2: tipk_sum_slabs_group) that are READY when it starts riding in it as
+ * further workgroups behind the 8 + n_row_wg of the stage, as in tipk_gather_sum_riders: the stage is a chain of L2 round trips
+ * on a third of the chip (80 workgroups at BioSNAP), the d att slab sums of both R-GCN layers run next to it instead of behind
+ * the dense products of layer 1.  Every sum adds in the order of tipk_sum_slabs_group (bit for bit); a sum with count == 0 is
+ * skipped; n_sums == 0 is tipk_pd_stage_bwd itself.  TIPK_EINVAL -- before anything is launched -- for n_sums outside 0 .. 3,
+ * sums == NULL with n_sums > 0, or a descriptor tipk_sum_slabs_group refuses. */
+int tipk_pd_stage_bwd_riders(const float* g, int64_t ld_g, const float* d_norm, const float* mean, const float* w, int p, int q,
+                             int64_t rows, int ne, int cat, float* g_xd, int64_t ld_gxd, float* g_w_slabs,
+                             const int32_t* tptr, const int32_t* tdst, const float* tw, int64_t n_src,
+                             const int32_t* wg_rows, int64_t n_row_wg,
+                             const float* agg, int64_t ld_agg, int c1, const float* w2, int64_t w2_sk, int64_t w2_sn,
+                             const float* row_scale, float* gw, int64_t ld_gw, float* dw2_slabs, float* db2_slabs,
+                             const struct tipk_slab_sum_desc* sums /* host, [n_sums <= 3], nullable */, int32_t n_sums,
+                             tipk_stream_t stream);
 
 /* out[c] = sum_r in[r, c]  (bias gradients of GCNConv).  `scratch` holds >= 256*cols floats.  rows == 0: out = 0, `in` is
  * not read and may be NULL. */

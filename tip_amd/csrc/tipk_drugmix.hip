@@ -17,6 +17,7 @@
 //             dependent round trips (row pointer -> edge list -> rows of g) took 19 us against 5.5 us for the plan kernel.)
 // All sums in fixed order: bitwise reproducible.
 #include "tipk_common.h"
+#include "tipk_slabs.h"
 
 namespace {
 
@@ -350,6 +351,18 @@ struct PdBwdArgs {
     int dbg;                                                  // debug builds: 1 = no d W_h, 2 = no gather, 4 = no d W2 partials, 8 = no prelude
 };
 
+// Ordered slab sums that are ready when the stage's backward launch starts ride in it as further workgroups (tipk_pd_stage_bwd_riders):
+// the stage has 8 + n_row_wg workgroups (BioSNAP: 80) and waits on L2 round trips, most of the chip is free next to them.  The d att
+// slab sums of both R-GCN layers (2 x 138 workgroups, 17.7 MB of slabs) take the launch from 11.0 to 12.6 us in the step's trace
+// and leave the dense products of layer 1 alone in theirs (16.2 -> 9.1 us, profiles/att_sums_riders.md).  A rider workgroup uses
+// the first SLAB_RED_FLOATS floats of the kernel's LDS.
+constexpr int PD_RIDERS = 3;
+struct PdRiders {
+    int count;
+    int first[PD_RIDERS + 1];                                 // first workgroup of every rider; first[count] = the grid
+    SlabArgs s[PD_RIDERS];
+};
+
 // LDS of a row workgroup (floats): W_h^T [q x p] | W2 [p x c1] | g_h [64 x p] | the workgroup's rows of agg [64 x c1] | the gathered
 // rows [64 x q] | a chunk of weighted rows of g_pd [PD_CHUNK_E x q'] | the chunk's edge ids, weights + the row pointers;
 // workgroups 0 .. PD_WH_WGS - 1 use the first DG_STAGE + 4096 floats as drug_mix_bwd_kernel does
@@ -365,11 +378,20 @@ constexpr int PD_OFF_EID = PD_OFF_PROD + PD_PROD;             // ids [512] | wei
 constexpr int PD_ROWS = 4;                                    // (rows_per_wg = 64)
 constexpr int PD_WH_WGS = 8;                                  // workgroups (= slabs) of d W_h
 constexpr int PD_LDS = PD_OFF_EID + 2 * PD_CHUNK_E + 128;
-static_assert(PD_LDS >= DG_STAGE + 4096 && PD_LDS * 4 <= 160 * 1024, "LDS layout");
+static_assert(PD_LDS >= DG_STAGE + 4096 && PD_LDS * 4 <= 160 * 1024 && PD_LDS >= SLAB_RED_FLOATS, "LDS layout");
 
 template <int PL>
-__global__ __launch_bounds__(1024) void pd_stage_bwd_kernel(PdBwdArgs A) {
-    __shared__ float sm[PD_LDS];
+__global__ __launch_bounds__(1024) void pd_stage_bwd_kernel(PdBwdArgs A, PdRiders rd) {
+    __shared__ __attribute__((aligned(16))) float sm[PD_LDS];
+    if (rd.count > 0 && (int)blockIdx.x >= rd.first[0]) {     // a rider workgroup: one block of an ordered slab sum
+        SlabArgs sa = rd.s[0];
+        int first = rd.first[0];
+#pragma unroll
+        for (int q = 1; q < PD_RIDERS; ++q)
+            if (q < rd.count && (int)blockIdx.x >= rd.first[q]) { sa = rd.s[q]; first = rd.first[q]; }
+        slab_sum_body(sa, (int)blockIdx.x - first, sm);
+        return;
+    }
     const DgBwdArgs& a = A.m;
     const int t = threadIdx.x;
     const int qoff = a.cat ? a.ne : 0;
@@ -688,6 +710,33 @@ extern "C" int tipk_pd_stage_bwd(const float* g, int64_t ld_g, const float* d_no
                                  const float* agg, int64_t ld_agg, int c1, const float* w2, int64_t w2_sk, int64_t w2_sn,
                                  const float* row_scale, float* gw, int64_t ld_gw, float* dw2_slabs, float* db2_slabs,
                                  tipk_stream_t stream) {
+    return tipk_pd_stage_bwd_riders(g, ld_g, d_norm, mean, w, p, q, rows, ne, cat, g_xd, ld_gxd, g_w_slabs, tptr, tdst, tw, n_src, wg_rows,
+                                    n_row_wg, agg, ld_agg, c1, w2, w2_sk, w2_sn, row_scale, gw, ld_gw, dw2_slabs, db2_slabs, nullptr, 0,
+                                    stream);
+}
+
+extern "C" int tipk_pd_stage_bwd_riders(const float* g, int64_t ld_g, const float* d_norm, const float* mean, const float* w, int p,
+                                        int q, int64_t rows, int ne, int cat, float* g_xd, int64_t ld_gxd, float* g_w_slabs,
+                                        const int32_t* tptr, const int32_t* tdst, const float* tw, int64_t n_src,
+                                        const int32_t* wg_rows, int64_t n_row_wg,
+                                        const float* agg, int64_t ld_agg, int c1, const float* w2, int64_t w2_sk, int64_t w2_sn,
+                                        const float* row_scale, float* gw, int64_t ld_gw, float* dw2_slabs, float* db2_slabs,
+                                        const tipk_slab_sum_desc* sums, int32_t n_sums, tipk_stream_t stream) {
+    if (n_sums < 0 || n_sums > PD_RIDERS || (n_sums > 0 && !sums)) return TIPK_EINVAL;
+    PdRiders rd;
+    rd.count = 0;
+    int64_t rider_blocks = 0;
+    for (int i = 0; i < n_sums; ++i) {                                          // (every descriptor is checked before anything is launched)
+        int rc;
+        const int64_t nb = fill_slab_args(sums[i], rd.s[rd.count], &rc);
+        if (rc != TIPK_OK) return rc;
+        if (nb == 0) continue;
+        rd.first[rd.count] = (int)rider_blocks;
+        rider_blocks += nb;
+        if (rider_blocks > 0x3fffffffLL) return TIPK_EUNSUPPORTED;
+        ++rd.count;
+    }
+    for (int i = rd.count; i <= PD_RIDERS; ++i) rd.first[i] = (int)rider_blocks;
     if (rows < 0 || ne < 0 || n_src < 0) return TIPK_EINVAL;
     if (!tipk_pd_stage_bwd_supported(p, q, rows, c1) || (!cat && q != ne)) return TIPK_EUNSUPPORTED;
     if (!g || !mean || !w || !g_w_slabs || !tptr || !tdst || !tw || !agg || !w2 || !gw || !dw2_slabs || !db2_slabs || n_src == 0 ||
@@ -713,11 +762,13 @@ extern "C" int tipk_pd_stage_bwd(const float* g, int64_t ld_g, const float* d_no
     A.agg = agg; A.ld_agg = ld_agg; A.c1 = c1; A.w2 = w2; A.w2_sk = w2_sk; A.w2_sn = w2_sn; A.row_scale = row_scale;
     A.gw = gw; A.ld_gw = ld_gw; A.dw2 = dw2_slabs; A.db2 = db2_slabs;
     A.dbg = TIPK_DBG(tipk_option(TIPK_OPT_DM_DEBUG));
-    const dim3 grid((unsigned)(PD_WH_WGS + n_wg));
+    const int stage_wgs = PD_WH_WGS + (int)n_wg;                                // the riders' workgroups follow the stage's
+    for (int i = 0; i <= PD_RIDERS; ++i) rd.first[i] += stage_wgs;
+    const dim3 grid((unsigned)(stage_wgs + rider_blocks));
     hipStream_t st = (hipStream_t)stream;
-    if (q <= 8) hipLaunchKernelGGL(pd_stage_bwd_kernel<8>, grid, dim3(1024), 0, st, A);
-    else if (q <= 16) hipLaunchKernelGGL(pd_stage_bwd_kernel<16>, grid, dim3(1024), 0, st, A);
-    else if (q <= 32) hipLaunchKernelGGL(pd_stage_bwd_kernel<32>, grid, dim3(1024), 0, st, A);
-    else hipLaunchKernelGGL(pd_stage_bwd_kernel<64>, grid, dim3(1024), 0, st, A);
+    if (q <= 8) hipLaunchKernelGGL(pd_stage_bwd_kernel<8>, grid, dim3(1024), 0, st, A, rd);
+    else if (q <= 16) hipLaunchKernelGGL(pd_stage_bwd_kernel<16>, grid, dim3(1024), 0, st, A, rd);
+    else if (q <= 32) hipLaunchKernelGGL(pd_stage_bwd_kernel<32>, grid, dim3(1024), 0, st, A, rd);
+    else hipLaunchKernelGGL(pd_stage_bwd_kernel<64>, grid, dim3(1024), 0, st, A, rd);
     TIPK_RETURN_LAUNCH();
 }

@@ -514,17 +514,17 @@ int bwd_impl(const tipk_encoder* h, const tipk_encoder_params* p, const float* d
     if ((st = tipk_stream_gather_parts_two(w.pg1, w.pg2, nb, nb, h->n_alloc, h->part_first, h->part_len, h->wg_part, ag.n_wg, ag.wave_ptr,
                                            ag.cells, ag.ids, ag.idx_unit, ag.zero_ptr, ag.zero_rows, w.att1, w.att2, nb, s)) != TIPK_OK)
         return st;
-    // 13. d basis1, d root1, dX0 + the two d att slab sums
+    // 13. d basis1, d root1, dX0
+    dense_jobs(wj, w.x0, n, cols, p->basis1, p->root1, nb, d1, w.gx1, w.dxb1, nullptr, w.gx0, gr->basis1, gr->root1);
+    if ((st = tipk_gemm_wg_group(wj, 3, nullptr, 0, s)) != TIPK_OK) return st;
+    // 14. the P -> D stage down to conv2's g W; d W_h, d W2, d b2 as slabs; the two d att slab sums ride
     const int64_t r = h->n_rel;
     tipk_slab_sum_desc sums[3];
     sums[0] = slab_desc(w.att1, h->n_parts, r * nb, nb, gr->att1);
     sums[1] = slab_desc(w.att2, h->n_parts, r * nb, nb, gr->att2);
-    dense_jobs(wj, w.x0, n, cols, p->basis1, p->root1, nb, d1, w.gx1, w.dxb1, nullptr, w.gx0, gr->basis1, gr->root1);
-    if ((st = tipk_gemm_wg_group(wj, 3, sums, 2, s)) != TIPK_OK) return st;
-    // 14. the P -> D stage down to conv2's g W; d W_h, d W2, d b2 as slabs
-    if ((st = tipk_pd_stage_bwd(w.gx0, cols, d_norm, w.mean, p->hgcn_w, PP_HID2, q, n, ne, dm.cat, gr->embed, ne, w.gwh, h->t_ptr, h->t_dst,
-                                h->t_w, nr, h->t_wg, h->n_t_wg, w.agg2, PP_HID1, PP_HID1, p->pp_w2, w2_so, w2_si, nullptr, w.gw, PP_HID1,
-                                w.dw2, w.db2, s)) != TIPK_OK)
+    if ((st = tipk_pd_stage_bwd_riders(w.gx0, cols, d_norm, w.mean, p->hgcn_w, PP_HID2, q, n, ne, dm.cat, gr->embed, ne, w.gwh, h->t_ptr,
+                                       h->t_dst, h->t_w, nr, h->t_wg, h->n_t_wg, w.agg2, PP_HID1, PP_HID1, p->pp_w2, w2_so, w2_si, nullptr,
+                                       w.gw, PP_HID1, w.dw2, w.db2, sums, 2, s)) != TIPK_OK)
         return st;
     // 15. conv2's transposed gather; conv1's ReLU gate and the partial rows of its bias gradient in the epilogue
     float* g_w2 = p->lin_layout ? gr->pp_w2 : w.gw2;                      // d W2 as [in, out]

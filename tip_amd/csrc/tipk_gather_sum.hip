@@ -413,10 +413,11 @@ int launch_gather(const float* table, int64_t ld_table, const int32_t* row_id, c
         if (threads > 1024 || threads % TIPK_WAVE != 0) return TIPK_EUNSUPPORTED;
         const int64_t blocks = tipk_ceil_div(n_items, group_slots);
         if (blocks > 0x7fffffffLL) return TIPK_EUNSUPPORTED;
-        const size_t lds = (size_t)threads * sizeof(Acc<V>);
+        size_t lds = (size_t)threads * sizeof(Acc<V>);
         int64_t grid = blocks;
         if (rd.count > 0) {                             // riders: 1024-thread workgroups behind the gather's own
             if (threads != 1024) return TIPK_EUNSUPPORTED;
+            if (lds < SLAB_RED_FLOATS * sizeof(float)) lds = SLAB_RED_FLOATS * sizeof(float);   // (V == 1: what a rider's lane sum takes)
             const int rider_blocks = rd.first[rd.count];        // (filled relative to 0 by the caller)
             for (int q = 0; q <= rd.count; ++q) rd.first[q] += (int)blocks;
             grid += rider_blocks;

@@ -628,7 +628,7 @@ struct SlabGroupArgs {
 // x (1024 / lanes) elements; per element the additions happen in exactly the order of
 // sum_slabs_kernel<lanes>.
 __global__ __launch_bounds__(1024) void sum_slabs_group_kernel(SlabGroupArgs sa) {
-    __shared__ float red[1024];
+    __shared__ __attribute__((aligned(16))) float red[SLAB_RED_FLOATS];
     SlabArgs a = sa.s[0];
     int first = 0;
 #pragma unroll
@@ -660,9 +660,14 @@ __global__ __launch_bounds__(1024) void sum_slabs_group_kernel(SlabGroupArgs sa)
 //     masked zeros; two consecutive terms share one tile instead (lanes of the lower k half: term 2t, upper: term 2t + 1).
 // The epilogue's c_in and gate values are requested before the K loop by the thread that will use them.
 constexpr int WGK_MAX = 4, WGK_SUMS = 3, WGK_WAVES = 16;
-// 192 would take dX of layer 1 (168) as well: 7.3 us alone instead of 12.6, but 236 product workgroups in the launch that
-// also carries both d att slab sums (9.7 us alone, 18 workgroups) ran 18.5 us against 16.4 (profiles/wg_tail.md)
-constexpr int WGK_QUARTER_MAX = 128;
+// 192 takes dX of layer 1 (645 x 64: 168) as well, d basis1 (256) stays on 32 x 32: dX0 alone 7.4 us instead of 12.4, the three
+// products of layer 1 with both 63-slab d att sums 11.5 us instead of 15.8.  At 128 the constant had been held back by those
+// sums: 2 x 549 workgroups of dword loads (the grid says 1 098, not the "18" written here before) that ran one after the
+// other with 236 product workgroups.  On 16-byte loads they are 2 x 138 workgroups (4.2 us alone instead of 9.8), and the fused
+// step carries them in the next launch (tipk_pd_stage_bwd_riders): launch 13 of the step 16.2 -> 9.1 us.  The per-layer route,
+// whose tail launch keeps its one d att sum, gains too (0.239 -> 0.230 ms per step), so one constant serves launches with and
+// without a riding sum (profiles/att_sums_riders.md).
+constexpr int WGK_QUARTER_MAX = 192;
 
 struct WgkJob {
     const float* a; int64_t a_sm, a_sk, a_sq, a_sz;

@@ -7,14 +7,64 @@ namespace {
 
 struct SlabArgs {
     const float* in; int64_t n_slabs, slab_stride, count; float alpha; int accumulate;
-    const float* row_scale; int64_t cols; const float* addend; int relu; const float* gate; float* out; int lanes;
+    const float* row_scale; int64_t cols; const float* addend; int relu; const float* gate; float* out;
+    int lanes;                                             // 4 | 16: the dword layouts; SLAB_VEC4 | SLAB_VEC16: their 16-byte forms
 };
+constexpr int SLAB_VEC4 = 1, SLAB_VEC16 = 2;
+constexpr int SLAB_RED_FLOATS = 4096;                      // LDS of a host of slab_sum_body (16 lanes x 256 elements), 16-byte aligned
 
-// one workgroup (1024 threads) of an ordered slab sum: `block` = its index inside the sum, red = 1024 floats of LDS
+// one workgroup (1024 threads) of an ordered slab sum: `block` = its index inside the sum, red = SLAB_RED_FLOATS floats of LDS
 __device__ __forceinline__ void slab_sum_body(const SlabArgs& a, int block, float* red) {
     const int first = 0;
     const float* __restrict__ in = a.in;
-    if (a.lanes == 1) {
+    if (a.lanes == SLAB_VEC16) {
+        // 16 slab lanes, vectorised: a thread owns 4 consecutive elements and ONE slab lane j (= its wave), walks slabs j, j + 16,
+        // ... with 16-byte loads, four in flight; the 16 lanes are added through LDS in lane order and the epilogue follows -- per
+        // element every addition in exactly the order of the 16-lane dword layout below.  A workgroup covers 256 elements
+        // instead of 64: the two d att sums of BioSNAP (63 slabs x 35 104) are 2 x 138 workgroups instead of 2 x 549, 4.2 us as a
+        // launch of their own instead of 9.8 (profiles/att_sums_riders.md).
+        const int e4 = threadIdx.x & 63, j = threadIdx.x >> 6;
+        const int64_t i = (int64_t)(block - first) * 256 + e4 * 4;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < a.count) {                                 // (count % 4 == 0: the whole quad)
+            const float4* p = reinterpret_cast<const float4*>(in + i);
+            const int64_t st4 = a.slab_stride / 4;
+            int64_t k = j;
+            for (; k + 48 < a.n_slabs; k += 64) {
+                const float4 v0 = p[k * st4], v1 = p[(k + 16) * st4], v2 = p[(k + 32) * st4], v3 = p[(k + 48) * st4];
+                s.x += v0.x; s.y += v0.y; s.z += v0.z; s.w += v0.w;
+                s.x += v1.x; s.y += v1.y; s.z += v1.z; s.w += v1.w;
+                s.x += v2.x; s.y += v2.y; s.z += v2.z; s.w += v2.w;
+                s.x += v3.x; s.y += v3.y; s.z += v3.z; s.w += v3.w;
+            }
+            if (k < a.n_slabs) {                           // at most three slabs left: requested together (clamped), added in order
+                float4 v[3];
+#pragma unroll
+                for (int u = 0; u < 3; ++u) v[u] = p[(k + 16 * u < a.n_slabs ? k + 16 * u : k) * st4];
+#pragma unroll
+                for (int u = 0; u < 3; ++u)
+                    if (k + 16 * u < a.n_slabs) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
+            }
+        }
+        *reinterpret_cast<float4*>(red + j * 256 + e4 * 4) = s;
+        __syncthreads();
+        const int e = threadIdx.x;
+        const int64_t o = (int64_t)(block - first) * 256 + e;
+        if (e < 256 && o < a.count) {
+            float t = red[e];
+#pragma unroll
+            for (int q = 1; q < 16; ++q) t += red[q * 256 + e];
+            t *= a.alpha;
+            if (a.row_scale) t *= a.row_scale[o / a.cols];
+            if (a.addend) t += a.addend[o];
+            if (a.accumulate) t += a.out[o];
+            if (a.relu) t = fmaxf(t, 0.f);
+            if (a.gate && !(a.gate[o] > 0.f)) t = 0.f;
+            a.out[o] = t;
+        }
+        return;
+    }
+    if (a.lanes == SLAB_VEC4) {
         // 4 slab lanes, vectorised: ONE thread owns 4 consecutive elements and plays all four slab lanes itself
         // (lane j = slabs j, j+4, ... in order; then ((s0 + s1) + s2) + s3: bit for bit the sums of the 4-lane
         // layout below) -- 16-byte loads, eight of them in flight, no LDS and no barrier.  The dword layout
@@ -106,12 +156,16 @@ inline int64_t fill_slab_args(const tipk_slab_sum_desc& d, SlabArgs& a, int* rc)
     a.gate = d.gate; a.out = d.out;
     // same slab-lane rule as tipk_sum_slabs_ex, so grouped and single launches add in the same order
     a.lanes = (d.n_slabs >= 32 && tipk_ceil_div(d.count, 64) < 2048) ? 16 : 4;
-    // the 4-lane sums run vectorised (lanes = 1: same order of additions, 16-byte accesses) when alignment allows
+    // both layouts run vectorised (same order of additions, 16-byte accesses) when alignment allows: the 4-lane sums of at least
+    // one vector workgroup of elements, the 16-lane sums always (a workgroup then covers 256 elements instead of 64)
     const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (a.lanes == 4 && d.count % 4 == 0 && d.slab_stride % 4 == 0 && al16(d.in) && al16(d.out) && al16(d.addend) &&
-        al16(d.gate) && (!d.row_scale || d.cols % 4 == 0) && d.count >= 4096)
-        a.lanes = 1;
-    return a.lanes == 1 ? tipk_ceil_div(d.count, 4096) : tipk_ceil_div(d.count, 1024 / a.lanes);
+    const bool vec = d.count % 4 == 0 && d.slab_stride % 4 == 0 && al16(d.in) && al16(d.out) && al16(d.addend) && al16(d.gate) &&
+                     (!d.row_scale || d.cols % 4 == 0);
+    if (a.lanes == 4 && vec && d.count >= 4096) a.lanes = SLAB_VEC4;
+    else if (a.lanes == 16 && vec) a.lanes = SLAB_VEC16;
+    if (a.lanes == SLAB_VEC4) return tipk_ceil_div(d.count, 4096);
+    if (a.lanes == SLAB_VEC16) return tipk_ceil_div(d.count, 256);
+    return tipk_ceil_div(d.count, 1024 / a.lanes);
 }
 
 }  // namespace

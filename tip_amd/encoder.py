@@ -19,8 +19,9 @@ lists over libtipk (include/tipk.h) -- 8 + 8 launches at BioSNAP, where the per-
              10  d basis2, d root2, dX1 (ReLU gate)                                               tipk_gemm_wg_group
              11  dXB1 + pair-gradient rows, layer 1                                               tipk_rgcn_pair_grads
              12  d att slabs of BOTH layers                                                       tipk_stream_gather_parts_two
-             13  d basis1, d root1, dX0 + the two d att slab sums                                 tipk_gemm_wg_group
-             14  d embed, d W_h, transposed P -> D gather, conv2's g W and d W2 / d b2 partials   tipk_pd_stage_bwd
+             13  d basis1, d root1, dX0                                                           tipk_gemm_wg_group
+             14  d embed, d W_h, transposed P -> D gather, conv2's g W and d W2 / d b2 partials
+                 + the two d att slab sums as riders                                              tipk_pd_stage_bwd_riders
              15  conv2's transposed gather + conv1's ReLU gate + d b1 partials + d W2 / d b2 sums tipk_gather_sum_riders
              16  conv1's transposed gather = d W1 (+ the d b1 sum)                                tipk_gather_sum_riders
 
@@ -36,7 +37,7 @@ Whether a layer takes the pair form is asked of `ops.rgcn_route`, the one route 
 import torch
 
 from . import ops
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import SlabSumDesc, check, lib, ptr, stream_ptr
 
 
 class EncoderPlans(object):
@@ -109,9 +110,10 @@ def drug_mix_gather_xb(xd, h, w_h, d_norm, cat, pd_graph, basis, root, xb_nb):
     return out, mean, xroot
 
 
-def pd_stage_bwd(g_x0, d_norm, mean, w_h, ne, cat, pd_graph, agg, w2, row_scale, want_xd=True):
+def pd_stage_bwd(g_x0, d_norm, mean, w_h, ne, cat, pd_graph, agg, w2, row_scale, want_xd=True, riders=()):
     """(d xd, slab job of d W_h, gw = (g_h W2) * row_scale, slab job of d W2 ([in, out] storage), slab job of d b2): the backward pass of the
-    P -> D stage down to the input of conv2's transposed gather, one launch (`tipk_pd_stage_bwd`)."""
+    P -> D stage down to the input of conv2's transposed gather, one launch (`tipk_pd_stage_bwd`).
+    riders: up to 3 `ops.slab_job`s that are ready now, summed by further workgroups of the same launch (`tipk_pd_stage_bwd_riders`)."""
     csr = pd_graph.pd_csr
     n, p = mean.shape
     q = w_h.shape[1]
@@ -124,12 +126,15 @@ def pd_stage_bwd(g_x0, d_norm, mean, w_h, ne, cat, pd_graph, agg, w2, row_scale,
     gw = torch.empty((n_src, c1), dtype=torch.float32, device=dev)
     dw2 = torch.empty((n_slabs, c1, p), dtype=torch.float32, device=dev)
     db2 = torch.empty((n_slabs, p), dtype=torch.float32, device=dev)
-    with ops._timed('pd_stage_bwd[%dx%dx%d,rows=%d]' % (n, p, q, n_src)):
-        check(lib().tipk_pd_stage_bwd(ptr(g_x0), g_x0.stride(0), ptr(d_norm), ptr(mean), ptr(w_h), p, q, n, ne, int(cat),
-                                      ptr(g_xd), g_xd.stride(0) if g_xd is not None else 0, ptr(g_w),
-                                      ptr(csr['t_ptr']), ptr(csr['t_dst']), ptr(csr['t_w']), n_src, ptr(csr['t_wg']), n_slabs,
-                                      ptr(agg), agg.stride(0), c1, ptr(w2), w2.stride(0), w2.stride(1), ptr(row_scale),
-                                      ptr(gw), gw.stride(0), ptr(dw2), ptr(db2), stream_ptr(dev)), 'tipk_pd_stage_bwd')
+    riders = list(riders)
+    arr = (SlabSumDesc * max(1, len(riders)))(*[r.desc for r in riders])
+    with ops._timed('pd_stage_bwd[%dx%dx%d,rows=%d]' % (n, p, q, n_src) + ('+%d sums' % len(riders) if riders else '')):
+        check(lib().tipk_pd_stage_bwd_riders(ptr(g_x0), g_x0.stride(0), ptr(d_norm), ptr(mean), ptr(w_h), p, q, n, ne, int(cat),
+                                             ptr(g_xd), g_xd.stride(0) if g_xd is not None else 0, ptr(g_w),
+                                             ptr(csr['t_ptr']), ptr(csr['t_dst']), ptr(csr['t_w']), n_src, ptr(csr['t_wg']), n_slabs,
+                                             ptr(agg), agg.stride(0), c1, ptr(w2), w2.stride(0), w2.stride(1), ptr(row_scale),
+                                             ptr(gw), gw.stride(0), ptr(dw2), ptr(db2), arr if riders else None, len(riders),
+                                             stream_ptr(dev)), 'tipk_pd_stage_bwd_riders')
     return g_xd, ops.slab_job(g_w), gw, ops.slab_job(dw2), ops.slab_job(db2)
 
 
@@ -216,11 +221,12 @@ class _EncoderStep(torch.autograd.Function):
         pg1, dxb1 = ops.pair_grads(pb, cells1, xb1, g_x1, table=0)
         # 12. d att of both layers: one launch over the shared plan
         j_att1, j_att2 = pair_att_gather_two(pb, pg1, pg2)
-        # 13. layer 1's dense gradients + both d att slab sums
-        g_x0, g_basis1, g_root1 = ops.rgcn_dense_tail(x0, basis1, root1, g_x1, dxb1, None, [j_att1, j_att2])
-        # 14. the P -> D stage down to conv2's g W, d W2 / d b2 as slabs
+        # 13. layer 1's dense gradients
+        g_x0, g_basis1, g_root1 = ops.rgcn_dense_tail(x0, basis1, root1, g_x1, dxb1, None, [])
+        # 14. the P -> D stage down to conv2's g W, d W2 / d b2 as slabs; both d att slab sums (ready since launch 12, read by
+        # nothing in the step) on the CUs the stage's 80 workgroups leave idle
         g_xd, j_wh, gw, j_w2, j_b2 = pd_stage_bwd(g_x0, d_norm, mean, w_h, ctx.ne, plans.cat, plans.pd, agg2, w2, plans.pp_rows.scale,
-                                                 want_xd=ctx.needs_input_grad[0])
+                                                 want_xd=ctx.needs_input_grad[0], riders=[j_att1, j_att2])
         # 15. conv2's transposed gather; conv1's ReLU gate and the partial rows of its bias gradient in the epilogue
         g_h1, parts = ops.gather_sum(plans.pp_rows.bwd, gw, riders=[j_w2, j_b2, j_wh], gate=h1, colsum=True)
         # 16. conv1's transposed gather IS d W1 (identity features)

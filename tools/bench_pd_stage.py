@@ -25,6 +25,12 @@ print('drug_mix_gather_xb_fwd %.1f us' % bench.time_launch_us(f))
 gup, agg, w2 = torch.randn(n, ne + q, device=dev), torch.randn(ns, c1, device=dev), torch.randn(c1, p, device=dev).t()
 b = lambda: encoder.pd_stage_bwd(gup, dn, mean, w, ne, True, g, agg, w2, None)
 print('pd_stage_bwd %.1f us' % bench.time_launch_us(b))
+# as in the BioSNAP step: both layers' d att slab sums (63 slabs x 1 097 relations x 32 bases) ride in the launch
+from tip_amd import ops
+big = [torch.randn(63, 1097, nb, device=dev) for _ in range(2)]
+br = lambda: encoder.pd_stage_bwd(gup, dn, mean, w, ne, True, g, agg, w2, None, riders=[ops.slab_job(s) for s in big])
+print('pd_stage_bwd + two 63-slab sums %.1f us' % bench.time_launch_us(br))
+print('   two 63-slab sums alone %.1f us' % bench.time_launch_us(lambda: ops.gemm_group([], [ops.slab_job(s) for s in big])))
 if '+debug' in _lib.build_id():
     for bits, what in ((16, 'up to the edge ids of the first chunk'), (32, 'up to the weighted rows in LDS'), (64, 'up to the row sums of the first chunk'), (1, 'without d W_h'), (2, 'without the gather and what follows'), (3, 'prelude + d xd only'), (4, 'without the d W2 partials'),
                        (5, 'without d W_h and the d W2 partials')):
