@@ -67,6 +67,11 @@ const char* tipk_build_id(void);
  *                            in LDS (section 4j; both routes return the same bits)
  *      "partner_sum_global"  1 = tipk_distmult_partner_sum reads z rows from global memory even where the LDS image fits
  *                            (section 4l; both routes return the same bits)
+ *      "combo_no_prefix"     1 = the combination-burden kernel sums every level of every combination; 0: it keeps the sum of
+ *                            the slower slots in LDS while the last slot advances (section 4n; both routes return the same
+ *                            bits)
+ *      "combo_run"           combinations a wavefront of the combination-burden kernel takes in one run, 1..64 (0 = chosen
+ *                            from the size of the call; section 4n; every value returns the same bits)
  *      "rg_debug", "dp_debug", "dm_debug"  bit masks that SKIP parts of tipk_rel_gather / tipk_rgcn_dy_products / the decoder kernels
  *                            (timing decompositions): accepted by -DTIPK_DEBUG builds only; a release
  *                            library returns TIPK_EUNSUPPORTED for a non-zero value and its kernels
@@ -1489,6 +1494,96 @@ int     tipk_distmult_fit(const float* z, int64_t n_nodes, int dim, int64_t n_fi
                           const float* init /* nullable: zeros */, int max_iter, float gtol,
                           float* out_w, float* out_loss, float* out_grad, int32_t* out_info, void* workspace,
                           tipk_stream_t stream);
+
+/* 4n. Combination burden: the TOTAL expected weighted number of side effects of every regimen a query can form by choosing
+ *     one alternative per open slot on top of its fixed drugs, per (query, combination), and the k combinations of every
+ *     query with the lowest burden (serving; the question after 4i when more than one choice is open: which trio of
+ *     alternatives, which drugs of a list to stop; no reference call site).
+ *
+ *   A QUERY q is a list of FIXED drugs (possibly empty) and S >= 0 SLOTS, each a non-empty list of ALTERNATIVES: a drug id, or
+ *   -1 for "leave this slot empty".  All lists are DEVICE arrays:
+ *     fix_drugs int32 [n_fix], fix_ptr int64 [n_q + 1]: the fixed drugs of q, in list order;
+ *     slot_ptr int64 [n_q + 1]: q owns the slots slot_ptr[q] .. slot_ptr[q+1]; alt_ptr int64 [n_slots + 1], alt int32 [n_alt]:
+ *     slot s owns alt[alt_ptr[s] .. alt_ptr[s+1]).  A_s is the size of slot s; the alternatives of q are numbered j = 0, 1, ...
+ *     in slot order.
+ *   A COMBINATION picks one alternative per slot; its index is c = sum_s c_s * prod_{t > s} A_t: the LAST slot runs fastest
+ *   (itertools.product).  A query has C = prod_s A_s combinations (1 with S = 0: the fixed list alone).
+ *     comb_ptr int64 [n_q + 1]: q owns out_burden[comb_ptr[q] - comb_ptr[0] .. comb_ptr[q+1] - comb_ptr[0]); n_comb is the
+ *     number of entries of the call.  row_ptr int64 [n_q + 1]: q owns that range of workspace rows (relative to row_ptr[0]);
+ *     a legal query has 1 + sum_s A_s + sum_{s < t} A_s A_t of them and n_rows is the total.  Both are taken relative to
+ *     their first entry, so a caller may pass a window [q0, q1] of longer arrays.
+ *   The REGIMEN of a combination is the fixed drugs plus the chosen ids that are not -1.  Its burden follows 4d / 4i: for
+ *   every unordered pair of the regimen the logit is that of the pair (min id, max id) -- 4i's arithmetic, DistMult or
+ *   table --, and a triple contributes unless it is KNOWN for the pair's key (the pair-major lists of 4d).  Per relation r
+ *     TIPK_REGIMEN_NOISY_OR  A_r = sum of softplus(logit) over the contributing triples, P_r = -expm1f(-A_r)
+ *     TIPK_REGIMEN_MAX       P_r = sigma(L) = 1.0f / (1.0f + expf(-L)), L the largest contributing logit
+ *   P_r = 0 without a contributing triple; B = sum_r weights[r] * P_r.  A regimen of 0 or 1 drugs has B = +0 exactly.
+ *   ORDER of the fp32 sums (noisy-or), fixed and the same on every route -- LEVEL ORDER.  Three kinds of partial sums, each a
+ *   chain of one-rounding adds from +0.0f:
+ *     base_r       over the pairs (i, j), i < j, of the fixed list, i ascending, then j ascending;
+ *     single[j]_r  alternative j with the fixed drugs in list order;
+ *     cross[j][j']_r  the one term of the pair of alternatives j, j' of different slots.
+ *   A_r = base_r; then for s = 1 .. S: A_r += single[c_s]_r, then A_r += cross[c_s][c_t]_r for t = 1 .. s - 1 ascending; the
+ *   terms of a -1 alternative are skipped (not added as zeros).  Under TIPK_REGIMEN_MAX the same terms hold largest logits
+ *   (-inf: none) and the sum is a maximum.  Then the sum over r as 4i: with l = r mod 64, b_l = fmaf(weights[r], P_r, b_l)
+ *   for r = l, l + 64, ... ascending from 0.0f, then b_l = b_l + b_(l + off) for off = 32, 16, 8, 4, 2, 1; B = b_0.  The order
+ *   depends on nothing but the query: BITWISE repeatable, run to run and route to route; no floating-point atomics.
+ *   NOT APPLICABLE -- the burden is NaN and the combination is never selected: two chosen drugs coincide; a chosen drug is
+ *   a fixed drug; any triple of its pairs that is not known has a NaN logit (under either aggregate, whatever the weights).
+ *   ILLEGAL QUERY -- every entry of its comb_ptr range is NaN and nothing is read out of bounds: a fixed id outside
+ *   [0, n_nodes); a repeated fixed drug; an alternative outside [-1, n_nodes); an empty slot; more than
+ *   tipk_addon_max_context() (64) fixed drugs, tipk_combo_max_slots() (10) slots, tipk_combo_max_alternatives() (64)
+ *   alternatives in all its slots or tipk_combo_max_combinations() (2^24) combinations; offsets that leave [0, n_fix],
+ *   [0, n_slots], [0, n_alt], [0, n_comb] or [0, n_rows] or descend; a comb_ptr range that is not C entries or a row_ptr range
+ *   that is not the row count above.  An entry of out_burden that no query owns is NaN.
+ *   Output (device): out_burden fp32 [n_comb].  k > 0: out_best_burden fp32 [n_q x k], out_best_comb int32 [n_q x k] = the k
+ *   combinations of each query with the lowest burden, ascending, ties by ascending combination index; the selection reads
+ *   the fp32 values written to out_burden; padding is (+inf, -1).  k == 0 skips the selection and both may be NULL.
+ *   Work: three launches on one stream.  (1) Tables: one wavefront per (query, row) -- base, single[j], cross[j][j'] -- with
+ *   lane-owned relations in windows as 4i; a row of n_rel floats goes to `workspace` (row stride n_rel rounded up to 4
+ *   floats) with coalesced stores; a NaN logit of a triple that is not known is stored as NaN and wins every maximum, and
+ *   the row of a pair that cannot be (one drug twice, an alternative that is fixed) is NaN throughout.  (2) Burden:
+ *   persistent workgroups, a wavefront takes runs of consecutive combinations and reads its rows from the workspace; while
+ *   only the last slot advances the sum through level S - 1 is kept per relation in LDS (n_rel <= 2 048; option
+ *   "combo_no_prefix" turns it off, "combo_run" sets the run length): same bits.  (3) Selection, one wavefront per query.
+ *   Supported: as 4i -- 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256 (DistMult; rel_w 16-byte aligned), 1 <= n_rel <=
+ *   65 536, 0 <= k <= 128; n_comb below 2^31; workspace 16-byte aligned.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k < 0, a negative size, n_nodes or n_rel < 1,
+ *   ld < n_rel, an unknown `aggregate`, a NULL required pointer (with n_q > 0: the five offset arrays, the tables, fix_drugs
+ *   with n_fix > 0, alt with n_alt > 0, out_burden with n_comb > 0, workspace with n_rows > 0, and with k > 0 the two best
+ *   outputs), known arrays given only in part; then TIPK_EUNSUPPORTED outside the supported range; n_q == 0 is TIPK_OK with no
+ *   launch and nothing written; TIPK_OK implies correct numbers.
+ *   workspace: tipk_*_combo_burden_workspace_bytes(..., n_rows, k) bytes (-1: unsupported; may be 0).
+ *   Nothing lives in host memory: these entries do NOT synchronise or allocate and may be captured into a hipGraph
+ *   (sequential launches, no parallel branches).
+ */
+int     tipk_combo_max_slots(void);
+int     tipk_combo_max_alternatives(void);
+int64_t tipk_combo_max_combinations(void);
+int     tipk_distmult_combo_burden_supported(int64_t n_nodes, int dim, int64_t n_rel, int k);
+int64_t tipk_distmult_combo_burden_workspace_bytes(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_rows, int k);
+int     tipk_distmult_combo_burden(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                   const int32_t* fix_drugs, const int64_t* fix_ptr /* device [n_q+1] */, int64_t n_fix,
+                                   const int32_t* alt, const int64_t* alt_ptr /* device [n_slots+1] */, int64_t n_alt,
+                                   const int64_t* slot_ptr /* device [n_q+1] */, int64_t n_slots,
+                                   const int64_t* comb_ptr, const int64_t* row_ptr /* device [n_q+1] */, int64_t n_q,
+                                   int64_t n_comb, int64_t n_rows, const float* weights /* nullable */,
+                                   const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                   int64_t n_known_pairs /* nullable together */,
+                                   int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
+                                   int32_t* out_best_comb /* nullable with k == 0 */, void* workspace, tipk_stream_t stream);
+int     tipk_pair_table_combo_burden_supported(int64_t n_nodes, int64_t n_rel, int k);
+int64_t tipk_pair_table_combo_burden_workspace_bytes(int64_t n_nodes, int64_t n_rel, int64_t n_rows, int k);
+int     tipk_pair_table_combo_burden(const float* s1, const float* s2, int64_t ld, int64_t n_nodes, int64_t n_rel,
+                                     const int32_t* fix_drugs, const int64_t* fix_ptr /* device [n_q+1] */, int64_t n_fix,
+                                     const int32_t* alt, const int64_t* alt_ptr /* device [n_slots+1] */, int64_t n_alt,
+                                     const int64_t* slot_ptr /* device [n_q+1] */, int64_t n_slots,
+                                     const int64_t* comb_ptr, const int64_t* row_ptr /* device [n_q+1] */, int64_t n_q,
+                                     int64_t n_comb, int64_t n_rows, const float* weights /* nullable */,
+                                     const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                     int64_t n_known_pairs /* nullable together */,
+                                     int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
+                                     int32_t* out_best_comb /* nullable with k == 0 */, void* workspace, tipk_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,

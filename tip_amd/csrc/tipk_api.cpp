@@ -19,12 +19,13 @@ static const char tipk_build_marker[] = "TIPK_BUILD_ID=" TIPK_BUILD_ID;
 #endif
 extern "C" const char* tipk_build_id(void) { return tipk_build_marker + 14; }
 
-static int g_options[TIPK_OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int g_options[TIPK_OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static const char* const g_option_names[TIPK_OPT_COUNT] = {"gemm_no_stream", "gemm_thin_k_narrow", "gemm_stream_kk",
                                                             "rg_debug", "dp_debug", "rg_occupancy", "dm_debug", "dm_task_kernel",
                                                             "screen_search", "pair_topk_stream", "regimen_global",
                                                             "pair_rank_stream", "partner_rank_global", "addon_global",
-                                                            "attribution_global", "partner_sum_global"};
+                                                            "attribution_global", "partner_sum_global", "combo_no_prefix",
+                                                            "combo_run"};
 
 int tipk_option(int id) { return (id >= 0 && id < TIPK_OPT_COUNT) ? g_options[id] : 0; }
 

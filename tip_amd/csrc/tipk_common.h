@@ -40,7 +40,9 @@ enum {
     TIPK_OPT_ADDON_GLOBAL = 13,       // tipk_distmult_addon_burden: rel_w rows read from global memory even where the LDS image fits
     TIPK_OPT_ATTRIBUTION_GLOBAL = 14, // tipk_rgcn_attribution: the per-query table in the caller's workspace even where it fits in LDS
     TIPK_OPT_PARTNER_SUM_GLOBAL = 15, // tipk_distmult_partner_sum: z rows read from global memory even where the LDS image fits
-    TIPK_OPT_COUNT = 16
+    TIPK_OPT_COMBO_NO_PREFIX = 16,    // tipk_*_combo_burden: every combination sums all its levels (no prefix kept while the last slot advances)
+    TIPK_OPT_COMBO_RUN = 17,          // tipk_*_combo_burden: combinations per wavefront run (0 = chosen from the call's size; at most 64)
+    TIPK_OPT_COUNT = 18
 };
 int tipk_option(int id);
 #ifdef TIPK_DEBUG

@@ -39,12 +39,15 @@ NewDrugs = namedtuple('NewDrugs', ['x0', 'h', 'z', 'degree', 'n_targets'])
 NewSideEffects = namedtuple('NewSideEffects', ['weight', 'loss', 'grad_norm', 'evaluations', 'status', 'n_pairs', 'decoder', 'known'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
+# TIP.combination_risk's result: the total burden of every combination of alternatives and each query's k safest ones
+CombinationRisk = namedtuple('CombinationRisk', ['burden', 'ptr', 'best_burden', 'best_combination', 'best_drugs'])
 # TIP.drug_profile's result: per queried drug the expected number of unrecorded partners for every side effect column
 DrugProfile = namedtuple('DrugProfile', ['expected', 'candidates', 'top_expected', 'top_relation'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
-           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects']
+           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects',
+           'CombinationRisk']
 
 
 # ---------------------------------------------------------------------------------------------
@@ -913,6 +916,13 @@ class MultiInnerProductDecoder(nn.Module):
         relation."""
         return ops.distmult_addon_burden(z.detach(), self._rows(relations), ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
 
+    def combination_burden(self, z, plan, k, aggregate='noisy_or', weights=None, known=None, relations=None):
+        """Combination burden (extension, `tipk_distmult_combo_burden`): sum_r weights[r] * P_r over ALL pairs of every
+        regimen the queries of `plan` (`ops.combo_plan`) can form, and the k combinations of each query with the lowest
+        burden -> (burden [n_comb], comb_ptr [Q + 1], best_burden [Q, k], best_comb int32 [Q, k]) as
+        `ops.distmult_combo_burden`; no autograd.  known, relations and weights as `addon_burden`."""
+        return ops.distmult_combo_burden(z.detach(), self._rows(relations), plan, k, aggregate, weights, known)
+
 
 def normalize_regimens(regimens, n_drug, max_drugs):
     """Host normalisation of `TIP.regimen_side_effects`: a list of lists of drug ids, or a (drugs, ptr) pair of int tensors
@@ -1017,6 +1027,84 @@ def normalize_add_on_queries(regimens, candidates, replace, n_drug, max_context)
         if lo < 0 or hi >= n_drug:
             raise ValueError('candidate drug id out of range: [%d, %d] for %d drugs' % (lo, hi, n_drug))
     return drugs.to(torch.int32), ptr, cand.to(torch.int32), cand_ptr
+
+
+def normalize_combination_queries(slots, fixed, n_drug, limits):
+    """Host normalisation of `TIP.combination_risk` -> (fix_drugs int32, fix_ptr int64 [G + 1], alt int32, alt_ptr int64
+    [n_slots + 1], slot_ptr int64 [G + 1]) on the host, the lists of include/tipk.h section 4n, in the order given.
+    slots: ONE query as a list of slots, each a non-empty list of alternatives (a drug id, or -1 for "leave the slot
+    empty"), or a list of G such queries; an empty list is a query without slots (`[[]]`: one such query).  fixed: None
+    (no fixed drugs), one list of drug ids (one query, or shared by all G), or G lists.  limits: `ops.combo_limits()`.
+    ValueError, with the query's number, for a fixed id outside [0, n_drug), a repeated fixed drug, an alternative outside
+    [-1, n_drug), an empty slot, more than limits.max_fixed fixed drugs, limits.max_slots slots, limits.max_alternatives
+    alternatives or limits.max_combinations combinations, or lists that are not what the above says.  A drug that is both
+    fixed and an alternative, or an alternative of two slots, is legal: the combinations that take it twice come back NaN."""
+    def plain(x):
+        return x.tolist() if torch.is_tensor(x) else x
+
+    def seq(x):
+        return isinstance(x, (list, tuple))
+
+    def ints(x, what):
+        try:
+            if not seq(x) or any(seq(v) or isinstance(v, (bool, float)) for v in x):
+                raise TypeError
+            return [int(v) for v in x]
+        except (TypeError, ValueError):
+            raise ValueError('%s: a list of drug ids expected, got %r' % (what, x)) from None
+
+    slots = plain(slots)
+    if not seq(slots):
+        raise ValueError('slots: a list of slots (lists of alternatives), or a list of such queries expected')
+    slots = [plain(e) for e in slots]
+    # an entry is a QUERY when it is an empty list or a list of lists, a SLOT when it is a non-empty list of ids; a list of
+    # queries needs every entry to be one, anything else is read as the slots of one query
+    def is_query(e):
+        return seq(e) and all(seq(plain(v)) for v in e)
+    queries = [[plain(v) for v in e] for e in slots] if len(slots) > 0 and all(is_query(e) for e in slots) else [slots]
+    G = len(queries)
+    if fixed is None:
+        fixed_lists = [[] for _ in range(G)]
+    elif seq(plain(fixed)) and len(plain(fixed)) > 0 and all(seq(plain(f)) for f in plain(fixed)):
+        fixed = [plain(f) for f in plain(fixed)]
+        if len(fixed) != G:
+            raise ValueError('fixed: %d lists for %d queries' % (len(fixed), G))
+        fixed_lists = [ints(f, 'fixed (query %d)' % g) for g, f in enumerate(fixed)]
+    else:
+        shared = ints(plain(fixed), 'fixed')
+        fixed_lists = [list(shared) for _ in range(G)]
+    fix, fptr, alt, aptr, sptr = [], [0], [], [0], [0]
+    for g, (q, f) in enumerate(zip(queries, fixed_lists)):
+        if not isinstance(q, (list, tuple)):
+            raise ValueError('query %d: a list of slots expected, got %r' % (g, q))
+        if len(f) > limits.max_fixed:
+            raise ValueError('query %d: %d fixed drugs, at most %d are scored' % (g, len(f), limits.max_fixed))
+        if any(d < 0 or d >= n_drug for d in f):
+            raise ValueError('query %d: fixed drug id out of range for %d drugs: %r' % (g, n_drug, [d for d in f if d < 0 or d >= n_drug]))
+        if len(set(f)) != len(f):
+            raise ValueError('query %d: a fixed drug is repeated' % g)
+        if len(q) > limits.max_slots:
+            raise ValueError('query %d: %d slots, at most %d' % (g, len(q), limits.max_slots))
+        count, total = 1, 0
+        for si, slot in enumerate(q):
+            a = ints(slot, 'query %d, slot %d' % (g, si))
+            if len(a) == 0:
+                raise ValueError('query %d: slot %d is empty' % (g, si))
+            if any(d < -1 or d >= n_drug for d in a):
+                raise ValueError('query %d, slot %d: alternative out of range [-1, %d): %r'
+                                 % (g, si, n_drug, [d for d in a if d < -1 or d >= n_drug]))
+            alt += a
+            aptr.append(len(alt))
+            count, total = count * len(a), total + len(a)
+        if total > limits.max_alternatives:
+            raise ValueError('query %d: %d alternatives in all slots, at most %d' % (g, total, limits.max_alternatives))
+        if count > limits.max_combinations:
+            raise ValueError('query %d: %d combinations, at most %d' % (g, count, limits.max_combinations))
+        fix += f
+        fptr.append(len(fix))
+        sptr.append(len(aptr) - 1)
+    return (torch.tensor(fix, dtype=torch.int32), torch.tensor(fptr, dtype=torch.int64), torch.tensor(alt, dtype=torch.int32),
+            torch.tensor(aptr, dtype=torch.int64), torch.tensor(sptr, dtype=torch.int64))
 
 
 def screen_queries(num_et, relations=None, drugs=None):
@@ -1180,6 +1268,13 @@ class NNDecoder(nn.Module):
         with torch.no_grad():
             s1, s2 = self._tables(z.detach(), relations)
         return ops.pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggregate, weights, known)
+
+    def combination_burden(self, z, plan, k, aggregate='noisy_or', weights=None, known=None, relations=None):
+        """Combination burden (extension, `tipk_pair_table_combo_burden`) on the two tables `forward` forms; arguments and
+        result as `MultiInnerProductDecoder.combination_burden`."""
+        with torch.no_grad():
+            s1, s2 = self._tables(z.detach(), relations)
+        return ops.pair_table_combo_burden(s1, s2, plan, k, aggregate, weights, known)
 
     def objective(self, z, pos_index, neg_index, edge_type):
         """-mean log(sigma(pos)+eps) - mean log(1-sigma(neg)+eps) (src/layers.py:335-340 with this decoder as
@@ -1575,6 +1670,75 @@ class TIP(nn.Module):
             else:
                 best_drug = _ids_at(best_p, cand_flat_d, task_ptr_d[:-1, None])
         return AddOnRisk(burden.reshape(-1), cand_flat_d, task_ptr_d, best_b, best_drug)
+
+    def combination_risk(self, slots, fixed=None, k=10, aggregate='noisy_or', weights=None, relations=None, exclude=None):
+        """Serving (extension): the TOTAL expected side-effect burden of every regimen that takes one alternative per open
+        slot on top of the fixed drugs, and the k safest combinations (`decoder.combination_burden`:
+        `tipk_distmult_combo_burden` / `tipk_pair_table_combo_burden` on `self.embeddings`, under no_grad; both decoder
+        kinds).  The burden of a regimen is sum_r weights[r] * P_r with P_r over ALL its pairs -- 1 - prod (1 - sigma) under
+        'noisy_or', sigma(largest logit) under 'max' --, which is not additive over drugs: every combination is scored.
+        slots / fixed: as `normalize_combination_queries` -- one query (a list of slots) or a list of queries; an
+        alternative of -1 leaves its slot empty, so `[[d, -1] for d in drugs]` asks which drugs of a list to stop.
+        weights / relations / exclude: exactly as `add_on_risk`.
+        -> CombinationRisk(burden float32 [T], ptr int64 [G + 1], best_burden float32 [G, k], best_combination int64 [G, k],
+        best_drugs int64 [G, k, S_max]) on the model's device: query g owns burden[ptr[g]:ptr[g + 1]], a combination's index
+        is its position there, the last slot running fastest (itertools.product); NaN where a combination takes a drug
+        twice (two slots, or a slot and the fixed list) or a logit is NaN.  best_*: ascending burden, ties by combination
+        index, padded with (+inf, -1); best_drugs: the drug chosen in every slot, -1 for an empty slot, for a slot the query
+        does not have (S_max is the largest slot count) and for padding."""
+        _refuse_sharded(self.shard, 'combinations')
+        _check_known_mode('exclude', exclude)
+        if aggregate not in ops.REGIMEN_AGGREGATES:
+            raise ValueError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+        k = int(k)
+        if k < 0:
+            raise ValueError('k must be >= 0, not %d' % k)
+        d = self.data
+        fix, fptr, alt, aptr, sptr = normalize_combination_queries(slots, fixed, d.n_drug, ops.combo_limits())
+        rel_host = _relation_ids(relations, 'cpu')
+        n_w = d.n_dd_et if rel_host is None else rel_host.numel()
+        if weights is not None:
+            try:
+                weights = torch.as_tensor(weights).detach().to(torch.float32)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError('weights: one number per side effect expected') from None
+            if weights.dim() != 1 or weights.numel() != n_w:
+                raise ValueError('weights: %d entries expected (one per side effect%s), got shape %s'
+                                 % (n_w, '' if rel_host is None else ' of `relations`', tuple(weights.shape)))
+            if not bool((torch.isfinite(weights) & (weights >= 0)).all()):
+                raise ValueError('weights must be finite and >= 0')
+        dev = self.embeddings.device
+        plan = ops.combo_plan(fix, fptr, alt, aptr, sptr, dev)
+        G = plan.n_q
+        rel = None if rel_host is None else rel_host.to(dev)
+        known = _pair_known(d, exclude, rel)
+        with torch.no_grad():
+            w_d = None if weights is None else weights.to(dev)
+            burden, ptr_d, best_b, best_c = self.decoder.combination_burden(self.embeddings, plan, k, aggregate, w_d, known, rel)
+            size = sptr[1:] - sptr[:-1]
+            s_max = int(size.max()) if G else 0
+            if k == 0:
+                best_b = torch.empty((G, 0), dtype=torch.float32, device=dev)
+                best_c = torch.empty((G, 0), dtype=torch.int64, device=dev)
+                best_drugs = torch.empty((G, 0, s_max), dtype=torch.int64, device=dev)
+            else:
+                # digit s of a combination index, last slot fastest: (c // prod_{t > s} A_t) % A_s
+                A = torch.ones((G, s_max + 1), dtype=torch.int64)
+                first = torch.zeros((G, max(s_max, 1)), dtype=torch.int64)
+                for g in range(G):
+                    s0, n_s = int(sptr[g]), int(size[g])
+                    A[g, :n_s] = aptr[s0 + 1:s0 + n_s + 1] - aptr[s0:s0 + n_s]
+                    first[g, :n_s] = aptr[s0:s0 + n_s]
+                A[:, s_max] = 1
+                after = torch.flip(torch.cumprod(torch.flip(A, [1]), 1), [1])[:, 1:] if s_max else A[:, :0]
+                A_d, after_d, first_d = A[:, :s_max].to(dev), after.to(dev), first[:, :s_max].to(dev)
+                best_c = best_c.to(torch.int64)
+                digit = torch.div(best_c[:, :, None].clamp(min=0), after_d[:, None, :], rounding_mode='floor') % A_d[:, None, :]
+                has = (torch.arange(s_max)[None, :] < size[:, None]).to(dev)[:, None, :] & (best_c >= 0)[:, :, None]
+                alt_d = torch.cat([plan.alt.to(torch.int64), plan.alt.new_zeros(1, dtype=torch.int64)])
+                best_drugs = torch.where(has, alt_d[(first_d[:, None, :] + digit).clamp(max=alt_d.numel() - 1)],
+                                         torch.full_like(digit, -1))
+        return CombinationRisk(burden, ptr_d, best_b, best_c, best_drugs)
 
     def rank_side_effects(self, triples=None, filter='all', ks=(1, 3, 10), relations=None):
         """Evaluation of what `side_effects` serves (extension): where each given (drug, drug, side effect) triple lands

@@ -1812,6 +1812,143 @@ def pair_table_addon_burden(s1, s2, ctx_drugs, ctx_ptr, cand, cand_ptr, k, aggre
     return out_b, best_b, best_p
 
 
+ComboLimits = collections.namedtuple('ComboLimits', ['max_fixed', 'max_slots', 'max_alternatives', 'max_combinations'])
+ComboPlan = collections.namedtuple('ComboPlan', ['fix_drugs', 'fix_ptr', 'alt', 'alt_ptr', 'slot_ptr', 'comb_ptr', 'row_ptr', 'n_q',
+                                     'n_fix', 'n_alt', 'n_slots', 'n_comb', 'n_rows', 'host_comb_ptr', 'host_row_ptr'])
+COMBO_WORKSPACE_BYTES = 1 << 30                                        # the tables of one entry call: more queries are chunked
+
+
+def combo_limits():
+    """The limits of the combination-burden entries (include/tipk.h section 4n), read from the library."""
+    return ComboLimits(int(lib().tipk_addon_max_context()), int(lib().tipk_combo_max_slots()),
+                       int(lib().tipk_combo_max_alternatives()), int(lib().tipk_combo_max_combinations()))
+
+
+def combo_plan(fix_drugs, fix_ptr, alt, alt_ptr, slot_ptr, device):
+    """The query lists of the combination-burden entries on `device`, with the two offset arrays the entries size their
+    output and workspace by.  fix_drugs int [n_fix], fix_ptr int [Q + 1]: the fixed drugs of every query; slot_ptr int
+    [Q + 1]: query q owns the slots slot_ptr[q]:slot_ptr[q + 1]; alt int [n_alt], alt_ptr int [n_slots + 1]: the alternatives
+    of every slot (-1: leave the slot empty).  Tensors or lists, host or device -- the sizes are taken on the host (one
+    synchronisation when the lists live on the device); the entry calls that use the plan do not synchronise.
+    A query within the limits owns prod A_s entries of the result (1 without slots) and 1 + sum A_s + sum_{s < t} A_s A_t
+    workspace rows; one that breaks a structural limit (more than `max_slots` slots, an empty slot, more than
+    `max_alternatives` alternatives or `max_combinations` combinations, offsets that descend) owns ONE entry, which the
+    kernel writes as NaN, and no row.  Ids and fixed lists are checked by the kernel."""
+    lim = combo_limits()
+    host = [torch.as_tensor(t).detach().to('cpu') for t in (fix_drugs, fix_ptr, alt, alt_ptr, slot_ptr)]
+    host = [t.to(torch.int64) if t.numel() == 0 and t.dim() == 1 else t for t in host]       # (an empty list has no dtype)
+    if any(t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool for t in host):
+        raise _lib.TipkError('combination queries: 1-d int tensors fix_drugs, fix_ptr [Q + 1], alt, alt_ptr [n_slots + 1] and '
+                             'slot_ptr [Q + 1] expected, got %s' % ', '.join('%s %s' % (t.dtype, tuple(t.shape)) for t in host))
+    fd, fp, al, ap, sp = (t.to(torch.int64) for t in host)
+    n_q = fp.numel() - 1
+    if n_q < 0 or sp.numel() != n_q + 1 or ap.numel() < 1:
+        raise _lib.TipkError('combination queries: fix_ptr and slot_ptr [Q + 1] and alt_ptr [n_slots + 1] expected, got %d, %d '
+                             'and %d entries' % (fp.numel(), sp.numel(), ap.numel()))
+    n_slots = ap.numel() - 1
+    size = (ap[1:] - ap[:-1]).tolist()
+    comb, rows = [0], [0]
+    for s0, s1 in zip(sp[:-1].tolist(), sp[1:].tolist()):
+        c, r, seen = 1, 1, 0
+        ok = 0 <= s0 <= s1 <= n_slots and s1 - s0 <= lim.max_slots
+        for a in (size[s0:s1] if ok else ()):
+            ok = ok and a >= 1
+            c, r, seen = c * max(a, 0), r + a + a * seen, seen + a
+        if not ok or seen > lim.max_alternatives or c > lim.max_combinations:
+            c, r = 1, 0
+        comb.append(comb[-1] + c)
+        rows.append(rows[-1] + r)
+    comb_ptr, row_ptr = torch.tensor(comb, dtype=torch.int64), torch.tensor(rows, dtype=torch.int64)
+    parts = [fp, sp, ap, comb_ptr, row_ptr]
+    flat = torch.cat(parts).to(device)                                   # two uploads: the offsets, the ids
+    cuts = [0]
+    for t in parts:
+        cuts.append(cuts[-1] + t.numel())
+    fp_d, sp_d, ap_d, cp_d, rp_d = (flat[cuts[i]:cuts[i + 1]] for i in range(5))
+    ids = torch.cat([fd, al, torch.zeros(1, dtype=torch.int64)]).to(torch.int32).to(device)   # (an empty tensor has no address)
+    fd_d, al_d = ids[:max(fd.numel(), 1)], ids[fd.numel():]
+    return ComboPlan(fd_d, fp_d, al_d, ap_d, sp_d, cp_d, rp_d, n_q, fd.numel(), al.numel(), n_slots, comb[-1], rows[-1],
+                     comb_ptr, row_ptr)
+
+
+def _combo_run(entry, ws_bytes, plan, k, aggregate, weights, known, n_rel, dev, who):
+    """The shared body of the two combination-burden ops: outputs, workspace, chunks of queries, the entry calls.
+    entry(lists..., out pointers, workspace) -> status; ws_bytes(n_rows) -> bytes."""
+    if aggregate not in REGIMEN_AGGREGATES:
+        raise _lib.TipkError("aggregate must be 'max' or 'noisy_or', not %r" % (aggregate,))
+    if not isinstance(plan, ComboPlan):
+        raise _lib.TipkError('%s: a ComboPlan (ops.combo_plan) expected, got %s' % (who, type(plan).__name__))
+    require_device(plan.fix_ptr, weights)
+    if weights is not None:
+        weights = _f32c(weights).contiguous()
+        if weights.dim() != 1 or weights.numel() != n_rel:
+            raise _lib.TipkError('weights: a float tensor [%d] expected, got %s' % (n_rel, tuple(weights.shape)))
+    keys, kptr, krel, n_keys = _known_lists(known)
+    k, agg, n_q = int(k), REGIMEN_AGGREGATES[aggregate], plan.n_q
+    out_b = torch.empty((plan.n_comb,), dtype=torch.float32, device=dev)
+    best_b = best_c = None
+    if k > 0:
+        best_b = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+        best_c = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    # chunks of consecutive queries whose tables fit COMBO_WORKSPACE_BYTES (a single query always gets its own call)
+    rows = plan.host_row_ptr.tolist()
+    cuts, q0 = [0], 0
+    for q in range(1, n_q + 1):
+        if q - q0 > 1 and ws_bytes(rows[q] - rows[q0]) > COMBO_WORKSPACE_BYTES:
+            cuts.append(q - 1)
+            q0 = q - 1
+    if n_q > 0:
+        cuts.append(n_q)
+    ws_most = max([ws_bytes(rows[b] - rows[a]) for a, b in zip(cuts[:-1], cuts[1:])] + [0])
+    if ws_most < 0:
+        raise _lib.TipkError('%s: unsupported shape (see include/tipk.h section 4n)' % who)
+    ws = torch.empty((max(ws_most, 16),), dtype=torch.uint8, device=dev)
+    combs = plan.host_comb_ptr.tolist()
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        check(entry(ptr(plan.fix_drugs), ptr(plan.fix_ptr[a:]), plan.n_fix, ptr(plan.alt), ptr(plan.alt_ptr), plan.n_alt,
+                    ptr(plan.slot_ptr[a:]), plan.n_slots, ptr(plan.comb_ptr[a:]), ptr(plan.row_ptr[a:]), b - a,
+                    combs[b] - combs[a], rows[b] - rows[a], ptr(weights), ptr(keys), ptr(kptr), ptr(krel), n_keys, agg, k,
+                    ptr(out_b[combs[a]:]) if combs[b] > combs[a] else None, None if best_b is None else ptr(best_b[a:]),
+                    None if best_c is None else ptr(best_c[a:]), ptr(ws), stream_ptr(dev)), who)
+    return out_b, plan.comb_ptr, best_b, best_c
+
+
+def distmult_combo_burden(z, rel_w, plan, k, aggregate='noisy_or', weights=None, known=None):
+    """The total burden sum_r weights[r] * P_r of every combination of every query of `plan` (`combo_plan`) by the DistMult
+    logits of ALL pairs of its regimen -- the fixed drugs plus one alternative per slot --, and the k combinations of each
+    query with the lowest burden (include/tipk.h section 4n).
+
+    aggregate, weights, known: as `distmult_addon_burden`.  -> (burden float32 [n_comb], comb_ptr int64 [Q + 1], best_burden
+    float32 [Q, k], best_comb int32 [Q, k]): query q owns burden[comb_ptr[q]:comb_ptr[q + 1]], combination index = position
+    in that range, the last slot running fastest (itertools.product); NaN where a combination is not applicable (two
+    chosen drugs coincide, a chosen drug is fixed, a NaN logit) or the query is illegal; best_*: ascending burden, ties by
+    combination index, padded with (+inf, -1); both None for k = 0.  Queries whose tables would take more than
+    COMBO_WORKSPACE_BYTES are dealt to several entry calls.  Does not synchronise."""
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_combo_burden')
+    dev = z.device
+    n, dim, n_rel = z.shape[0], z.shape[1], rel_w.shape[0]
+
+    def entry(*lists):
+        return lib().tipk_distmult_combo_burden(ptr(z), n, dim, ptr(rel_w), n_rel, *lists)
+
+    return _combo_run(entry, lambda n_rows: int(lib().tipk_distmult_combo_burden_workspace_bytes(n, dim, n_rel, n_rows, int(k))),
+                      plan, k, aggregate, weights, known, n_rel, dev, 'tipk_distmult_combo_burden')
+
+
+def pair_table_combo_burden(s1, s2, plan, k, aggregate='noisy_or', weights=None, known=None):
+    """`distmult_combo_burden` for the NN decoder's node-major tables s1, s2 [n, n_rel] (row stride free, the same for
+    both): the logit of the drugs c, d under r is s1[min(c, d), r] + s2[max(c, d), r]."""
+    s1, s2 = _table_pair(s1, s2, 'pair_table_combo_burden')
+    dev = s1.device
+    n, n_rel = s1.shape[0], s1.shape[1]
+
+    def entry(*lists):
+        return lib().tipk_pair_table_combo_burden(ptr(s1), ptr(s2), s1.stride(0), n, n_rel, *lists)
+
+    return _combo_run(entry, lambda n_rows: int(lib().tipk_pair_table_combo_burden_workspace_bytes(n, n_rel, n_rows, int(k))),
+                      plan, k, aggregate, weights, known, n_rel, dev, 'tipk_pair_table_combo_burden')
+
+
 _IN_EDGES = {}
 
 
