@@ -67,14 +67,15 @@ def stream_of(dev):
 
 
 class Encoder(object):
-    """One handle + its workspace.  graphs: pp [2, E], dp [2, E], dd [2, E], dd_range [R, 2] (int64, any device)."""
+    """One handle + its workspace.  graphs: pp [2, E], dp [2, E], dd [2, E], dd_range [R, 2] (any integer type, any device),
+    handed over as int64 (idx_bytes 8) or int32 (idx_bytes 4)."""
 
-    def __init__(self, lib, pp, dp, dd, dd_range, n_prot, n_drug, dims, dev):
+    def __init__(self, lib, pp, dp, dd, dd_range, n_prot, n_drug, dims, dev, idx_bytes=8):
         self.lib, self.dev, self.n_drug, self.dims = lib, dev, n_drug, dims
         self.h = P()
-        keep = [t.to(dev).to(torch.int64).contiguous() for t in (pp, dp, dd, dd_range)]
+        keep = [t.to(dev).to(torch.int64 if idx_bytes == 8 else torch.int32).contiguous() for t in (pp, dp, dd, dd_range)]
         self.status = lib.tipk_encoder_build(ptr(keep[0]), keep[0].shape[1], ptr(keep[1]), keep[1].shape[1], ptr(keep[2]), keep[2].shape[1],
-                                             ptr(keep[3]), keep[3].shape[0], 8, n_prot, n_drug, C.byref(dims), C.byref(self.h))
+                                             ptr(keep[3]), keep[3].shape[0], idx_bytes, n_prot, n_drug, C.byref(dims), C.byref(self.h))
         if self.status == 0:
             self.ws = torch.empty(lib.tipk_encoder_workspace_bytes(self.h), dtype=torch.uint8, device=dev)
             assert lib.tipk_encoder_workspace_init(self.h, ptr(self.ws), self.ws.numel(), stream_of(dev)) == 0

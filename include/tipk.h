@@ -1859,7 +1859,13 @@ void tipk_host_plan_free(tipk_host_plan* plan);
  *         negative or inconsistent arguments (ids out of range, ranges that do not tile the edge list, add with n_embed !=
  *         prot_drug_dim); TIPK_EUNSUPPORTED where the fused kernels do not take the shape (the conditions of encoder.py
  *         `usable`: more than 1 024 drugs, n_hid1 != 32, widths or base counts a `*_supported` query refuses, a P -> D edge that
- *         starts at a drug, every protein a P -> D source) -- there is no other route behind the handle.
+ *         starts at a drug, every protein a P -> D source, no P -> D edge that ends at a drug, no relation or no D-D edge) -- there
+ *         is no other route behind the handle.
+ *         Contracts pinned by tests/test_gpu_encoder_step_edges.py on the edge graphs of tests/encoder_cases.py (empty and one-edge
+ *         relations, drugs without targets or in-edges, a hub, duplicate triples, a dense and a one-edge D-D graph, node counts that
+ *         are no multiple of a tile, 1 024 drugs, the last n_rel of one LDS column block): z and all twelve gradients within
+ *         k 2^-24 A of fp64 elementwise; the bits of `_EncoderStep` for lin_layout 0 | 1 and idx_bytes 4 | 8; d_norm = NULL = a
+ *         tensor of ones; flags 0 = TIPK_ENCODER_FROM_FWD; TIPK_EUNSUPPORTED with a NULL handle exactly where `usable` is False.
  *     tipk_encoder_workspace_bytes: size of the caller-owned workspace (16-byte aligned).  It holds what the backward pass reads
  *         (conv outputs, x0, x1, the P -> D mean, both layers' pair cells and node-major XB, one pair-gradient table per layer) and
  *         the scratch of both passes.  tipk_encoder_workspace_init (one hipMemsetAsync on `stream`, capturable) prepares a workspace

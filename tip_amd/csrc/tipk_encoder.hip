@@ -348,6 +348,12 @@ int build_impl(const void* pp_index, int64_t n_pp, const void* dp_index, int64_t
     }
     const int64_t n_rows = (int64_t)rows.size();
     if (n_rows == 0 || n_rows >= n_prot) return TIPK_EUNSUPPORTED;
+    // ... and one without any edge that ENDS at a drug is one without P -> D edges (n_dp == 0 above; encoder.py `usable`)
+    {
+        int64_t into_drugs = 0;
+        for (int64_t i = 0; i < n_dp; ++i) into_drugs += dp[(size_t)(n_dp + i)] >= n_prot;
+        if (into_drugs == 0) return TIPK_EUNSUPPORTED;
+    }
     // D-D pair form (layers.py `rgcn_graph`, paired): one column block, lanes = bases / 4
     if (n_drug * n_drug >= (1 << 24) || tipk_stream_gather_supported(n_rel, d.num_base, 1) != 1 || d.num_base % 4 || d.num_base < 16 ||
         tipk_stream_gather_supported(n_rel, d.num_base, 4) != 1)

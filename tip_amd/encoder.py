@@ -60,6 +60,8 @@ def usable(plans, xd, w_h, d_norm, c2_weight, c1_bias, c2_bias, basis1, att1, ba
         return False
     if c1_bias is None or c2_bias is None or not xd.is_cuda:
         return False
+    if plans.pd.pd_csr['n_edges'] == 0:                    # no P -> D edge ends at a drug: as for the handle, nothing to fuse
+        return False
     n, ne = xd.shape
     p, q = w_h.shape
     nb, d_in, d1 = basis1.shape

@@ -273,11 +273,14 @@ def hier_graph(edge_index, n_all, n_source, chunk=DEFAULT_CHUNK, table_rows=None
     # four to a workgroup (W = 4), the others sixteen (a wavefront each); desc = {first index into `order`, n | W << 8}
     order, wgs = drug_workgroups(torch.bincount(dst, minlength=n_t))
     fwd_wg = torch.tensor(wgs, dtype=torch.int32, device=src.device).view(-1, 2).contiguous()
-    graph.pd_csr = dict(fwd_ptr=ptr(dst, n_t), fwd_src=i32(src[of]), scale=scale, fwd_wg=fwd_wg, fwd_order=i32(order), n_src=int(n_tab))
+    # (no edge ends at a target: an empty tensor has no address and the launchers refuse a NULL list -- one unread element)
+    some = lambda t: t if t.numel() else t.new_zeros(1)
+    graph.pd_csr = dict(fwd_ptr=ptr(dst, n_t), fwd_src=some(i32(src[of])), scale=scale, fwd_wg=fwd_wg, fwd_order=i32(order), n_src=int(n_tab),
+                        n_edges=int(src.numel()))
     # CSR by SOURCE row (edge order kept inside a row) with 1 / count of the edge's target: the transposed gather inside the
     # fused backward launch of the stage (tipk_pd_stage_bwd, tip_amd/encoder.py)
     ot = torch.sort(src, stable=True).indices
-    graph.pd_csr.update(t_ptr=ptr(src, n_tab), t_dst=i32(dst[ot]), t_w=scale[dst[ot]].contiguous())
+    graph.pd_csr.update(t_ptr=ptr(src, n_tab), t_dst=some(i32(dst[ot])), t_w=some(scale[dst[ot]].contiguous()))
     # ... and the deal of the source rows to that launch's workgroups: consecutive rows, at most max_rows of them and at most
     # max_edges edges (a row with more edges than that has a workgroup to itself)
     if src.is_cuda:
