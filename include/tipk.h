@@ -1585,6 +1585,72 @@ int     tipk_pair_table_combo_burden(const float* s1, const float* s2, int64_t l
                                      int aggregate, int k, float* out_burden, float* out_best_burden /* nullable with k == 0 */,
                                      int32_t* out_best_comb /* nullable with k == 0 */, void* workspace, tipk_stream_t stream);
 
+/* 4o. Protein attribution: which protein targets -- of the explained drug AND of the drugs it interacts with -- a prediction
+ *     rests on (serving; no reference call site -- FMEncoder.forward, src/layers.py:520-550, read backwards).
+ *
+ *   Both R-GCN layers are bias-free, the only non-linearity between the drug inputs and z is the ReLU behind rgcn1, and the
+ *   P -> D stage is linear in the protein embeddings.  For the ReLU pattern of the stored h, probe . z[v] therefore equals
+ *   gradient x input summed over every protein and every drug's own feature row: an exact partition of the logit.
+ *   Operands (DEVICE, fp32): hp [n_prot x p] (ld_hp) the P-P encoder's output by protein id; w_pd [p x pd] dense;
+ *   xe [n_nodes x ne] (ld_xe) the drug embedding rows already divided by d_norm; h [n_nodes x d1] (ld_h) the stored
+ *   relu(rgcn1(x0)), read ONLY for the mask h > 0; layer l = basis_l dense, att_l [n_rel x n_bases] (ld_att_l), root_l dense:
+ *   basis1 [n_bases x d0 x d1], root1 [d0 x d1], basis2 [n_bases x d1 x d2], root2 [d1 x d2], d0 = cat ? ne + pd : ne
+ *   (add: ne == pd).
+ *   D-D in-edges, CSR by destination: pe_ptr int64 [n_nodes + 1], pe_src / pe_rel int32 [n_edges]; node j owns the positions
+ *   pe_ptr[j] .. pe_ptr[j+1], sorted by (SOURCE, relation) (tip_amd.ops.in_edges_by_pair) -- the edges of one pair are
+ *   adjacent and in the order they have in the (relation, source) segment of 4j; deg_j = max(pe_ptr[j+1] - pe_ptr[j], 1),
+ *   duplicates counted, a self pair is an edge like any other.
+ *   Protein-side CSR of the P -> D edges: prot_ptr int64 [n_prot + 1], prot_drug int32 [n_pd_edges] (the drugs protein t
+ *   targets, duplicates kept), inv_cnt fp32 [n_nodes] = the correctly rounded 1.0f / max(number of P -> D edges into the
+ *   drug, 1).  Ids in range are the caller's contract (tip_amd.ops checks them once per tensor); an id out of range is
+ *   skipped, the pointers are clamped, nothing is read out of bounds.
+ *   Query q = (node v = q_node[q], probe g = probe[q * ld_probe .. + d2)).
+ *   Arithmetic, fp32, every chain starts at 0.0f and runs ascending:
+ *     cells    C_l[i,j,b] = (1.0f / deg_j) * (sum of att_l[rel_e, b] over the edges e: i -> j, by plain adds)    (once per call)
+ *     G2[b,i]  fma over o of basis2[b,i,o] g[o];   R2[i] fma over o of root2[i,o] g[o]
+ *     a1[j,i]  (fma over b of C2[j,v,b] G2[b,i], then + R2[i] where j == v) where h[j,i] > 0, else 0
+ *     U[i,b,o] sum over j of C1[i,j,b] a1[j,o] on v_mfma_f32_32x32x2_f32 (exact fp32, j ascending)
+ *     a0[i,c]  ONE fma chain: basis1[b,c,o] U[i,b,o] over (b, o), then root1[c,o] a1[i,o] over o
+ *     own_i    fma over c < ne of a0[i,c] xe[i,c];   qv[i,x] fma over c < pd of w_pd[x,c] a0[i, (cat ? ne : 0) + c]
+ *     c_t      plain adds, over t's entries e ascending, of inv_cnt[i_e] * (fma over x of hp[t,x] qv[i_e,x])
+ *     direct_t the same sum over the entries with i_e == v only.
+ *   Candidates: the proteins with at least one entry.  Output (device), per query: out_contrib fp32 / out_protein int32 /
+ *   out_direct fp32 [n_q x k] = the k candidates with the largest c_t, c_t descending, ties (+0 and -0 tie) by ascending
+ *   protein id, with direct_t; fewer than k candidates are padded with (-inf, -1, +0); a NaN c_t is never listed.
+ *   out_features [n_q] = sum_i own_i, out_proteins [n_q] = the sum of c_t over ALL candidates: fp32 values added in fp64 --
+ *   thread t of 256 adds the items t, t + 256, ... ascending, lanes by x_l += x_(l + off), off = 32 .. 1, the four wavefronts
+ *   as ((w0 + w1) + w2) + w3 -- and rounded once.  Then g . z[v] = out_features + out_proteins up to rounding.
+ *   No float atomics: every output is BITWISE repeatable, and the same for a query whatever else is in the call.
+ *   q_node outside [0, n_nodes): a fully padded row, out_features = out_proteins = NaN, nothing read out of bounds.
+ *   Work: the cells kernel once; then per chunk of tipk_protein_attribution_chunk() = 256 queries three launches (a1; the
+ *   large product with everything behind it -- a workgroup owns a drug i and 256 / d1p columns' worth of queries, C1[i] and
+ *   a1 stream through LDS in slices of 32 rows, U and a0 never leave the chip --; the protein pass with the selection of 4c).
+ *   Queries beyond one chunk are looped inside the entry.
+ *   Supported: 1 <= n_nodes <= 4 096 (the dense cells take 2 n_nodes^2 n_bases floats), 1 <= n_bases <= 64, every width
+ *   (p, pd, ne, d0, d1, d2) in [1, 128] and any value, 1 <= k <= 1 024; n_prot, n_rel, n_edges, n_pd_edges, n_q below 2^31.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k <= 0, a negative size, a size or width < 1, a row
+ *   stride shorter than its row, add mode with ne != pd, a NULL required pointer (with n_q > 0: everything, `workspace`
+ *   included, but pe_src / pe_rel when n_edges == 0 and prot_drug when n_pd_edges == 0); then TIPK_EUNSUPPORTED outside the
+ *   supported range; n_q == 0 is TIPK_OK with no launch and nothing written.
+ *   workspace: tipk_protein_attribution_workspace_bytes(...) bytes (-1: unsupported sizes), 4-byte aligned.
+ *   Nothing lives in host memory: the entry does NOT synchronise or allocate and may be captured into a hipGraph.
+ */
+int     tipk_protein_attribution_supported(int64_t n_nodes, int64_t n_prot, int64_t n_rel, int n_bases, int ne, int pd, int p,
+                                           int d1, int d2, int cat, int k);
+int64_t tipk_protein_attribution_chunk(void);
+int64_t tipk_protein_attribution_workspace_bytes(int64_t n_nodes, int n_bases, int d1, int p, int64_t n_q);   /* -1 unsupported */
+int     tipk_protein_attribution(const float* hp, int64_t ld_hp, int64_t n_prot, int p, const float* w_pd, int pd,
+                                 const float* xe, int64_t ld_xe, int ne, const float* h, int64_t ld_h, int64_t n_nodes, int d1,
+                                 const float* basis1, const float* att1, int64_t ld_att1, const float* root1,
+                                 const float* basis2, const float* att2, int64_t ld_att2, const float* root2, int d2,
+                                 int64_t n_rel, int n_bases,
+                                 const int64_t* pe_ptr /* [n_nodes+1] */, const int32_t* pe_src, const int32_t* pe_rel, int64_t n_edges,
+                                 const int64_t* prot_ptr /* [n_prot+1] */, const int32_t* prot_drug, int64_t n_pd_edges,
+                                 const float* inv_cnt /* [n_nodes] */, int cat,
+                                 const int32_t* q_node /* [n_q] */, const float* probe, int64_t ld_probe, int64_t n_q, int k,
+                                 float* out_contrib, int32_t* out_protein, float* out_direct /* [n_q x k] */,
+                                 float* out_features, float* out_proteins /* [n_q] */, void* workspace, tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

@@ -34,7 +34,9 @@ ScreenResult = namedtuple('ScreenResult', ['score', 'u', 'v', 'relation'])
 # TIP.side_effects' result: per pair row the k best side effects, best first (padding: score 0 / -inf, relation -1)
 SideEffects = namedtuple('SideEffects', ['score', 'relation'])
 Explanation = namedtuple('Explanation', ['logit', 'offset', 'own', 'neighbours', 'contribution', 'partner', 'relation', 'degree'])
-NewDrugs = namedtuple('NewDrugs', ['x0', 'h', 'z', 'degree', 'n_targets'])
+ProteinExplanation = namedtuple('ProteinExplanation', ['logit', 'offset', 'features', 'proteins', 'contribution', 'protein', 'direct',
+                                                       'targets'])
+NewDrugs = namedtuple('NewDrugs',['x0', 'h', 'z', 'degree', 'n_targets'])
 # TIP.fit_side_effects' result: per new side effect its fitted DistMult row and how the fit ended
 NewSideEffects = namedtuple('NewSideEffects', ['weight', 'loss', 'grad_norm', 'evaluations', 'status', 'n_pairs', 'decoder', 'known'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
@@ -1871,6 +1873,75 @@ class TIP(nn.Module):
             in_ptr = ops.in_edges_by_node(d.dd_train_idx, d.dd_train_range, h.shape[0])[0]
             return Explanation(logit, offset, own, total, c, src.to(torch.int64), rel.to(torch.int64),
                                in_ptr[node + 1] - in_ptr[node])
+
+    def explain_proteins(self, triples=None, k=10, side='v', direction='raise', max_workspace_bytes=1 << 30):
+        """Which protein targets a prediction rests on (extension): the logit of every given (drug u, drug v, side effect r)
+        triple, split EXACTLY over every targeted protein -- the targets of the explained drug and those of the drugs it
+        interacts with, two hops back -- and every drug's own feature row.  Both R-GCN layers are bias-free, the only
+        non-linearity between the drug inputs and z is the ReLU behind rgcn1 and the P -> D stage is linear in the protein
+        embeddings, so for the ReLU pattern of this model
+            logit = offset + features + proteins,   proteins = the sum of one contribution per targeted protein,
+        and the k largest contributions are listed (`ops.protein_attribution`: one `tipk_protein_attribution` call, a fused
+        reverse pass on the fp32 matrix cores; both decoder kinds, both `mod`s).
+        triples, side, direction: as `explain` ('lower' lists the proteins that pull the logit down most, most negative
+        first).  The model is RE-ENCODED with its current parameters (`FMEncoder.fold_in_tables`, `encode_layers`, under
+        no_grad); `self.embeddings` is not overwritten.
+        -> ProteinExplanation(logit [T], offset [T] as `explain`; features [T]: the part of ALL drugs' own feature rows;
+        proteins [T]: the sum over ALL targeted proteins; contribution [T, k], protein int64 [T, k], direct [T, k]: the
+        listed proteins, and the part of each contribution that arrives through the explained drug's own targets (0 for a
+        protein it does not target), padded with (-inf, or +inf under 'lower'; -1; 0); targets int64 [T]: the explained
+        drug's number of P -> D edges) on the model's device, in the triples' order.
+        NotImplementedError for a relation-sharded model, a layer with a bias, sizes `tipk_protein_attribution_supported`
+        refuses, or a workspace above max_workspace_bytes; ValueError for a bad side or direction."""
+        _refuse_sharded(self.shard, 'proteins')
+        if side not in ('u', 'v'):
+            raise ValueError("side must be 'u' or 'v', not %r" % (side,))
+        if direction not in ('raise', 'lower'):
+            raise ValueError("direction must be 'raise' or 'lower', not %r" % (direction,))
+        d, enc = self.data, self.encoder
+        r1, r2 = enc.rgcn1, enc.rgcn2
+        if r1.bias is not None or r2.bias is not None or r1.shard is not None or r2.shard is not None:
+            raise NotImplementedError('explain_proteins splits the sums of bias-free layers that hold every relation; a layer '
+                                      'has a bias or a relation shard')
+        ne, cat = enc.embed.shape[1], enc.mod == 'cat'
+        p, pd = enc.pp_encoder.out_dim, enc.hgcn.out_dim
+        if not ops.protein_attribution_supported(d.n_drug, d.n_prot, d.n_dd_et, r1.num_bases, ne, pd, p, r1.out_channels,
+                                                 r2.out_channels, cat, k):
+            raise NotImplementedError('explain_proteins: tipk_protein_attribution does not take these sizes (include/tipk.h 4o)')
+        dev = self.embeddings.device
+        idx, et = _checked_triples(triples, d, dev)
+        need = ops.protein_attribution_workspace_bytes(d.n_drug, r1.num_bases, r1.out_channels, p, et.numel())
+        if need > int(max_workspace_bytes):
+            raise NotImplementedError('explain_proteins: the dense pair cells need a workspace of %d bytes, above '
+                                      'max_workspace_bytes = %d' % (need, int(max_workspace_bytes)))
+        with torch.no_grad():
+            args = (d.d_feat, d.dd_train_idx, d.dd_train_et, d.dd_train_range, d.d_norm, d.p_feat, d.pp_train_indices,
+                    d.dp_edge_index, d.dp_range_list)
+            h_prot, x0, h = enc.fold_in_tables(*args)
+            z = enc.encode_layers(*args)[1]
+            node, probe, offset = self.decoder.probe(z, idx, et, side)
+            if self.decoder_kind == 'nn':
+                logit = ops.pair_table_score(*self.decoder._tables(z), idx, et, sigmoid=False)
+            else:
+                logit = self.decoder(z, idx, et, sigmoid=False)
+            if cat:
+                xe = x0[:, :ne]                                           # the rows the model itself read
+            else:
+                xe = enc._drug_feat.apply_table(d.d_feat, enc.embed).detach()
+                if d.d_norm is not None:
+                    xe = xe / torch.as_tensor(d.d_norm).to(device=dev, dtype=torch.float32).reshape(-1, 1)
+            lower = direction == 'lower'
+            targets = ops.targets_by_protein(d.dp_edge_index, d.n_prot, d.n_drug)
+            c, prot, direct, features, proteins = ops.protein_attribution(
+                h_prot, enc.hgcn.weight.detach(), xe, h, (r1.basis.detach(), r1.att.detach(), r1.root.detach()),
+                (r2.basis.detach(), r2.att.detach(), r2.root.detach()),
+                ops.in_edges_by_pair(d.dd_train_idx, d.dd_train_range, d.n_drug), targets, cat, node,
+                -probe if lower else probe, k)
+            if lower:
+                c, features, proteins = -c, -features, -proteins
+                direct = torch.where(prot >= 0, -direct, direct)
+            return ProteinExplanation(logit, offset, features, proteins, c, prot.to(torch.int64), direct,
+                                      targets[3].to(dev)[node])
 
     def embed_new_drugs(self, targets, interactions=None, features=None, d_norm=None):
         """Embed drugs that are NOT nodes of the training graph (extension): a compound known by its protein targets and

@@ -1950,6 +1950,7 @@ def pair_table_combo_burden(s1, s2, plan, k, aggregate='noisy_or', weights=None,
 
 
 _IN_EDGES = {}
+_PAIR_EDGES = {}
 
 
 def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
@@ -1960,32 +1961,45 @@ def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
     relation order) or edge_type int [E].  Built with torch ops on edge_index's device (CPU tensors work too): one stable
     sort of the key (dst * R + rel) * n + src.  IndexError for a node id outside [0, n_nodes) or a negative relation.
     Cached per edge tensor(s)."""
+    return _in_edges(edge_index, range_list_or_type, n_nodes, False, _IN_EDGES, 'in_edges_by_node')
+
+
+def in_edges_by_pair(edge_index, range_list_or_type, n_nodes):
+    """The in-edge CSR of include/tipk.h section 4o: as `in_edges_by_node`, but node v's positions are sorted by (SOURCE,
+    relation), so the edges of one pair (source -> v) are adjacent -- in the order they have in `in_edges_by_node`'s
+    (relation, source) segment.  -> (pe_ptr int64 [n_nodes + 1], pe_src int32 [E], pe_rel int32 [E]).  Same arguments, same
+    errors; cached per edge tensor(s), next to `in_edges_by_node`'s."""
+    return _in_edges(edge_index, range_list_or_type, n_nodes, True, _PAIR_EDGES, 'in_edges_by_pair')
+
+
+def _in_edges(edge_index, range_list_or_type, n_nodes, by_pair, cache, who):
+    """`in_edges_by_node` (by_pair False) / `in_edges_by_pair` (True): one stable sort of the edges' key."""
     def ident(t):
         return (t.data_ptr(), t._version, tuple(t.shape), str(t.device)) if torch.is_tensor(t) else None
 
     edge_index = torch.as_tensor(edge_index)
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype.is_floating_point:
-        raise _lib.TipkError('in_edges_by_node: an int tensor edge_index [2, E] expected, got %s %s'
+        raise _lib.TipkError(who + ': an int tensor edge_index [2, E] expected, got %s %s'
                              % (edge_index.dtype, tuple(edge_index.shape)))
     n, n_edges, dev = int(n_nodes), edge_index.shape[1], edge_index.device
     tag = (ident(edge_index), ident(range_list_or_type), n)
-    hit = _IN_EDGES.get(tag) if tag[1] is not None else None
+    hit = cache.get(tag) if tag[1] is not None else None
     if hit is not None:
         return hit
     rt = torch.as_tensor(range_list_or_type)
     if rt.dtype.is_floating_point:
-        raise _lib.TipkError('in_edges_by_node: an int range_list [R, 2] or edge_type [E] expected, got %s' % rt.dtype)
+        raise _lib.TipkError(who + ': an int range_list [R, 2] or edge_type [E] expected, got %s' % rt.dtype)
     if rt.dim() == 2 and rt.shape[1] == 2:
         ends = rt.to(device=dev, dtype=torch.int64)[:, 1].contiguous()
         if rt.shape[0] == 0 or int(ends[-1]) != n_edges:
-            raise _lib.TipkError('in_edges_by_node: range_list must tile all %d edges' % n_edges)
+            raise _lib.TipkError(who + ': range_list must tile all %d edges' % n_edges)
         rel = torch.bucketize(torch.arange(n_edges, device=dev), ends, right=True)
         n_rel = rt.shape[0]
     elif rt.dim() == 1 and rt.numel() == n_edges:
         rel = rt.to(device=dev, dtype=torch.int64)
         n_rel = int(rel.max()) + 1 if n_edges else 1
     else:
-        raise _lib.TipkError('in_edges_by_node: range_list [R, 2] or edge_type [%d] expected, got %s'
+        raise _lib.TipkError(who + ': range_list [R, 2] or edge_type [%d] expected, got %s'
                              % (n_edges, tuple(rt.shape)))
     src, dst = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
     if n_edges:
@@ -1994,14 +2008,14 @@ def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
             raise IndexError('node id out of range: [%d, %d] for %d nodes' % (lo, hi, n))
         if rlo < 0:
             raise IndexError('relation id out of range: %d' % rlo)
-    order = torch.sort((dst * n_rel + rel) * n + src, stable=True)[1]
+    order = torch.sort((dst * n + src) * n_rel + rel if by_pair else (dst * n_rel + rel) * n + src, stable=True)[1]
     in_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     in_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
     hit = (in_ptr, src[order].to(torch.int32).contiguous(), rel[order].to(torch.int32).contiguous())
     if tag[1] is not None:
-        if len(_IN_EDGES) > 8:
-            _IN_EDGES.clear()
-        _IN_EDGES[tag] = hit
+        if len(cache) > 8:
+            cache.clear()
+        cache[tag] = hit
     return hit
 
 
@@ -2052,6 +2066,131 @@ def rgcn_edge_attribution(h, basis, att, root, in_edges, q_node, probe, k):
                                       ptr(probe), probe.stride(0), n_q, k, ptr(contrib), ptr(src), ptr(rel), ptr(own),
                                       ptr(total), ptr(ws), stream_ptr(dev)), 'tipk_rgcn_attribution')
     return contrib, src, rel, own, total
+
+
+_PROT_EDGES = {}
+
+
+def targets_by_protein(dp_edge_index, n_prot, n_nodes):
+    """The protein-side CSR of include/tipk.h section 4o from the P -> D edge list (dp_edge_index [2, E]: row 0 the protein id,
+    row 1 n_prot + the drug id, as the data set stores it) -> (prot_ptr int64 [n_prot + 1], prot_drug int32 [E], inv_cnt
+    float32 [n_nodes], cnt int64 [n_nodes]): protein t owns the positions prot_ptr[t] .. prot_ptr[t+1], drugs ascending,
+    duplicates kept; cnt = the number of P -> D edges into every drug and inv_cnt = 1 / max(cnt, 1), correctly rounded.
+    Built with torch ops on the tensor's device; IndexError for an id out of range.  Cached per edge tensor."""
+    ei = torch.as_tensor(dp_edge_index)
+    if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype.is_floating_point:
+        raise _lib.TipkError('targets_by_protein: an int tensor dp_edge_index [2, E] expected, got %s %s'
+                             % (ei.dtype, tuple(ei.shape)))
+    n_prot, n = int(n_prot), int(n_nodes)
+    tag = (ei.data_ptr(), ei._version, tuple(ei.shape), str(ei.device), n_prot, n)
+    hit = _PROT_EDGES.get(tag)
+    if hit is not None:
+        return hit
+    prot, drug = ei[0].to(torch.int64), ei[1].to(torch.int64) - n_prot
+    if ei.shape[1]:
+        plo, phi, dlo, dhi = torch.stack([prot.min(), prot.max(), drug.min(), drug.max()]).tolist()
+        if plo < 0 or phi >= n_prot:
+            raise IndexError('protein id out of range: [%d, %d] for %d proteins' % (plo, phi, n_prot))
+        if dlo < 0 or dhi >= n:
+            raise IndexError('drug id out of range: [%d, %d] for %d drugs' % (dlo, dhi, n))
+    order = torch.sort(prot * n + drug, stable=True)[1]
+    prot_ptr = torch.zeros(n_prot + 1, dtype=torch.int64, device=ei.device)
+    prot_ptr[1:] = torch.cumsum(torch.bincount(prot, minlength=n_prot), 0)
+    cnt = torch.bincount(drug, minlength=n)
+    inv_cnt = 1.0 / cnt.clamp(min=1).to(torch.float32)
+    hit = (prot_ptr, drug[order].to(torch.int32).contiguous(), inv_cnt.contiguous(), cnt)
+    if len(_PROT_EDGES) > 8:
+        _PROT_EDGES.clear()
+    _PROT_EDGES[tag] = hit
+    return hit
+
+
+def protein_attribution_supported(n_nodes, n_prot, n_rel, n_bases, ne, pd, p, d1, d2, cat, k):
+    """Whether `protein_attribution` takes these sizes (include/tipk.h section 4o)."""
+    return bool(lib().tipk_protein_attribution_supported(int(n_nodes), int(n_prot), int(n_rel), int(n_bases), int(ne), int(pd),
+                                                         int(p), int(d1), int(d2), int(bool(cat)), int(k)))
+
+
+def protein_attribution_workspace_bytes(n_nodes, n_bases, d1, p, n_q):
+    """Bytes of workspace `protein_attribution` allocates for such a call (-1: sizes the entry does not take)."""
+    return int(lib().tipk_protein_attribution_workspace_bytes(int(n_nodes), int(n_bases), int(d1), int(p), int(n_q)))
+
+
+def protein_attribution(h_prot, hgcn_w, xe, h, layer1, layer2, pair_edges, targets, cat, q_node, probe, k):
+    """The k protein targets every query's probe . z[node] rests on most, by one fused reverse pass through both bias-free
+    R-GCN layers and the P -> D stage (include/tipk.h section 4o; no autograd, no per-edge temporary).
+
+    h_prot [P, p]: the P-P encoder's output for every protein; hgcn_w [p, pd]; xe [n, ne]: the drug embedding rows already
+    divided by d_norm; h [n, d1]: the stored relu(rgcn1(x0)) (read for its mask h > 0 only); layer1 / layer2 = (basis, att,
+    root) of rgcn1 / rgcn2; pair_edges: `in_edges_by_pair` of the D-D graph; targets: `targets_by_protein` of the P -> D
+    edges; cat: the encoder's mode; q_node int [Q]; probe fp32 [Q, d2].  All fp32 device tensors, row strides free.
+    -> (contrib float32 [Q, k], protein int32 [Q, k], direct float32 [Q, k], features float32 [Q], proteins float32 [Q]):
+    the k targeted proteins with the largest contribution c_t, descending, ties by ascending protein id, with the part of
+    c_t that arrives through the queried drug's own P -> D edges, padded with (-inf, -1, +0); features = the sum of every
+    drug's own-feature part, proteins = the sum of c_t over ALL targeted proteins (fp64 accumulation, rounded once), so
+    probe . z[node] = features + proteins up to rounding.  A node outside [0, n): padding and NaN features / proteins.
+    Bitwise repeatable, and the same for a query whatever else is in the call.  Does not synchronise (a first call checks
+    the ids of `pair_edges` and `targets` once per tensor)."""
+    h_prot, hgcn_w, xe, h, probe = _f32c(h_prot), _f32c(hgcn_w).contiguous(), _f32c(xe), _f32c(h), _f32c(probe)
+    basis1, att1, root1 = _f32c(layer1[0]).contiguous(), _f32c(layer1[1]), _f32c(layer1[2]).contiguous()
+    basis2, att2, root2 = _f32c(layer2[0]).contiguous(), _f32c(layer2[1]), _f32c(layer2[2]).contiguous()
+    pe_ptr, pe_src, pe_rel = pair_edges
+    prot_ptr, prot_drug, inv_cnt = targets[:3]
+    q_node = torch.as_tensor(q_node)
+    require_device(h_prot, hgcn_w, xe, h, probe, basis1, att1, root1, basis2, att2, root2, pe_ptr, pe_src, pe_rel, prot_ptr,
+                   prot_drug, inv_cnt, q_node)
+    if h_prot.dim() != 2 or hgcn_w.dim() != 2 or xe.dim() != 2 or h.dim() != 2 or basis1.dim() != 3 or basis2.dim() != 3 or \
+            att1.dim() != 2 or att2.dim() != 2 or hgcn_w.shape[0] != h_prot.shape[1] or xe.shape[0] != h.shape[0]:
+        raise _lib.TipkError('protein_attribution: h_prot [P, p], hgcn_w [p, pd], xe [n, ne], h [n, d1] and two layers '
+                             '(basis [B, d_in, d_out], att [R, B], root [d_in, d_out]) expected')
+    n_prot, p = h_prot.shape
+    pd, (n, ne), d1 = hgcn_w.shape[1], xe.shape, h.shape[1]
+    n_bases, d0, d2 = basis1.shape[0], basis1.shape[1], basis2.shape[2]
+    n_rel, k, cat = att1.shape[0], int(k), bool(cat)
+    if d0 != (ne + pd if cat else ne) or (not cat and ne != pd) or tuple(basis1.shape) != (n_bases, d0, d1) or \
+            tuple(basis2.shape) != (n_bases, d1, d2) or tuple(root1.shape) != (d0, d1) or tuple(root2.shape) != (d1, d2) or \
+            tuple(att1.shape) != (n_rel, n_bases) or tuple(att2.shape) != (n_rel, n_bases):
+        raise _lib.TipkError('protein_attribution: widths do not chain: ne %d, pd %d, cat %s, basis1 %s, root1 %s, att1 %s, '
+                             'basis2 %s, root2 %s, att2 %s' % (ne, pd, cat, tuple(basis1.shape), tuple(root1.shape),
+                                                                 tuple(att1.shape), tuple(basis2.shape), tuple(root2.shape),
+                                                                 tuple(att2.shape)))
+    if q_node.dim() != 1 or q_node.dtype.is_floating_point or probe.dim() != 2 or tuple(probe.shape) != (q_node.numel(), d2):
+        raise _lib.TipkError('protein_attribution: q_node int [Q] and probe [Q, %d] expected, got %s %s and %s'
+                             % (d2, q_node.dtype, tuple(q_node.shape), tuple(probe.shape)))
+    if pe_ptr.dtype != torch.int64 or pe_src.dtype != torch.int32 or pe_rel.dtype != torch.int32 or pe_ptr.numel() != n + 1 or \
+            pe_src.dim() != 1 or pe_src.shape != pe_rel.shape:
+        raise _lib.TipkError('protein_attribution: pair_edges = (int64 [%d], int32 [E], int32 [E]) of in_edges_by_pair expected'
+                             % (n + 1))
+    if prot_ptr.dtype != torch.int64 or prot_drug.dtype != torch.int32 or inv_cnt.dtype != torch.float32 or \
+            prot_ptr.numel() != n_prot + 1 or prot_drug.dim() != 1 or inv_cnt.numel() != n:
+        raise _lib.TipkError('protein_attribution: targets = (int64 [%d], int32 [E], float32 [%d]) of targets_by_protein expected'
+                             % (n_prot + 1, n))
+    if not protein_attribution_supported(n, n_prot, n_rel, n_bases, ne, pd, p, d1, d2, cat, k):
+        raise _lib.TipkError('protein_attribution: tipk_protein_attribution does not take n = %d, B = %d, widths (%d, %d, %d, '
+                             '%d, %d), k = %d (include/tipk.h 4o)' % (n, n_bases, ne, pd, p, d1, d2, k))
+    h_prot, xe, h, att1, att2, probe = (t if t.stride(0) >= t.shape[1] else t.contiguous()
+                                        for t in (h_prot, xe, h, att1, att2, probe))
+    _range_checked(pe_src, n, 'pair_edges source')
+    _range_checked(pe_rel, n_rel, 'pair_edges relation')
+    _range_checked(prot_drug, n, 'targets drug')
+    dev, n_q = h.device, q_node.numel()
+    pe_ptr, pe_src, pe_rel = pe_ptr.contiguous(), pe_src.contiguous(), pe_rel.contiguous()
+    prot_ptr, prot_drug, inv_cnt = prot_ptr.contiguous(), prot_drug.contiguous(), inv_cnt.contiguous()
+    qn = q_node.to(torch.int32).contiguous()
+    contrib, protein = _topk_outputs(n_q, k, 1, dev)
+    direct = torch.empty_like(contrib)
+    features = torch.empty(n_q, dtype=torch.float32, device=dev)
+    proteins = torch.empty(n_q, dtype=torch.float32, device=dev)
+    ws_bytes = protein_attribution_workspace_bytes(n, n_bases, d1, p, n_q)
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=dev)
+    check(lib().tipk_protein_attribution(ptr(h_prot), h_prot.stride(0), n_prot, p, ptr(hgcn_w), pd, ptr(xe), xe.stride(0), ne,
+                                         ptr(h), h.stride(0), n, d1, ptr(basis1), ptr(att1), att1.stride(0), ptr(root1),
+                                         ptr(basis2), ptr(att2), att2.stride(0), ptr(root2), d2, n_rel, n_bases, ptr(pe_ptr),
+                                         ptr(pe_src), ptr(pe_rel), pe_src.numel(), ptr(prot_ptr), ptr(prot_drug),
+                                         prot_drug.numel(), ptr(inv_cnt), int(cat), ptr(qn), ptr(probe), probe.stride(0), n_q,
+                                         k, ptr(contrib), ptr(protein), ptr(direct), ptr(features), ptr(proteins), ptr(ws),
+                                         stream_ptr(dev)), 'tipk_protein_attribution')
+    return contrib, protein, direct, features, proteins
 
 
 def drug_fold_in_supported(n_nodes, n_prot, n_rel, n_bases, ne, p, pd, d1, d2, cat):
