@@ -874,6 +874,8 @@ int tipk_pair_table_loss(const float* s1t, const float* s2t, int64_t ld, int64_t
  *   u*n+v; a query with fewer than k candidates is padded with (-inf, -1, -1).
  *   Numerics: each logit is fp32, a = z[u,k] * w[r,k] rounded, then fmaf(a, z[v,k], acc) for k ascending from 0 -- one
  *   value per pair on every route and split; the result is BITWISE repeatable (the merge across workgroups is by rank).
+ *   A candidate whose logit is NaN is never returned; +inf and -inf logits rank as values, so a -inf candidate is an entry
+ *   (valid u and v, score -inf) ahead of the padding, not padding.
  *   Filter routes: an LDS bitmap of the relation's known pairs when n_nodes^2 bits fit in 64 KB
  *   (tipk_distmult_screen_bitmap_route), binary search in the keys otherwise or under option "screen_search"; same bits.
  *   Supported (tipk_distmult_screen_supported): 1 <= n_nodes <= 46 340 (n^2 < 2^31), dim % 4 == 0 in 4..256, 1 <= k <= 1 024.

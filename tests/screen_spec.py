@@ -10,6 +10,9 @@ tiny graphs.  `check_screen` holds a returned list to the acceptance rule agains
   4. no unfiltered candidate missing from a full list has an fp64 logit above the k-th returned pair's fp64 logit + the
      two pairs' tau;
   5. padding (-inf, -1, -1) fills exactly the slots beyond the candidate count.
+`exact_screen` is the spec again, vectorised and rounded to fp32, for inputs whose fp32 logits are exact: the contract's
+order with no tolerance, NaN logits never returned, +-inf ranked as values.  `assert_screen_exact` compares with it bit for
+bit (tests/screen_cases.py holds the inputs).
 """
 import torch
 
@@ -57,6 +60,85 @@ def spec_screen(z, w, queries, k, known=None):
         for j, (s, _, u, v) in enumerate(cands[:k]):
             out_s[i, j], out_u[i, j], out_v[i, j] = s, u, v
     return out_s, out_u, out_v
+
+
+def _known_row(keys, ptr, r, n, du, device):
+    """bool [n]: the partners v of drug du with du*n+v or v*n+du a key of relation r (no n x n mask: n may be 46 340)."""
+    m = torch.zeros(n, dtype=torch.bool, device=device)
+    if keys is None:
+        return m
+    ptr = [int(x) for x in torch.as_tensor(ptr).tolist()]
+    ks = keys[ptr[r]:ptr[r + 1]].to(device=device, dtype=torch.int64)
+    a, b = ks // n, ks % n
+    m[b[a == du]] = True
+    m[a[b == du]] = True
+    return m
+
+
+def _first_k(logits32, cand, k):
+    """The first k of a stable descending sort over the candidates in ascending position -> (score fp32 [<= k], position)."""
+    pos = cand.nonzero().flatten()
+    top = torch.sort(logits32[pos], descending=True, stable=True)
+    return top.values[:k], pos[top.indices[:k]]
+
+
+def exact_screen(z, w, queries, k, known=None):
+    """The screen with NO tolerance, vectorised, on z's device -> (score float32 [Q, k], u int32 [Q, k], v int32 [Q, k]),
+    padding (-inf, -1, -1).  The logits are fp64, (z * w_r) @ z.T, rounded to fp32: for inputs whose fp32 logits equal the
+    fp64 ones (tests/test_host_screen_cases.py shows it for every case of tests/screen_cases.py) the rounding changes nothing,
+    and a sum beyond the fp32 range becomes +-inf as it does in the kernel.  Candidates: u < v for a relation query, v != u
+    for a drug query; known pairs in either direction and NaN logits are masked; the answer is the first k of a stable
+    descending sort over the candidates laid out in ascending key u*n+v.  A relation query forms its relation's n x n
+    matrix, once per distinct relation; a drug query forms its own row only, so it runs at n = 46 340."""
+    dev = z.device
+    z64, w64 = z.double(), w.double().to(dev)
+    n = z64.shape[0]
+    qs = [tuple(q) for q in torch.as_tensor(queries).reshape(-1, 2).tolist()]
+    out_s = torch.full((len(qs), k), float('-inf'), dtype=torch.float32, device=dev)
+    out_u = torch.full((len(qs), k), -1, dtype=torch.int32, device=dev)
+    out_v = torch.full((len(qs), k), -1, dtype=torch.int32, device=dev)
+    rows_of = {}
+    for i, q in enumerate(qs):
+        rows_of.setdefault(q, []).append(i)
+    ar = torch.arange(n, device=dev)
+    for (r, du), rows in rows_of.items():
+        if du < 0:
+            L = ((z64 * w64[r]) @ z64.t()).float()
+            cand = (ar[None, :] > ar[:, None]) & ~torch.isnan(L)
+            if known is not None:
+                cand &= ~known_mask(known[0], known[1], r, n, dev)
+            s, key = _first_k(L.flatten(), cand.flatten(), k)                # row-major positions ARE the keys u*n+v
+            u, v = key // n, key % n
+        else:
+            L = ((z64[du] * w64[r]) @ z64.t()).float()
+            cand = (ar != du) & ~torch.isnan(L)
+            if known is not None:
+                cand &= ~_known_row(known[0], known[1], r, n, du, dev)
+            s, v = _first_k(L, cand, k)
+            u = torch.full_like(v, du)
+        rows = torch.tensor(rows, device=dev)
+        out_s[rows, :s.numel()] = s
+        out_u[rows, :s.numel()] = u.int()
+        out_v[rows, :s.numel()] = v.int()
+    return out_s, out_u, out_v
+
+
+def assert_screen_exact(got, want):
+    """got == want, all three tensors, bit for bit (`torch.equal`: no tolerance); reports the first differing (query, slot)."""
+    names = ('score', 'u', 'v')
+    for g, x, name in zip(got, want, names):
+        assert g.shape == x.shape and g.dtype == x.dtype, (name, g.shape, x.shape, g.dtype, x.dtype)
+    if all(torch.equal(g, x.to(g.device)) for g, x in zip(got, want)):
+        return
+    diff = torch.zeros(got[0].shape, dtype=torch.bool, device=got[0].device)
+    for g, x in zip(got, want):
+        x = x.to(g.device)
+        diff |= (g != x) | (g.isnan() if g.is_floating_point() else torch.zeros_like(diff))
+    at = diff.flatten().nonzero().flatten()
+    q, j = divmod(int(at[0]), got[0].shape[1])
+    raise AssertionError('screen differs from the exact order in %d slots, first at query %d slot %d: got (%r, %d, %d), want '
+                         '(%r, %d, %d)' % (at.numel(), q, j, float(got[0][q, j]), int(got[1][q, j]), int(got[2][q, j]),
+                                           float(want[0][q, j]), int(want[1][q, j]), int(want[2][q, j])))
 
 
 def _pair64(z64, w64, r, u, v):

@@ -7,7 +7,7 @@ import types
 import pytest
 import torch
 
-from screen_spec import check_screen, keys_from_pairs, spec_screen
+from screen_spec import assert_screen_exact, check_screen, exact_screen, keys_from_pairs, spec_screen
 from tip_amd import _lib
 
 EINVAL, EUNSUPPORTED = -1, -2
@@ -165,6 +165,32 @@ def test_spec_negative_weights_and_all_known():
     every = keys_from_pairs([[], [(a, b) for a in range(4) for b in range(a + 1, 4)]], 4)
     s, u, v = spec_screen(z, w, [[1, -1], [1, 3]], 2, every)
     assert s.isneginf().all() and (u == -1).all() and (v == -1).all()
+
+
+def test_exact_screen_equals_spec_on_hand_graphs():
+    """The vectorised exact reference gives the Python-loop spec's answer on every hand-worked graph above, and
+    `assert_screen_exact` names the first differing (query, slot)."""
+    z, w = _line_graph()
+    ones = torch.ones(3, 2)
+    z4 = torch.tensor([[1.0, 0.0], [0.0, 1.0], [1.0, 1.0], [2.0, -1.0]])
+    w4 = torch.tensor([[1.0, -1.0], [0.5, 0.5]])
+    every = keys_from_pairs([[], [(a, b) for a in range(4) for b in range(a + 1, 4)]], 4)
+    for zz, ww, q, k, known in [(z, w, [[0, -1]], 2, None), (z, w, [[0, -1]], 5, None),
+                                (z, w, [[0, -1], [0, 1]], 3, keys_from_pairs([[(2, 1)]], 3)), (z, w, [[0, 1]], 2, None),
+                                (ones, torch.ones(1, 2), [[0, -1], [0, 2]], 3, None), (z4, w4, [[0, -1], [1, -1]], 3, None),
+                                (z4, w4, [[1, -1], [1, 3], [0, 3], [0, -1]], 2, every)]:
+        s, u, v = spec_screen(zz, ww, q, k, known)
+        got = exact_screen(zz, ww, q, k, known)
+        assert_screen_exact(got, (s.float(), u.int(), v.int()))
+    got = exact_screen(ones, torch.ones(1, 2), [[0, -1], [0, 2]], 3)
+    bad = [t.clone() for t in got]
+    bad[2][1, [0, 1]] = bad[2][1, [1, 0]]                                  # two tied partners in the wrong order
+    with pytest.raises(AssertionError, match='query 1 slot 0'):
+        assert_screen_exact(bad, got)
+    zn = z.clone()
+    zn[0] = float('nan')                                                   # NaN logits are never returned
+    s, u, v = exact_screen(zn, w, [[0, -1], [0, 0]], 2)
+    assert s.tolist() == [[6.0, float('-inf')], [float('-inf')] * 2] and u.tolist() == [[1, -1], [-1, -1]]
 
 
 def test_check_screen_catches_mistakes():

@@ -1062,7 +1062,8 @@ def distmult_screen(z, rel_w, queries, k, known=None):
     partners v != u); read on the host.  known: None or (keys int64 u*n+v sorted inside each relation, ptr int64
     [n_rel + 1]) on z's device -- the sampler's layout (`neg_sampling._cached_keys`); a list without keys drops nothing.
     -> (logits float32 [Q, k], u int32 [Q, k], v int32 [Q, k]), descending logit then ascending key; (-inf, -1, -1)
-    pads a query with fewer than k candidates.  Synchronises the current stream once (the query list goes to the device)."""
+    pads a query with fewer than k candidates.  A candidate whose logit is NaN is never returned; +inf and -inf logits rank
+    as values, so a -inf candidate is an entry (valid u and v, score -inf) ahead of the padding, not padding.  Synchronises the current stream once (the query list goes to the device)."""
     z, rel_w = _distmult_operands(z, rel_w, 'distmult_screen')
     keys, kptr = _relation_known(known)
     q = torch.as_tensor(queries).to('cpu', torch.int32).reshape(-1, 2).contiguous()
