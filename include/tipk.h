@@ -1653,6 +1653,68 @@ int     tipk_protein_attribution(const float* hp, int64_t ld_hp, int64_t n_prot,
                                  float* out_contrib, int32_t* out_protein, float* out_direct /* [n_q x k] */,
                                  float* out_features, float* out_proteins /* [n_q] */, void* workspace, tipk_stream_t stream);
 
+/* 4p. Confidence of a side-effect prediction (serving; no reference call site): a Gaussian (Laplace) posterior of DistMult
+ *     decoder rows from the Hessian of 4m, and the pair top-k of 4d ranked on a key that knows the variance of every logit.
+ *
+ *   Model (a modelling choice).  Row b has the Hessian H_b of 4m at w_b (l2 > 0: positive definite)
+ *   and P_b recorded pairs; its posterior is N(w_b, (P_b H_b)^-1), the embeddings taken as exact.  With H_b = L_b L_b^T and
+ *   W_b = P_b^(-1/2) L_b^-1 (lower triangular) the logit s = phi . w_b of the feature phi = z[u] * z[v] has the variance
+ *   var = |W_b phi|^2.
+ *
+ *   tipk_spd_factor.  DEVICE: hess fp32 [n_rows x dim x dim] row-major, of which ONLY the lower triangle (column <= row) is
+ *   read; row_scale fp32 [n_rows] (P_b^(-1/2), the caller's).  Output: out_l [n_rows x dim x dim] row-major, L_b =
+ *   chol(H_b); out_w [n_rows x dim x dim] = W_b = row_scale[b] L_b^-1 stored TRANSPOSED: W_b[i][j] is at
+ *   out_w[(b * dim + j) * dim + i] -- the 4 columns x 16 rows a lane group of the query's matrix-core operand reads are 64
+ *   consecutive floats; status int32 [n_rows], 1 = factored.  The strict upper triangles of L_b and W_b (j > i) are exact
+ *   +0.0f.  A row with a pivot that is not > 0 or not finite, a non-finite entry in its lower triangle or a non-finite
+ *   row_scale has status 0 and L_b = W_b = 0 throughout; no other row is affected.
+ *   Arithmetic, fp32, one wavefront per row: the right-looking Cholesky of tipk_newton_step (4m; the same loop): column k
+ *   takes d = sqrtf(pivot), L[i][k] = L[i][k] / d for i > k, then L[i][c] = fmaf(-L[i][k], L[c][k], L[i][c]) for
+ *   k < c <= i.  Column c of W_b by forward substitution of row_scale[b] e_c: x_k = x_k / L[k][k], then
+ *   x_i = fmaf(-L[i][k], x_k, x_i) for i > k, k ascending from c.  BITWISE repeatable; a row's bits depend on that row alone.
+ *   Supported: 1 <= dim <= 32, n_rows < 2^31.  Status: TIPK_EINVAL for a negative n_rows, dim < 1, a NULL pointer (with
+ *   n_rows > 0); then TIPK_EUNSUPPORTED; n_rows == 0 is TIPK_OK with no launch.
+ *
+ *   tipk_distmult_pair_conf_topk.  z [n_nodes x dim], rel_w [n_rel x dim], w_fac [n_rel x dim x dim] = the out_w of
+ *   tipk_spd_factor for the same rows; pair_u / pair_v and the pair-major known lists exactly as in 4d.
+ *   Arithmetic, fp32, per (pair, relation r): phi_j = z[u,j] * z[v,j] rounded once; the logit s and every
+ *   y_i = sum_j W_r[i][j] phi_j are fmaf chains over ALL j < dim ascending from +0.0f (v_mfma_f32_16x16x4_f32 is that chain;
+ *   the zeros of the upper triangle are multiplied, so an infinite phi_j gives NaN); the rows are dealt to four groups,
+ *   group g owning i = 16 h + 4 g + x (h = 0, 1; x = 0..3; rows >= dim count as y_i = 0): t_g = the chain
+ *   fmaf(y_i, y_i, t_g) from +0.0f with h then x ascending, and var = (t_0 + t_1) + (t_2 + t_3).
+ *   Key: mode TIPK_CONF_MODERATED (0): s / sqrtf(fmaf(pi/8, var, 1.0f)), pi/8 = 0.39269908169872414f -- the logit of
+ *   MacKay's moderated probability; mode TIPK_CONF_BOUND (1): fmaf(c, sqrtf(var), s), c finite (c < 0 a lower bound of the
+ *   logit, c > 0 an upper one, c == 0 the logit itself); sqrtf and the division correctly rounded.
+ *   Output per pair (device), each [n_pairs x k]: out_key fp32, out_rel int32, out_logit fp32, out_var fp32 = the k relations
+ *   with the largest key among those not known for the pair, key descending, ties by ascending relation id; a row with fewer
+ *   than k candidates -- and the whole row of a pair with an id outside [0, n_nodes) -- is padded with (-inf, -1, -inf, +inf).
+ *   A NaN key is never returned.  dense_logit / dense_var fp32 [n_pairs x n_rel] (nullable together): s and var of EVERY
+ *   relation, known ones included; (-inf, +inf) throughout for a pair with an id out of range.  The top-k bits are the same
+ *   with and without the dense outputs.  No [n_pairs x n_rel x dim] temporary, no float atomics: BITWISE repeatable, a
+ *   pair's bits the same whatever else is in the call.
+ *   Work: persistent workgroups of 16 wavefronts, one per CU; a workgroup takes 16 pairs (the N of the matrix-core tile,
+ *   their phi resting in registers) through all relations in tiles of 256, wavefront w scoring 16 relations of the tile with
+ *   w_fac read straight from L2; then wavefront p selects for pair p from the tile in LDS.
+ *   Supported: 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..32, 1 <= n_rel <= 65 536, 0 <= k <= 128 (k == 0: the dense
+ *   outputs only; the four top-k pointers may be NULL).
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for k < 0, a negative size, n_nodes, n_rel or dim < 1,
+ *   a mode that is not 0 or 1, c not finite, a NULL required pointer (with n_pairs > 0), known arrays or dense outputs given
+ *   only in part; then TIPK_EUNSUPPORTED outside the supported range; n_pairs == 0 is TIPK_OK with no launch.
+ *   Nothing lives in host memory: the entries do NOT synchronise or allocate and may be captured into a hipGraph.
+ */
+#define TIPK_CONF_MODERATED 0
+#define TIPK_CONF_BOUND     1
+int     tipk_spd_factor(const float* hess, const float* row_scale, int64_t n_rows, int dim, float* out_l, float* out_w,
+                        int32_t* status, tipk_stream_t stream);
+int     tipk_distmult_pair_conf_topk_supported(int64_t n_nodes, int dim, int64_t n_rel, int k);
+int     tipk_distmult_pair_conf_topk(const float* z, int64_t n_nodes, int dim, const float* rel_w, const float* w_fac,
+                                     int64_t n_rel, const int32_t* pair_u, const int32_t* pair_v /* device */, int64_t n_pairs,
+                                     const int64_t* known_pair_keys, const int64_t* known_pair_ptr, const int32_t* known_rel,
+                                     int64_t n_known_pairs /* nullable together */, int k, int mode, float c,
+                                     float* out_key, int32_t* out_rel, float* out_logit, float* out_var /* [n_pairs x k] */,
+                                     float* dense_logit, float* dense_var /* [n_pairs x n_rel], nullable together */,
+                                     tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

@@ -23,9 +23,10 @@
 // No atomics, no workgroup waits for another, every trip count depends on sizes and list lengths only: BITWISE repeatable.
 //
 // Step, newton_step_kernel: one wavefront per relation; lane j owns component j.  Armijo test with 16 ulp slack, Cholesky of
-//   the trial Hessian in LDS (right-looking, column k by the lanes i > k), the two triangular solves with the vector in
-//   registers (one shuffle per column); a pivot that is not > 0 gives the scaled steepest-descent direction.
-#include "tipk_common.h"
+//   the trial Hessian in LDS (ch_factor of tipk_chol.h: right-looking, column k by the lanes i > k), the two triangular
+//   solves with the vector in registers (one shuffle per column); a pivot that is not > 0 gives the scaled steepest-descent
+//   direction.
+#include "tipk_chol.h"
 #include <math.h>
 
 namespace {
@@ -38,7 +39,7 @@ constexpr int SF_PAD = 4;                   // floats behind a row of the LDS im
 constexpr int SF_CW = 2 * SF_RB + 4;        // floats of a lane's coefficient row: 8 used; 12 words apart, the 16-byte stores of
                                             // 8 consecutive lanes fall on 32 different banks
 constexpr int SF_CH = 256;                  // recorded pairs per chunk of the sparse pass
-constexpr int SF_DMAX = 32;
+constexpr int SF_DMAX = CH_DMAX;
 constexpr int64_t SF_NMAX = 46340;
 constexpr int64_t SF_FITMAX = 65536;
 constexpr int64_t SF_TARGET_WGS = 1024;     // dense workgroups to aim for: four per CU
@@ -401,21 +402,7 @@ __global__ void __launch_bounds__(TIPK_WAVE) newton_step_kernel(StepArgs a) {
         } else {
             // Cholesky of the trial Hessian; L[i][k], i >= k
             float hmax = sf_wave_max(own ? L[lane][lane] : -INFINITY);
-            bool ok = true;
-            for (int k = 0; k < dim; ++k) {
-                const float piv = L[k][k];
-                if (!(piv > 0.f) || piv - piv != 0.f) { ok = false; break; }       // uniform: every lane reads L[k][k]
-                const float d = sqrtf(piv);
-                __syncthreads();
-                if (own && lane > k) L[lane][k] = L[lane][k] / d;
-                if (lane == k) L[k][k] = d;
-                __syncthreads();
-                if (own && lane > k) {
-                    const float lik = L[lane][k];
-                    for (int c = k + 1; c <= lane; ++c) L[lane][c] = fmaf(-lik, L[c][k], L[lane][c]);
-                }
-                __syncthreads();
-            }
+            const bool ok = ch_factor(L, dim, lane);
             if (ok) {
                 float b = -g;                                   // L y = -g, then L^T p = y
                 for (int k = 0; k < dim; ++k) {

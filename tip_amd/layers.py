@@ -47,9 +47,27 @@ CombinationRisk = namedtuple('CombinationRisk', ['burden', 'ptr', 'best_burden',
 DrugProfile = namedtuple('DrugProfile', ['expected', 'candidates', 'top_expected', 'top_relation'])
 RankReport = namedtuple('RankReport', ['rank', 'logit', 'mrr', 'hits', 'per_relation', 'macro_mrr', 'unranked'])
 
+
+class DecoderPosterior(namedtuple('DecoderPosterior', ['weight', 'factor', 'n_pairs', 'relation', 'known'])):
+    """TIP.decoder_posterior's result: the Gaussian (Laplace) posterior N(weight[b], covariance()[b]) of B DistMult rows.
+    factor [B, dim, dim]: W_b = P_b^(-1/2) chol(H_b)^-1 in the layout `ops.spd_factor` writes (factor[b, j, i] = W_b[i][j]);
+    n_pairs int64 [B] = P_b; relation int64 [B]: the side-effect id of every row (global ids for the model's rows, 0..B-1 for
+    given rows); known: None for the model's rows, else the given pairs as pair-major lists (`ops.known_relations_by_pair`)."""
+    __slots__ = ()
+
+    def covariance(self):
+        """Sigma [B, dim, dim] = W^T W = (P_b H_b)^-1, rows and columns in the order of `weight`'s components."""
+        return self.factor @ self.factor.transpose(1, 2)
+
+
+# TIP.side_effects_confidence's result: per pair row the k best side effects by the chosen key, best first (padding:
+# probabilities 0, logit -inf, std +inf, relation -1)
+ConfidentSideEffects = namedtuple('ConfidentSideEffects', ['probability', 'mean_probability', 'logit', 'std', 'relation',
+                                                           'dense_logit', 'dense_std'])
+
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects',
-           'CombinationRisk']
+           'CombinationRisk', 'DecoderPosterior', 'ConfidentSideEffects']
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1336,6 +1354,36 @@ def _pair_known(d, mode, rel):
     return known if rel is None else ops.restrict_known_relations(known, rel, d.n_dd_et)
 
 
+def _training_pairs_of(d, rel):
+    """The training pairs of the side effects `rel` (int64, host), each unordered pair once, in the (edge_index, ptr) form
+    `ops.fit_pairs_csr` takes: relation i of the result is side effect rel[i]."""
+    idx = d.dd_train_idx.to('cpu', torch.int64)
+    rng = torch.as_tensor(d.dd_train_range).to('cpu', torch.int64).reshape(-1, 2)
+    n = int(d.n_drug)
+    cols, counts = [], []
+    for r in rel.tolist():
+        e = idx[:, int(rng[r, 0]):int(rng[r, 1])]
+        key = torch.unique(torch.minimum(e[0], e[1]) * n + torch.maximum(e[0], e[1]))
+        cols.append(torch.stack([torch.div(key, n, rounding_mode='floor'), key % n]))
+        counts.append(key.numel())
+    ptr = torch.zeros(len(counts) + 1, dtype=torch.int64)
+    if counts:
+        ptr[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0)
+    return (torch.cat(cols, 1) if cols else torch.zeros((2, 0), dtype=torch.int64)), ptr
+
+
+def _pair_major_known(fp, n, dev):
+    """The distinct recorded pairs of a `FitPairs` as pair-major known lists on `dev` (include/tipk.h section 4d): keys
+    u * n + v (u <= v) ascending, ptr, and inside a pair's block the ascending ids of the relations that list it."""
+    b = fp.ptr.numel() - 1
+    rel = torch.repeat_interleave(torch.arange(b, dtype=torch.int64), fp.ptr[1:] - fp.ptr[:-1])
+    c = torch.unique((fp.u.to(torch.int64) * int(n) + fp.v.to(torch.int64)) * max(b, 1) + rel)
+    keys, counts = torch.unique_consecutive(torch.div(c, max(b, 1), rounding_mode='floor'), return_counts=True)
+    ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return keys.to(dev), ptr.to(dev), (c % max(b, 1)).to(torch.int32).to(dev)
+
+
 def _checked_triples(triples, d, dev):
     """The triples a rank evaluation ranks -> (edge_index [2, T], edge_type int64 [T]) on `dev`: the held-out set of `d` for
     None, else the given (edge_index, edge_type), refused with ValueError unless int tensors of these shapes with ids in
@@ -2053,6 +2101,149 @@ class TIP(nn.Module):
             gn = grad.abs().amax(dim=1) if b else grad.new_zeros(0)
             return NewSideEffects(w, loss, gn, info[:, 1], info[:, 0], fp.n_pairs.to(dev), dec,
                                   tuple(t.to(dev) for t in fp.known))
+
+    def decoder_posterior(self, pairs=None, weight=None, relations=None, l2=1e-4, neg_weight=1.0, new=None):
+        """How sure the decoder is of its rows (extension): a Gaussian (Laplace) posterior N(w_b, (P_b H_b)^-1) of DistMult
+        rows, from the exact Hessian H_b of the objective `fit_side_effects` minimises (`ops.distmult_posterior`:
+        `tipk_distmult_fit_stats`, then `tipk_spd_factor`; under no_grad on `self.embeddings`).  The objective is a mean, so
+        counted in observations the negative log posterior is P_b L_b: P_b positives, neg_weight P_b observations' worth of
+        weight on the unrecorded pairs, and a Gaussian prior of precision l2 P_b.
+        pairs = None: the model's trained rows with, per side effect, its training pairs -- each unordered pair once;
+        `relations` restricts the rows (None = all) and `relation` of the result holds global ids.  This is the same formula
+        at the trained row: the Hessian is that of the objective the row was trained on, but l2 is a CHOSEN prior -- the
+        model itself trains without one -- and the trained row need not be the optimum.
+        Otherwise pairs is what `fit_side_effects` takes and weight [B, dim] the rows, e.g. `fitted.weight`: for a fitted row
+        this is the Laplace approximation at its optimum (same l2 and neg_weight).  `relation` is 0..B-1 and `known` the
+        given lists in pair-major form.  new: the `NewDrugs` of `embed_new_drugs`, as in `fit_side_effects`.
+        The embeddings are treated as exact.  The reported spread is therefore a lower bound on the model's uncertainty.
+        -> DecoderPosterior(weight [B, dim], factor [B, dim, dim], n_pairs int64 [B], relation int64 [B], known).
+        ValueError for l2 <= 0, neg_weight <= 0, an id out of range, a `weight` of the wrong shape, a row without pairs, or
+        rows whose factorisation failed (their ids are named); NotImplementedError for the NN decoder, a relation-sharded
+        model, or sizes `tipk_distmult_fit_supported` refuses.  Reads the factor's status: one synchronisation."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('decoder_posterior is the posterior of DistMult rows; this model scores with the NN decoder')
+        _refuse_sharded(self.shard, 'side effects')
+        if not float(l2) > 0:
+            raise ValueError('l2 must be > 0 (the prior keeps the Hessian positive definite), not %r' % (l2,))
+        if not float(neg_weight) > 0:
+            raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
+        d = self.data
+        n_all = d.n_drug + (0 if new is None else int(new.z.shape[0]))
+        dim = self.decoder.in_dim
+        if pairs is None:
+            if weight is not None:
+                raise ValueError('weight: rows are given together with their pairs')
+            rel = torch.arange(d.n_dd_et, dtype=torch.int64) if relations is None \
+                else torch.as_tensor(relations).to('cpu', torch.int64).reshape(-1)
+            if rel.numel() and (int(rel.min()) < 0 or int(rel.max()) >= d.n_dd_et):
+                raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (int(rel.min()), int(rel.max()), d.n_dd_et))
+            pairs = _training_pairs_of(d, rel)
+        else:
+            if relations is not None:
+                raise ValueError('relations selects rows of the model; given rows are numbered 0..B-1')
+            rel = None
+        fp = ops.fit_pairs_csr(pairs, n_all, neg_weight)
+        b = fp.dense_w.numel()
+        if rel is None:
+            rel = torch.arange(b, dtype=torch.int64)
+            if weight is None:
+                raise ValueError('weight: the rows [%d, %d] of the given pairs are needed' % (b, dim))
+            weight = torch.as_tensor(weight)
+            if tuple(weight.shape) != (b, dim):
+                raise ValueError('weight: [%d, %d] expected, got %s' % (b, dim, tuple(weight.shape)))
+        if not ops.distmult_fit_supported(n_all, dim, max(b, 1)):
+            raise NotImplementedError('decoder_posterior: tipk_distmult_fit_stats does not take n = %d, dim = %d, %d side effects '
+                                      '(include/tipk.h 4m)' % (n_all, dim, b))
+        empty = torch.nonzero(fp.n_pairs == 0).reshape(-1)
+        if empty.numel():
+            raise ValueError('a posterior needs at least one recorded pair; side effects without: %s' % rel[empty].tolist()[:20])
+        with torch.no_grad():
+            z = self.embeddings.detach()
+            dev = z.device
+            if new is not None:
+                z = torch.cat([z, new.z.detach().to(dev)])
+            custom = weight is not None
+            w = weight.detach().to(dev, torch.float32) if custom else self.decoder.weight.detach()[rel.to(dev)]
+            w = w.contiguous()
+            factor, _, status, _ = ops.distmult_posterior(z, w, fp, float(l2))
+            bad = torch.nonzero(status == 0).reshape(-1).cpu()
+            if bad.numel():
+                raise ValueError('the Hessian of %d row(s) is not positive definite or not finite; side effects: %s'
+                                 % (bad.numel(), rel[bad].tolist()[:20]))
+            known = _pair_major_known(fp, n_all, dev) if custom else None
+            return DecoderPosterior(w, factor, fp.n_pairs.to(dev), rel.to(dev), known)
+
+    def side_effects_confidence(self, pairs, posterior, k=10, rank_by='moderated', z_score=1.645, exclude=None, dense=False,
+                                new=None):
+        """Serving (extension): `side_effects` with error bars -- for every drug pair of `pairs` [2, P] the k side effects of
+        `posterior` (a `DecoderPosterior`) that rank highest once the spread of each logit under the posterior is taken into
+        account (one `tipk_distmult_pair_conf_topk` launch on `self.embeddings`, under no_grad).  For the triple (u, v, b)
+        with phi = z[u] * z[v]: logit s = phi . w_b, variance var = |W_b phi|^2.
+        rank_by: 'moderated' ranks by MacKay's moderated probability sigma(s / sqrt(1 + pi var / 8)) -- an uncertain logit is
+        pulled towards 1/2; 'lower' by s - z_score sqrt(var) (what the model is confident of); 'upper' by
+        s + z_score sqrt(var) (what it cannot rule out).
+        exclude: for the model's rows as `side_effects` ('train', 'all', None); only the posterior's side effects are
+        candidates and global ids are returned.  For given rows True drops the pairs the rows were given with, None nothing.
+        dense = True also returns every side effect's logit and std [P, B] (recorded ones included, columns in the
+        posterior's order).  new: the `NewDrugs` the posterior was made with; ids n_drug + i are then allowed.
+        The embeddings are treated as exact.  The reported spread is therefore a lower bound on the model's uncertainty.
+        -> ConfidentSideEffects(probability [P, k] = the moderated probability, mean_probability = sigma(s), logit, std =
+        sqrt(var), relation int64 [P, k], dense_logit, dense_std); padding: probabilities 0, logit -inf, std +inf, relation -1.
+        ValueError for a bad rank_by, a z_score that is not finite, k outside 0..128, an id out of range or a bad exclude;
+        NotImplementedError for the NN decoder, a relation-sharded model or sizes the entry refuses."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('side_effects_confidence ranks with DistMult rows; this model scores with the NN decoder')
+        _refuse_sharded(self.shard, 'side effects')
+        if rank_by not in ('moderated', 'lower', 'upper'):
+            raise ValueError("rank_by must be 'moderated', 'lower' or 'upper', not %r" % (rank_by,))
+        if not math.isfinite(float(z_score)):
+            raise ValueError('z_score must be finite, not %r' % (z_score,))
+        k = int(k)
+        if k < 0 or k > 128:
+            raise ValueError('k must be in 0..128, not %d' % k)
+        custom = posterior.known is not None
+        if custom:
+            if exclude not in (True, False, None):
+                raise ValueError('exclude must be True or None for given rows, not %r' % (exclude,))
+        else:
+            _check_known_mode('exclude', exclude)
+        d = self.data
+        n_all = d.n_drug + (0 if new is None else int(new.z.shape[0]))
+        pairs = torch.as_tensor(pairs)
+        if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype.is_floating_point:
+            raise ValueError('pairs: an int tensor [2, P] expected, got %s %s' % (pairs.dtype, tuple(pairs.shape)))
+        if pairs.numel():
+            lo, hi = torch.stack([pairs.min(), pairs.max()]).tolist()
+            if lo < 0 or hi >= n_all:
+                raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (lo, hi, n_all))
+        b, dim = posterior.weight.shape
+        if b < 1 or not ops.distmult_pair_conf_topk_supported(n_all, dim, b, k):
+            raise NotImplementedError('side_effects_confidence: tipk_distmult_pair_conf_topk does not take n = %d, dim = %d, '
+                                      '%d side effects (include/tipk.h 4p)' % (n_all, dim, b))
+        with torch.no_grad():
+            z = self.embeddings.detach()
+            dev = z.device
+            if new is not None:
+                z = torch.cat([z, new.z.detach().to(dev)])
+            pairs = pairs.to(dev)
+            if custom:
+                known = posterior.known if exclude else None
+            else:
+                full = posterior.relation.numel() == d.n_dd_et and \
+                    bool((posterior.relation == torch.arange(d.n_dd_et, device=posterior.relation.device)).all())
+                known = _pair_known(d, exclude, None if full else posterior.relation.to(dev))
+                if known is not None and n_all != d.n_drug:              # the lists are keyed u * n_drug + v: same pairs, same order
+                    keys = known[0].to(torch.int64)
+                    known = (torch.div(keys, d.n_drug, rounding_mode='floor') * n_all + keys % d.n_drug,) + tuple(known[1:])
+            mode, c = (0, 0.0) if rank_by == 'moderated' else (1, -float(z_score) if rank_by == 'lower' else float(z_score))
+            _, idx, logit, var, d_logit, d_var = ops.distmult_pair_conf_topk(z, posterior.weight, posterior.factor, pairs, k,
+                                                                             mode, c, known, dense)
+            have = idx >= 0
+            zero = torch.zeros_like(logit)
+            prob = torch.where(have, torch.sigmoid(logit / torch.sqrt(1.0 + (math.pi / 8) * var)), zero)
+            mean = torch.where(have, torch.sigmoid(logit), zero)
+            return ConfidentSideEffects(prob, mean, logit, torch.sqrt(var), _ids_at(idx, posterior.relation.to(dev)), d_logit,
+                                        None if d_var is None else torch.sqrt(d_var))
 
     def drug_profile(self, drugs=None, k=10, exclude='all', relations=None, partner_weights=None, new=None):
         """Serving (extension): the liability profile of single drugs -- for every side effect, with how many OTHER drugs the

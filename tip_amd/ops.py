@@ -1626,6 +1626,73 @@ def distmult_fit(z, fp, l2=1e-4, init=None, max_iter=16, gtol=1e-5):
     return w, loss, grad, info
 
 
+CONF_MODES = {'moderated': 0, 'bound': 1}                             # TIPK_CONF_MODERATED, TIPK_CONF_BOUND
+
+
+def distmult_pair_conf_topk_supported(n_nodes, dim, n_rel, k=10):
+    return bool(lib().tipk_distmult_pair_conf_topk_supported(n_nodes, dim, n_rel, k))
+
+
+def spd_factor(hess, row_scale):
+    """Cholesky factors of B symmetric positive definite matrices and their scaled inverses (include/tipk.h section 4p).
+    hess [B, dim, dim] (only the lower triangle is read), row_scale [B].
+    -> (L [B, dim, dim] = chol(hess), W [B, dim, dim] = row_scale * L^-1 in the PHYSICAL layout the query entry reads:
+    W[b, j, i] holds the logical entry (i, j), i.e. the tensor is the transpose of the lower-triangular factor; status
+    int32 [B], 1 = factored, 0 = not positive definite or not finite: that row's L and W are zeros).  Does not synchronise."""
+    hess, row_scale = _f32c(hess).contiguous(), _f32c(row_scale).contiguous()
+    require_device(hess, row_scale)
+    if hess.dim() != 3 or hess.shape[1] != hess.shape[2] or tuple(row_scale.shape) != (hess.shape[0],):
+        raise _lib.TipkError('spd_factor: hess [B, dim, dim] and row_scale [B] expected, got %s and %s'
+                             % (tuple(hess.shape), tuple(row_scale.shape)))
+    dev = hess.device
+    out_l, out_w = torch.empty_like(hess), torch.empty_like(hess)
+    status = torch.empty(hess.shape[0], dtype=torch.int32, device=dev)
+    check(lib().tipk_spd_factor(ptr(hess), ptr(row_scale), hess.shape[0], hess.shape[1], ptr(out_l), ptr(out_w), ptr(status),
+                                stream_ptr(dev)), 'tipk_spd_factor')
+    return out_l, out_w, status
+
+
+def distmult_pair_conf_topk(z, rel_w, w_fac, pairs, k, mode, c=0.0, known=None, dense=False):
+    """The k best relations of every pair by a key that knows the variance of the logit under the decoder rows' Laplace
+    posterior (include/tipk.h section 4p).  w_fac [n_rel, dim, dim]: the W of `spd_factor` / `distmult_posterior`; pairs and
+    known as `distmult_pair_topk`; mode 0 | 'moderated': key = s / sqrt(1 + pi/8 var); 1 | 'bound': key = s + c sqrt(var).
+    -> (key fp32 [P, k], relation int32 [P, k], logit [P, k], var [P, k], dense_logit, dense_var): key descending then
+    ascending relation id, padding (-inf, -1, -inf, +inf); the dense pair [P, n_rel] (known relations included) with
+    dense = True, else (None, None).  Does not synchronise."""
+    z, rel_w = _distmult_operands(z, rel_w, 'distmult_pair_conf_topk')
+    w_fac = _f32c(w_fac).contiguous()
+    require_device(w_fac)
+    n, dim, n_rel, k = z.shape[0], z.shape[1], rel_w.shape[0], int(k)
+    if tuple(w_fac.shape) != (n_rel, dim, dim):
+        raise _lib.TipkError('distmult_pair_conf_topk: w_fac [%d, %d, %d] expected, got %s' % (n_rel, dim, dim, tuple(w_fac.shape)))
+    mode = CONF_MODES.get(mode, mode)
+    dev = z.device
+    pu, pv, keys, kptr, krel, n_keys = _pair_topk_lists(pairs, known, dev)
+    n_p = pu.numel()
+    out_key, out_rel = _topk_outputs(n_p, k, 1, dev)
+    out_logit, out_var = torch.empty_like(out_key), torch.empty_like(out_key)
+    d_logit = torch.empty((n_p, n_rel), dtype=torch.float32, device=dev) if dense else None
+    d_var = torch.empty((n_p, n_rel), dtype=torch.float32, device=dev) if dense else None
+    check(lib().tipk_distmult_pair_conf_topk(ptr(z), n, dim, ptr(rel_w), ptr(w_fac), n_rel, ptr(pu), ptr(pv), n_p, ptr(keys),
+                                             ptr(kptr), ptr(krel), n_keys, k, int(mode), float(c), ptr(out_key), ptr(out_rel),
+                                             ptr(out_logit), ptr(out_var), ptr(d_logit), ptr(d_var), stream_ptr(dev)),
+          'tipk_distmult_pair_conf_topk')
+    return out_key, out_rel, out_logit, out_var, d_logit, d_var
+
+
+def distmult_posterior(z, w, fp, l2):
+    """The Laplace posterior N(w_b, (P_b H_b)^-1) of the decoder rows w [B, dim] given the recorded pairs `fp` (a `FitPairs`):
+    `distmult_fit_stats` at w, then `spd_factor` with row_scale = P_b^(-1/2) (include/tipk.h sections 4m, 4p).
+    -> (W [B, dim, dim] physical layout of `spd_factor`, L, status int32 [B], hess [B, dim, dim]).  Synchronises nowhere: the
+    caller reads `status`."""
+    if not float(l2) > 0:
+        raise _lib.TipkError('distmult_posterior: l2 must be > 0 (the prior makes the Hessian positive definite), not %r' % (l2,))
+    _, _, hess = distmult_fit_stats(z, w, fp, l2)
+    scale = fp.n_pairs.to(device=hess.device, dtype=torch.float64).clamp(min=1.0).rsqrt().to(torch.float32)
+    out_l, out_w, status = spd_factor(hess, scale)
+    return out_w, out_l, status, hess
+
+
 def targets_by_relation(edge_index, edge_type, n_rel):
     """Triples (u, v, r) grouped by the relation query r that ranks the pair {u, v} -- for the screen rank entry
     (include/tipk.h section 4h) -> (q_rel int32 [Q], tgt_ptr int64 [Q + 1], tgt_u int32 [T], tgt_v int32 [T], order int64
