@@ -359,20 +359,8 @@ def _model_of(model, sub=None):
     return ('table', s1, s2)
 
 
-@pytest.fixture
-def sampler_cache_as_found():
-    """`TIP()` draws its held-out negatives once, and that adds an entry to the sampler's process-wide key cache (nine
-    entries, then emptied).  The cache is left as it was found, so a test that runs later and counts on its own entry
-    staying cached meets the state it would meet without this file."""
-    from tip_amd import neg_sampling
-    before = dict(neg_sampling._key_cache)
-    yield
-    neg_sampling._key_cache.clear()
-    neg_sampling._key_cache.update(before)
-
-
 @pytest.mark.parametrize('decoder', ['distmult', 'nn'])
-def test_tip_combination_risk(decoder, sampler_cache_as_found):
+def test_tip_combination_risk(decoder):
     from tip_amd.layers import TIP, CombinationRisk, Setting
     torch.manual_seed(0)
     model = TIP(Setting(), torch.device(DEV), data_path=None, decoder=decoder)    # the bundled graph

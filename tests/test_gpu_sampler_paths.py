@@ -25,7 +25,7 @@ FORMS_ALL = ('int64', 'int32', 'packed')
 @pytest.fixture(autouse=True)
 def _fresh_key_cache():
     from tip_amd import neg_sampling as NS
-    NS._key_cache.clear()            # (keyed by data pointers: a freed tensor's address may come back with other positives)
+    NS._key_cache.clear()            # (every case builds its own keys; an entry pins its tensors, so emptying also frees them)
     yield
     NS._key_cache.clear()
 

@@ -142,13 +142,15 @@ def test_known_relations_by_pair_vs_dict():
     ei = torch.tensor([[0, 1, 0, 3, 0, 5, 6, 2],
                        [1, 0, 1, 3, 1, 2, 6, 5]])
     rl = [[0, 4], [4, 4], [4, 6], [6, 8]]
-    got = ops.known_relations_by_pair(ei, torch.tensor(rl), n)
+    rt = torch.tensor(rl)
+    got = ops.known_relations_by_pair(ei, rt, n)
     want = known_from_dict(_dict_of(ei.tolist(), rl, n), n)
     assert _as_lists(got) == _as_lists(want)
     assert got[0].dtype == torch.int64 and got[1].dtype == torch.int64 and got[2].dtype == torch.int32
     keys, ptr, rel = _as_lists(got)
     assert keys == [0 * n + 1, 2 * n + 5, 3 * n + 3, 6 * n + 6] and ptr == [0, 2, 4, 5, 6] and rel == [0, 2, 2, 3, 0, 3]
-    assert ops.known_relations_by_pair(ei, torch.tensor(rl), n) is got      # cached per edge tensor
+    assert ops.known_relations_by_pair(ei, rt, n) is got                    # cached per (edge tensor, range tensor)
+    assert _as_lists(ops.known_relations_by_pair(ei, torch.tensor(rl), n)) == _as_lists(got)
 
     # a second list merged in: a new pair, a new relation of an old pair, a repeat of an old entry
     ei2 = torch.tensor([[4, 1, 5], [2, 0, 2]])

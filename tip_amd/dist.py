@@ -446,7 +446,7 @@ def attach_shard(encoder, shard):
     for layer in (encoder.rgcn1, encoder.rgcn2):
         assert layer.num_relations == int(shard.rel_ids.numel()), 'build the encoder for the local relation count'
         layer.shard = shard
-        layer._cache.key = None                 # plans of an earlier (unsharded) call are stale
+        layer._cache.clear()                    # plans of an earlier (unsharded) call are stale
     return shard
 
 

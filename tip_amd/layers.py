@@ -7,8 +7,9 @@ launches the HIP kernels of libtipk through the C ABI.  There is no PyG and no C
 
 Static-graph caching: the reference's `GCNConv(cached=True)` (`src/layers.py:386-387`) keeps the
 normalised P-P graph after the first call.  Here EVERY layer caches its gather plans, keyed by the
-identity (storage pointer, shape, version counter) of the edge tensors it was given, because all
-three TIP graphs are constant during training.  Pass a new tensor (or modify in place) to rebuild.
+identity and version of the edge tensors it was given and pinning them while cached
+(`_cache.DerivedCache`), because all three TIP graphs are constant during training.  Pass a new
+tensor (or modify in place) to rebuild.
 """
 import math
 import os
@@ -21,6 +22,7 @@ from torch import nn
 from torch.nn import Parameter as Param
 
 from . import encoder, ops, switches
+from ._cache import DerivedCache, keyable
 from .data import Data, build_data_dict
 from .neg_sampling import typed_negative_sampling
 from .plan import (build_pair_bwd_plan, build_dest_plan, build_row_stream_plan, build_row_stream_plan_s, build_gather_plan, build_gather_plan_segmented, build_rel_plan, build_stream_plan, build_stream_plan_rows, build_csr_plan, group_slots_for,
@@ -73,42 +75,17 @@ __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder
 # ---------------------------------------------------------------------------------------------
 # plan caches
 # ---------------------------------------------------------------------------------------------
-def _ident(*tensors):
-    key = []
-    for t in tensors:
-        if t is None:
-            key.append(None)
-        elif t.is_sparse:                        # no storage pointer: the (pinned) object itself
-            key.append((id(t), tuple(t.shape), str(t.device), t.dtype))
-        else:
-            key.append((t.data_ptr(), tuple(t.shape), t._version, str(t.device), t.dtype))
-    return tuple(key)
+class _PlanCache(DerivedCache):
+    """One slot per layer (graphs are static; a changed tensor identity rebuilds); .value: the plans it handed out last.
+    Never pickled (`DerivedCache`): `torch.save(model, ...)` as in the reference's tip.py:36 works after a forward pass."""
 
-
-class _PlanCache(object):
-    """One slot per layer (graphs are static; a changed tensor identity rebuilds)."""
-
-    def __init__(self):
-        self.key, self.value, self.pins = None, None, None
+    def __init__(self, limit=1):
+        super().__init__(limit)
+        self.value = None
 
     def get(self, key_tensors, builder):
-        key = _ident(*key_tensors)
-        if key != self.key:
-            self.value = builder()
-            self.key, self.pins = key, key_tensors          # keep the tensors alive: pointers stay unique
+        self.value = super().get(key_tensors, None, builder)
         return self.value
-
-    # A cache is derived state (device plans, lazily built through closures): it is never pickled.
-    # `torch.save(model, ...)` as in the reference's tip.py:36, `copy.deepcopy` and multiprocessing
-    # therefore work after a forward pass; the plans are rebuilt on the first call after loading.
-    def __getstate__(self):
-        return {}
-
-    def __setstate__(self, state):
-        self.key, self.value, self.pins = None, None, None
-
-    def __deepcopy__(self, memo):
-        return _PlanCache()
 
 
 def _is_identity_features(x):
@@ -451,20 +428,18 @@ def relation_of_edges(range_list, n_edges, device):
 
 def _shared_pair_bwd_plan(src, dst, rel, n_nodes, n_rel, scale, symmetric, n_wg, lanes, share=None):
     """`build_pair_bwd_plan`; the R-GCN layers of one model run on the same graph and share the plan (it does not depend on the
-    layer's width).  share = (dict owned by the model, (edge_index, range_list) as the caller passed them): the entry keeps
-    those tensors alive, so their identity + version IS the edge list -- no checksums, no device sync, nothing global."""
+    layer's width).  share = (dict owned by the model, (edge_index, range_list) as the caller passed them): the dict holds the
+    layers' one `DerivedCache` (two entries: a training and an evaluation graph), whose entry keeps those tensors alive, so
+    their identity + version IS the edge list -- no checksums, no device sync, nothing global."""
     build = lambda: build_pair_bwd_plan(src, dst, rel, n_nodes, n_rel, scale, symmetric, n_wg, lanes, ops.rel_stream_piece())
     if share is None:
         return build()
-    cache, owners = share
-    key = tuple((id(t), t._version) if torch.is_tensor(t) else None for t in owners) + \
-        (int(n_nodes), int(n_rel), bool(symmetric), int(n_wg), int(lanes))
-    hit = cache.get(key)
-    if hit is None:
-        while len(cache) >= 2:                                # (a training and an evaluation graph)
-            cache.pop(next(iter(cache)))
-        hit = cache[key] = (build(), owners)
-    return hit[0]
+    owned, owners = share
+    cache = owned.get('pair_bwd')
+    if cache is None:
+        cache = owned['pair_bwd'] = DerivedCache(2)
+    return cache.get(tuple(t if torch.is_tensor(t) else None for t in owners),
+                     (int(n_nodes), int(n_rel), bool(symmetric), int(n_wg), int(lanes)), build)
 
 
 def pair_link_words(src, dst, n_nodes):
@@ -1142,24 +1117,21 @@ def screen_queries(num_et, relations=None, drugs=None):
     return q.to(torch.int32)
 
 
-_SCREEN_KEYS = {}
+_SCREEN_KEYS = DerivedCache(8)
 
 
 def _screen_known(d, exclude):
     """(keys, ptr) of the pairs `TIP.screen` drops: the training positives ('train', the sampler's cached keys) or
-    train + test ('all', merged once per pair of edge tensors and cached)."""
+    train + test ('all', merged once per (edge tensor, range list) of both and cached: `_cache.DerivedCache`)."""
     if exclude is None:
         return None
     from .neg_sampling import _cached_keys
     kt, pt = _cached_keys(d.dd_train_idx, d.n_drug, d.dd_train_range)[:2]
     if exclude == 'train':
         return kt, pt
-    ti = d.dd_test_idx
-    ident = (d.dd_train_idx.data_ptr(), d.dd_train_idx._version, ti.data_ptr(), tuple(ti.shape), ti._version,
-             str(ti.device), int(d.n_drug))
-    hit = _SCREEN_KEYS.get(ident)
-    if hit is None:
-        ke, pe = _cached_keys(ti, d.n_drug, d.dd_test_range)[:2]
+
+    def build():
+        ke, pe = _cached_keys(d.dd_test_idx, d.n_drug, d.dd_test_range)[:2]
         n_rel = pt.numel() - 1
         ids = torch.arange(n_rel, device=kt.device)
         rel = torch.cat([torch.repeat_interleave(ids, pt[1:] - pt[:-1]), torch.repeat_interleave(ids, pe[1:] - pe[:-1])])
@@ -1167,31 +1139,27 @@ def _screen_known(d, exclude):
         order = torch.sort(rel * (int(d.n_drug) ** 2) + keys).indices
         ptr = torch.zeros(n_rel + 1, dtype=torch.int64, device=kt.device)
         ptr[1:] = torch.cumsum(torch.bincount(rel, minlength=n_rel), 0)
-        hit = (keys[order].contiguous(), ptr)
-        if len(_SCREEN_KEYS) > 8:
-            _SCREEN_KEYS.clear()
-        _SCREEN_KEYS[ident] = hit
-    return hit
+        return keys[order].contiguous(), ptr
+
+    return _SCREEN_KEYS.get((d.dd_train_idx, keyable(d.dd_train_range), d.dd_test_idx, keyable(d.dd_test_range)),
+                            int(d.n_drug), build)
 
 
-_REKEYED = {}
+_REKEYED = DerivedCache(8)
 
 
 def _rekeyed_known(known, n, n_wide):
     """The relation-major lists `known` (keys u * n + v) as keys u * n_wide + v of a wider node set -- the same pairs in the
-    same order --, cached per key tensor like `_SCREEN_KEYS`; None stays None."""
+    same order --, cached per (keys, ptr) like `_SCREEN_KEYS`; None stays None."""
     if known is None:
         return None
     keys, ptr = known
-    ident = (keys.data_ptr(), keys._version, tuple(keys.shape), str(keys.device), int(n), int(n_wide))
-    hit = _REKEYED.get(ident)
-    if hit is None:
+
+    def build():
         kk = keys.to(torch.int64)
-        hit = ((torch.div(kk, int(n), rounding_mode='floor') * int(n_wide) + kk % int(n)).contiguous(), ptr, keys)
-        if len(_REKEYED) > 8:
-            _REKEYED.clear()
-        _REKEYED[ident] = hit
-    return hit[:2]
+        return (torch.div(kk, int(n), rounding_mode='floor') * int(n_wide) + kk % int(n)).contiguous(), ptr
+
+    return _REKEYED.get((keys, ptr), (int(n), int(n_wide)), build)
 
 
 class NNDecoder(nn.Module):

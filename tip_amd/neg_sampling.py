@@ -19,11 +19,12 @@ Differences, on purpose:
 import torch
 
 from . import ops
+from ._cache import DerivedCache, keyable
 
 _MASK = (1 << 64) - 1
 _state = {'seed': 1111}
 _counters = {}                 # device -> int64 [3] tensor {position, seed, ticket}: the stream's state ON THE DEVICE
-_key_cache = {}
+_key_cache = DerivedCache(8)
 
 
 def manual_seed(seed):
@@ -118,13 +119,10 @@ def sampler_units(rel_ptr, n_wg, build_cost=0.15, fixed_cost=2048):
 
 
 def _cached_keys(pos_edge_index, num_nodes, range_list, range_ident=None):
-    if range_ident is None:
-        range_ident = (range_list.data_ptr(), tuple(range_list.shape)) if torch.is_tensor(range_list) \
-            else tuple(map(tuple, range_list))
-    ident = (pos_edge_index.data_ptr(), tuple(pos_edge_index.shape), pos_edge_index._version,
-             str(pos_edge_index.device), int(num_nodes), range_ident)
-    hit = _key_cache.get(ident)
-    if hit is None:
+    """(keys, rel_ptr, n_rel, (wg_ptr, wg_units), (pos_edge_index, keys32)) of a positive list, built once per (edge tensor,
+    range list) -- a range tensor by identity, a range given as a list by value (`_cache.DerivedCache`).  range_ident: a
+    hashable that stands for a range list the caller derives from the edge tensor itself ('single')."""
+    def build():
         rel_ptr = relation_ptr(range_list, pos_edge_index.shape[1])
         keys = sorted_positive_keys(pos_edge_index, num_nodes, rel_ptr)
         dev = pos_edge_index.device
@@ -133,11 +131,11 @@ def _cached_keys(pos_edge_index, num_nodes, range_list, range_ident=None):
         wg_ptr, wg_units = sampler_units(rel_ptr, n_wg)     # (cost-model constants swept in round 6: 0.15 ... 2.0 -> 52.4 ... 53.6 us)
         # the same keys as 32-bit words (n^2 < 2^31): what the bitmap route sets its bits from -- half the bytes per step
         keys32 = keys.to(torch.int32).contiguous() if int(num_nodes) ** 2 < 2 ** 31 and dev.type == 'cuda' else None
-        hit = (keys, rel_ptr.to(dev), rel_ptr.numel() - 1, (wg_ptr.to(dev), wg_units.to(dev)), (pos_edge_index, keys32))
-        if len(_key_cache) > 8:
-            _key_cache.clear()
-        _key_cache[ident] = hit
-    return hit
+        return keys, rel_ptr.to(dev), rel_ptr.numel() - 1, (wg_ptr.to(dev), wg_units.to(dev)), (pos_edge_index, keys32)
+
+    if range_ident is not None:
+        return _key_cache.get((pos_edge_index,), (int(num_nodes), range_ident), build)
+    return _key_cache.get((pos_edge_index, keyable(range_list)), int(num_nodes), build)
 
 
 def typed_negative_sampling(pos_edge_index, num_nodes, range_list, seed=None, _range_ident=None, pos_offset=None, packed=False):

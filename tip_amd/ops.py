@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib, switches
+from ._cache import DerivedCache, keyable
 from ._lib import SlabSumDesc, GemmDesc, WgGemmDesc, check, lib, ptr, stream_ptr, require_device
 
 def _f32c(t):
@@ -970,22 +971,22 @@ def validate_triples(edge_index, edge_type, n_nodes, n_rel):
         _range_checked(edge_type, n_rel, 'relation')
 
 
-_TASK_CACHE = {}
+_TASK_CACHE = DerivedCache(16)
 TASK_POSITIONS = 2048          # = TASK_MAX in tipk_distmult.hip (a task's ids are staged in LDS)
 
 
 def relation_tasks(edge_type, pos_index=None):
     """int32 [T,4] (relation, begin, end, pos_weight) tasks for the LDS-resident decoder kernels, or
-    None when the triples are not grouped by relation (include/tipk.h section 4).  Built once per tensor.
+    None when the triples are not grouped by relation (include/tipk.h section 4).  Built once per tensor(s)
+    (`_cache.DerivedCache`; None is cached like a task list).
 
     pos_index: the positive triples of the fused objective.  If every relation's block is
     [pairs | the same pairs mirrored] (the data contract of the path, src/utils.py:35-65 -- verified
     here, element by element), the first half gets weight 2 and the mirrored half weight 0."""
-    key = (edge_type.data_ptr(), tuple(edge_type.shape), edge_type._version, str(edge_type.device),
-           None if pos_index is None else (pos_index.data_ptr(), pos_index._version))
-    hit = _TASK_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
+    return _TASK_CACHE.get((edge_type, pos_index), None, lambda: _relation_tasks(edge_type, pos_index))
+
+
+def _relation_tasks(edge_type, pos_index):
     tasks = None
     if edge_type.numel():
         rels, counts = torch.unique_consecutive(edge_type, return_counts=True)
@@ -1019,9 +1020,6 @@ def relation_tasks(edge_type, pos_index=None):
             cost = (end - begin) * (1 + (seg_w[run] > 0).long())
             order = torch.sort(cost, descending=True, stable=True).indices
             tasks = torch.stack([seg_rel[run], begin, end, seg_w[run]], dim=1)[order].to(torch.int32).contiguous()
-    if len(_TASK_CACHE) > 16:
-        _TASK_CACHE.clear()
-    _TASK_CACHE[key] = (tasks, edge_type, pos_index)                         # pin the tensors: pointers stay unique
     return tasks
 
 
@@ -1078,7 +1076,7 @@ def distmult_screen(z, rel_w, queries, k, known=None):
     return out_s, out_u, out_v
 
 
-_PAIR_KNOWN = {}
+_PAIR_KNOWN = DerivedCache(8)
 
 
 def known_relations_by_pair(edge_index, range_list, n_nodes, extra=None):
@@ -1086,32 +1084,31 @@ def known_relations_by_pair(edge_index, range_list, n_nodes, extra=None):
     strictly ascending min(u,v)*n+max(u,v), pair_ptr int64 [n_keys + 1], rel int32 ascending inside a pair's block), built
     with torch ops on edge_index's device (CPU tensors work too).  range_list [R, 2]: relation r owns the edge positions
     [begin, end) (the blocks tile the list in relation order).  Mirrored halves and duplicate edges collapse into one
-    entry.  extra = (edge_index, range_list) of a second list to merge (train + test).  Cached per edge tensor(s)."""
-    def ident(ei):
-        return (ei.data_ptr(), ei._version, tuple(ei.shape), str(ei.device))
-
+    entry.  extra = (edge_index, range_list) of a second list to merge (train + test).  Cached (`_cache.DerivedCache`) per
+    edge tensor(s) and range list(s) -- a range tensor by identity, a range given as a list by value; an edge_index given
+    as a list is not cached."""
     def combined(ei, rl, n_rel):
         ends = torch.as_tensor(rl).to(device=ei.device, dtype=torch.int64).reshape(-1, 2)[:, 1].contiguous()
         rel = torch.bucketize(torch.arange(ei.shape[1], device=ei.device), ends, right=True)
         u, v = ei[0].to(torch.int64), ei[1].to(torch.int64)
         return (torch.minimum(u, v) * int(n_nodes) + torch.maximum(u, v)) * n_rel + rel
 
-    n_rel = int(torch.as_tensor(range_list).reshape(-1, 2).shape[0])
-    tag = (ident(edge_index), int(n_nodes), n_rel, None if extra is None else ident(extra[0]))
-    hit = _PAIR_KNOWN.get(tag)
-    if hit is None:
-        c = combined(edge_index, range_list, n_rel)
+    def build():
+        n_rel = int(torch.as_tensor(range_list).reshape(-1, 2).shape[0])
+        c = combined(torch.as_tensor(edge_index), range_list, n_rel)
         if extra is not None:
-            c = torch.cat([c, combined(extra[0].to(edge_index.device), extra[1], n_rel)])
+            c = torch.cat([c, combined(torch.as_tensor(extra[0]).to(c.device), extra[1], n_rel)])
         c = torch.unique(c)                                              # sorted by (key, relation), duplicates gone
         keys, counts = torch.unique_consecutive(torch.div(c, n_rel, rounding_mode='floor'), return_counts=True)
         ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=c.device)
         ptr[1:] = torch.cumsum(counts, 0)
-        hit = (keys.contiguous(), ptr, (c % n_rel).to(torch.int32).contiguous())
-        if len(_PAIR_KNOWN) > 8:
-            _PAIR_KNOWN.clear()
-        _PAIR_KNOWN[tag] = hit
-    return hit
+        return keys.contiguous(), ptr, (c % n_rel).to(torch.int32).contiguous()
+
+    more_ei, more_rl = (None, None) if extra is None else extra
+    if not torch.is_tensor(edge_index) or not (extra is None or torch.is_tensor(more_ei)):
+        return build()
+    return _PAIR_KNOWN.get((edge_index, keyable(range_list), more_ei, None if extra is None else keyable(more_rl)),
+                           int(n_nodes), build)
 
 
 def _known_lists(known):
@@ -1387,21 +1384,20 @@ def pair_table_partner_rank(s1t, s2t, q_rel, q_drug, tgt_ptr, tgt_node, known=No
     return out_rank, out_logit
 
 
-_SYMMETRIC_KNOWN = {}
+_SYMMETRIC_KNOWN = DerivedCache(8)
 
 
 def symmetric_known(known, n_nodes):
     """Relation-major known lists (keys int64 u*n+v sorted inside each relation, ptr int64 [n_rel + 1]) that hold BOTH
     directions of every pair: each key is mirrored to v*n+u, the keys are sorted inside each relation and duplicates dropped
     (a self key u*n+u is its own mirror).  Lists that are already symmetric come back UNCHANGED (the same tuple); None stays
-    None.  Torch ops on the lists' device (CPU tensors work too); cached per list tensors, like the screen's merged keys."""
+    None.  Torch ops on the lists' device (CPU tensors work too); cached per list tensors (`_cache.DerivedCache`)."""
     if known is None:
         return None
     keys, kptr = known
     n = int(n_nodes)
-    tag = (keys.data_ptr(), keys._version, tuple(keys.shape), kptr.data_ptr(), kptr._version, str(keys.device), n)
-    hit = _SYMMETRIC_KNOWN.get(tag)
-    if hit is None:
+
+    def build():                                                        # None: already symmetric
         k64, p64 = keys.to(torch.int64), kptr.to(torch.int64)
         n_rel = p64.numel() - 1
         rel = torch.repeat_interleave(torch.arange(n_rel, device=keys.device), p64[1:] - p64[:-1])
@@ -1409,15 +1405,13 @@ def symmetric_known(known, n_nodes):
         mirror = rel * (n * n) + (k64 % n) * n + torch.div(k64, n, rounding_mode='floor')
         both = torch.unique(torch.cat([comb, mirror]))                  # sorted by (relation, key), duplicates gone
         if both.numel() == comb.numel() and torch.equal(both, comb):
-            hit = known
-        else:
-            ptr = torch.zeros(n_rel + 1, dtype=torch.int64, device=keys.device)
-            ptr[1:] = torch.cumsum(torch.bincount(torch.div(both, n * n, rounding_mode='floor'), minlength=n_rel), 0)
-            hit = ((both % (n * n)).contiguous(), ptr)
-        if len(_SYMMETRIC_KNOWN) > 8:
-            _SYMMETRIC_KNOWN.clear()
-        _SYMMETRIC_KNOWN[tag] = hit = (hit, known)                       # (the input is pinned: its address stays its own)
-    return hit[0]
+            return None
+        ptr = torch.zeros(n_rel + 1, dtype=torch.int64, device=keys.device)
+        ptr[1:] = torch.cumsum(torch.bincount(torch.div(both, n * n, rounding_mode='floor'), minlength=n_rel), 0)
+        return (both % (n * n)).contiguous(), ptr
+
+    both = _SYMMETRIC_KNOWN.get((keys, kptr), n, build)
+    return known if both is None else both
 
 
 def _partner_sum_lists(q_drug, k, rel_ids, partner_w, known, n, n_rel, dev):
@@ -2017,8 +2011,8 @@ def pair_table_combo_burden(s1, s2, plan, k, aggregate='noisy_or', weights=None,
                       plan, k, aggregate, weights, known, n_rel, dev, 'tipk_pair_table_combo_burden')
 
 
-_IN_EDGES = {}
-_PAIR_EDGES = {}
+_IN_EDGES = DerivedCache(8)
+_PAIR_EDGES = DerivedCache(8)
 
 
 def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
@@ -2028,7 +2022,8 @@ def in_edges_by_node(edge_index, range_list_or_type, n_nodes):
     range_list_or_type: range_list [R, 2] (relation r owns the edge positions [begin, end), the blocks tile the list in
     relation order) or edge_type int [E].  Built with torch ops on edge_index's device (CPU tensors work too): one stable
     sort of the key (dst * R + rel) * n + src.  IndexError for a node id outside [0, n_nodes) or a negative relation.
-    Cached per edge tensor(s)."""
+    Cached per (edge tensor, range or type tensor) by identity and version, the tensors pinned while cached
+    (`_cache.DerivedCache`); arguments given as lists are not cached."""
     return _in_edges(edge_index, range_list_or_type, n_nodes, False, _IN_EDGES, 'in_edges_by_node')
 
 
@@ -2036,24 +2031,24 @@ def in_edges_by_pair(edge_index, range_list_or_type, n_nodes):
     """The in-edge CSR of include/tipk.h section 4o: as `in_edges_by_node`, but node v's positions are sorted by (SOURCE,
     relation), so the edges of one pair (source -> v) are adjacent -- in the order they have in `in_edges_by_node`'s
     (relation, source) segment.  -> (pe_ptr int64 [n_nodes + 1], pe_src int32 [E], pe_rel int32 [E]).  Same arguments, same
-    errors; cached per edge tensor(s), next to `in_edges_by_node`'s."""
+    errors, same caching rule (a cache of its own next to `in_edges_by_node`'s)."""
     return _in_edges(edge_index, range_list_or_type, n_nodes, True, _PAIR_EDGES, 'in_edges_by_pair')
 
 
 def _in_edges(edge_index, range_list_or_type, n_nodes, by_pair, cache, who):
-    """`in_edges_by_node` (by_pair False) / `in_edges_by_pair` (True): one stable sort of the edges' key."""
-    def ident(t):
-        return (t.data_ptr(), t._version, tuple(t.shape), str(t.device)) if torch.is_tensor(t) else None
+    """`in_edges_by_node` (by_pair False) / `in_edges_by_pair` (True): one stable sort of the edges' key.  Arguments given as
+    lists are not cached (a temporary tensor's address names nothing)."""
+    build = lambda: _in_edges_built(torch.as_tensor(edge_index), range_list_or_type, int(n_nodes), by_pair, who)
+    if not (torch.is_tensor(edge_index) and torch.is_tensor(range_list_or_type)):
+        return build()
+    return cache.get((edge_index, range_list_or_type), int(n_nodes), build)
 
-    edge_index = torch.as_tensor(edge_index)
+
+def _in_edges_built(edge_index, range_list_or_type, n, by_pair, who):
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype.is_floating_point:
         raise _lib.TipkError(who + ': an int tensor edge_index [2, E] expected, got %s %s'
                              % (edge_index.dtype, tuple(edge_index.shape)))
-    n, n_edges, dev = int(n_nodes), edge_index.shape[1], edge_index.device
-    tag = (ident(edge_index), ident(range_list_or_type), n)
-    hit = cache.get(tag) if tag[1] is not None else None
-    if hit is not None:
-        return hit
+    n_edges, dev = edge_index.shape[1], edge_index.device
     rt = torch.as_tensor(range_list_or_type)
     if rt.dtype.is_floating_point:
         raise _lib.TipkError(who + ': an int range_list [R, 2] or edge_type [E] expected, got %s' % rt.dtype)
@@ -2079,12 +2074,7 @@ def _in_edges(edge_index, range_list_or_type, n_nodes, by_pair, cache, who):
     order = torch.sort((dst * n + src) * n_rel + rel if by_pair else (dst * n_rel + rel) * n + src, stable=True)[1]
     in_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     in_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
-    hit = (in_ptr, src[order].to(torch.int32).contiguous(), rel[order].to(torch.int32).contiguous())
-    if tag[1] is not None:
-        if len(cache) > 8:
-            cache.clear()
-        cache[tag] = hit
-    return hit
+    return in_ptr, src[order].to(torch.int32).contiguous(), rel[order].to(torch.int32).contiguous()
 
 
 def rgcn_edge_attribution(h, basis, att, root, in_edges, q_node, probe, k):
@@ -2136,7 +2126,7 @@ def rgcn_edge_attribution(h, basis, att, root, in_edges, q_node, probe, k):
     return contrib, src, rel, own, total
 
 
-_PROT_EDGES = {}
+_PROT_EDGES = DerivedCache(8)
 
 
 def targets_by_protein(dp_edge_index, n_prot, n_nodes):
@@ -2144,16 +2134,18 @@ def targets_by_protein(dp_edge_index, n_prot, n_nodes):
     row 1 n_prot + the drug id, as the data set stores it) -> (prot_ptr int64 [n_prot + 1], prot_drug int32 [E], inv_cnt
     float32 [n_nodes], cnt int64 [n_nodes]): protein t owns the positions prot_ptr[t] .. prot_ptr[t+1], drugs ascending,
     duplicates kept; cnt = the number of P -> D edges into every drug and inv_cnt = 1 / max(cnt, 1), correctly rounded.
-    Built with torch ops on the tensor's device; IndexError for an id out of range.  Cached per edge tensor."""
-    ei = torch.as_tensor(dp_edge_index)
+    Built with torch ops on the tensor's device; IndexError for an id out of range.  Cached per edge tensor
+    (`_cache.DerivedCache`); an edge list given as a Python list is not cached."""
+    build = lambda: _targets_by_protein(torch.as_tensor(dp_edge_index), int(n_prot), int(n_nodes))
+    if not torch.is_tensor(dp_edge_index):
+        return build()
+    return _PROT_EDGES.get((dp_edge_index,), (int(n_prot), int(n_nodes)), build)
+
+
+def _targets_by_protein(ei, n_prot, n):
     if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype.is_floating_point:
         raise _lib.TipkError('targets_by_protein: an int tensor dp_edge_index [2, E] expected, got %s %s'
                              % (ei.dtype, tuple(ei.shape)))
-    n_prot, n = int(n_prot), int(n_nodes)
-    tag = (ei.data_ptr(), ei._version, tuple(ei.shape), str(ei.device), n_prot, n)
-    hit = _PROT_EDGES.get(tag)
-    if hit is not None:
-        return hit
     prot, drug = ei[0].to(torch.int64), ei[1].to(torch.int64) - n_prot
     if ei.shape[1]:
         plo, phi, dlo, dhi = torch.stack([prot.min(), prot.max(), drug.min(), drug.max()]).tolist()
@@ -2166,11 +2158,7 @@ def targets_by_protein(dp_edge_index, n_prot, n_nodes):
     prot_ptr[1:] = torch.cumsum(torch.bincount(prot, minlength=n_prot), 0)
     cnt = torch.bincount(drug, minlength=n)
     inv_cnt = 1.0 / cnt.clamp(min=1).to(torch.float32)
-    hit = (prot_ptr, drug[order].to(torch.int32).contiguous(), inv_cnt.contiguous(), cnt)
-    if len(_PROT_EDGES) > 8:
-        _PROT_EDGES.clear()
-    _PROT_EDGES[tag] = hit
-    return hit
+    return prot_ptr, drug[order].to(torch.int32).contiguous(), inv_cnt.contiguous(), cnt
 
 
 def protein_attribution_supported(n_nodes, n_prot, n_rel, n_bases, ne, pd, p, d1, d2, cat, k):
