@@ -177,6 +177,14 @@ int tipk_gather_sum_lin(const float* table, int64_t ld_table, int64_t n_table, c
                         const float* w, int64_t w_so, int64_t w_si, const float* bias2 /* nullable */, int relu2,
                         float* out2, int64_t ld_out2, int d, int d2, int group_slots, tipk_stream_t stream);
 
+/* Host query, launches nothing: how many workgroups of the GROUPED gather kernel a plan of width d (d % 4 == 0, table below
+ * 4 GB) takes are resident on one CU (hipOccupancyMaxActiveBlocksPerMultiprocessor of that kernel instance with the launch's
+ * own block size and dynamic LDS).  `map`: 0 = tipk_gather_sum / tipk_gather_sum_riders without colsum, -1 = tipk_gather_sum_riders
+ * with colsum, d2 > 0 = tipk_gather_sum_lin with d2 outputs (`tipk_gather_sum_lin_supported`).  The 1024-thread workgroups of
+ * the encoder step (d = 16, 32) are built to be resident twice: tip_amd/plan.py sizes their plans for 32 waves per CU.
+ * TIPK_EUNSUPPORTED for a (d, group_slots, map) no grouped launch takes. */
+int tipk_gather_sum_occupancy(int d, int group_slots, int weighted, int map, int* workgroups_per_cu);
+
 /* --------------------------------------------------------------------------------------------
  * 1c. CSR rows -- the TRANSPOSED D-D pass of a large graph (autograd backward of K5/K6,
  *     src/layers.py:159-180): out[r] = sum_{e in [row_ptr[r], row_ptr[r+1])} table[row_id[e]] for every one
@@ -580,6 +588,9 @@ int tipk_sum_slabs_xb(const float* slabs, int64_t n_slabs, int64_t slab_stride, 
                       const float* row_scale /* nullable */, const float* addend /* nullable */, int relu, float* x,
                       const float* basis, const float* root, int n_bases, int d_out, float* xb, float* xroot,
                       tipk_stream_t stream);
+/* host query, launches nothing: 1024-thread workgroups of the kernel behind tipk_sum_slabs_xb resident on one CU for this
+ * d_out (hipOccupancyMaxActiveBlocksPerMultiprocessor; built to be 2, so that a step's workgroups run in one round) */
+int tipk_sum_slabs_xb_occupancy(int d_out, int* workgroups_per_cu);
 
 /* --------------------------------------------------------------------------------------------
  * 2h. LARGE node sets, both passes: the (relation, node) row sums are assembled in LDS and multiplied there -- neither

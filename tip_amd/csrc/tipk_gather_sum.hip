@@ -172,13 +172,39 @@ struct Acc<1> {
     __device__ __forceinline__ void store(float* p) const { *p = v; }
 };
 
+// Lane `J` of every L-lane slot, handed to all lanes of the slot.  L <= 32 with a constant J: ds_swizzle in bit-mask mode (lane =
+// (own lane & ~(L - 1)) | J inside each half wave) -- the pattern is an immediate, so the eight picks of a batch hold no address
+// register (eight of the 72 VGPRs that kept a 1024-thread workgroup alone on its CU); otherwise ds_bpermute.
+template <int L, int J>
+__device__ __forceinline__ int slot_pick(int v) {
+    if constexpr (L <= 32) return __builtin_amdgcn_ds_swizzle(v, ((~(L - 1)) & 31) | (J << 5));
+    else return __shfl(v, J, L);
+}
+// edge J of a step sits in register J / L of lane J % L (IPL == 1: register 0 of lane J): dst[J .. U) <- those, for the slot
+template <int L, int U, int J = 0, typename T, int IPL>
+__device__ __forceinline__ void slot_pick_all(const T (&src)[IPL], T (&dst)[U]) {
+    if constexpr (J < U) {
+        if constexpr (sizeof(T) == 4 && __is_same(T, float)) dst[J] = __int_as_float(slot_pick<L, J % L>(__float_as_int(src[J / L])));
+        else dst[J] = slot_pick<L, J % L>(src[J / L]);
+        slot_pick_all<L, U, J + 1>(src, dst);
+    }
+}
+
+// A 1024-thread workgroup is 4 waves per SIMD: two of them share a CU only at 8 waves per SIMD, i.e. at most 64 VGPRs.  The
+// instances below are asked for that budget and meet it without scratch (tools/kernel_resources.sh); the others (weighted
+// 16-byte rows on the 64-bit address path, or of a width the encoder step does not take) would spill and keep the default.
+constexpr bool two_per_cu(int V, int L, bool has_w, bool grouped, bool small) {
+    return grouped && (V == 1 || !has_w || (small && (L == 4 || L == 8)));
+}
+
 // GROUPED: the workgroup is exactly one block of G = blockDim / L items of a `group_slots` plan.
 // SMALL: the table is < 4 GB: a gathered row's address is the (scalar) table base + a 32-bit byte offset =
 // ONE 24-bit or 32-bit multiply per row; the general path pays a 64-bit multiply-add (three quarter-rate
 // v_mul_lo_u32 / v_mad_u64_u32 and two adds) per row, which made the narrow-row launches (P-P graph: 32- and
 // 16-float rows, 8 rows per wave-instruction) issue-bound rather than L2-bound.
 template <int V, int L, bool HAS_W, bool GROUPED, bool SMALL, int LIN = 0>   // LIN = outputs per lane of the fused linear map (0: none)
-__global__ __launch_bounds__(GROUPED ? 1024 : 256) void gather_sum_kernel(
+__global__ __launch_bounds__(GROUPED ? 1024 : 256) __attribute__((amdgpu_waves_per_eu(two_per_cu(V, L, HAS_W, GROUPED, SMALL) ? 8 : GROUPED ? 4 : 1)))
+void gather_sum_kernel(
     const float* __restrict__ table, int64_t ld_table, const int32_t* __restrict__ row_id,
     const float* __restrict__ edge_w, const int4* __restrict__ items, int64_t n_items,
     float* __restrict__ out, int64_t ld_out, float* __restrict__ partial, Epilogue ep, int d, Riders rd) {
@@ -206,7 +232,7 @@ __global__ __launch_bounds__(GROUPED ? 1024 : 256) void gather_sum_kernel(
     const int col = sub * V;
     const bool col_ok = col < d;
     const unsigned ldb = (unsigned)ld_table * 4u;          // SMALL: row stride in bytes (table bytes < 2^32)
-    const float* table_c = table + (col_ok ? col : 0);
+    const unsigned col_b = (unsigned)(col_ok ? col : 0) * 4u;   // ... and the lane's first column inside a row, in bytes
 
     Acc<V> acc;
     acc.zero();
@@ -256,29 +282,36 @@ __global__ __launch_bounds__(GROUPED ? 1024 : 256) void gather_sum_kernel(
         }
 #pragma unroll 1                          // one batch of U rows in flight: unrolling L/U batches cost 167 VGPRs at L = 32
         for (int j0 = 0; j0 < STEP; j0 += U) {
+            // ids first, rows next, weights last: the weights are not needed before the rows are back, and fetched behind the
+            // loads they share no live range with the row offsets
             int ids[U];
             float ws[U];
+            if constexpr (STEP == U) {                     // L <= 8: every pick is a constant lane of the slot
+                slot_pick_all<L, U>(id, ids);
+            } else {
 #pragma unroll
-            for (int j = 0; j < U; ++j) {
-                if (IPL == 1) {
-                    ids[j] = __shfl(id[0], j0 + j, L);
-                    if (HAS_W) ws[j] = __shfl(wgt[0], j0 + j, L);
-                } else {                                   // STEP == U: edge j of the step sits in register j / L of lane j % L
-                    ids[j] = __shfl(id[j / L], j % L, L);
-                    if (HAS_W) ws[j] = __shfl(wgt[j / L], j % L, L);
-                }
+                for (int j = 0; j < U; ++j) ids[j] = __shfl(id[0], j0 + j, L);
             }
             // all row loads of the batch are issued before the first use: a load whose result is
             // consumed inside its own exec-masked branch is waited for on the spot (U dependent memory
             // round trips per batch).  Lanes without an edge skip the load (short rows -- the backward
-            // plans average 2.5 edges per row -- must not pay for 8).
+            // plans average 2.5 edges per row -- must not pay for 8).  SMALL: the address is the scalar table base + ONE
+            // 32-bit byte offset per row with the lane's column offset folded in (no 64-bit pair per row).
             Acc<V> rows[U];
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 rows[j].zero();
                 if (ids[j] >= 0 && col_ok) {
-                    if (SMALL) rows[j].load_off(table_c, (unsigned)ids[j] * ldb);
+                    if (SMALL) rows[j].load_off(table, (unsigned)ids[j] * ldb + col_b);
                     else rows[j].load(table + col + (int64_t)ids[j] * ld_table);
+                }
+            }
+            if constexpr (HAS_W) {
+                if constexpr (STEP == U) {
+                    slot_pick_all<L, U>(wgt, ws);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < U; ++j) ws[j] = __shfl(wgt[0], j0 + j, L);
                 }
             }
 #pragma unroll
@@ -599,6 +632,66 @@ extern "C" int tipk_gather_sum_lin(const float* table, int64_t ld_table, int64_t
     if (L == 8) TIPK_GL(8, 2);
     TIPK_GL(16, 1);
 #undef TIPK_GL
+}
+
+namespace {
+
+template <int L, bool W, int LIN>
+int grouped_occupancy(int threads, size_t lds, int* out) {
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &n, reinterpret_cast<const void*>(&gather_sum_kernel<4, L, W, true, true, LIN>), threads, lds);
+    if (e != hipSuccess) return tipk_hip_status(e);
+    *out = n;
+    return TIPK_OK;
+}
+
+}  // namespace
+
+// the kernel instance and the dynamic LDS are those launch_gather / launch_gather_lin choose for the same arguments
+extern "C" int tipk_gather_sum_occupancy(int d, int group_slots, int weighted, int map, int* workgroups_per_cu) {
+    if (!workgroups_per_cu) return TIPK_EINVAL;
+    if (d <= 0 || d % 4 != 0 || d > 256 || group_slots <= 0 || map < -1) return TIPK_EUNSUPPORTED;
+    const int L = pow2_at_least(d / 4), threads = group_slots * L;
+    if (threads > 1024 || threads % TIPK_WAVE != 0) return TIPK_EUNSUPPORTED;
+    size_t lds = (size_t)threads * sizeof(Acc<4>);
+    const bool w = weighted != 0;
+#define TIPK_OCC(LL, LIN) return w ? grouped_occupancy<LL, true, LIN>(threads, lds, workgroups_per_cu) \
+                                   : grouped_occupancy<LL, false, LIN>(threads, lds, workgroups_per_cu)
+    if (map > 0) {
+        if (!tipk_gather_sum_lin_supported(d, map, group_slots)) return TIPK_EUNSUPPORTED;
+        const int per = map / L;
+        lds += (size_t)d * (L * per + 4) * sizeof(float);
+        if (L == 4 && per == 1) TIPK_OCC(4, 1);
+        if (L == 4 && per == 2) TIPK_OCC(4, 2);
+        if (L == 4) TIPK_OCC(4, 4);
+        if (L == 8 && per == 1) TIPK_OCC(8, 1);
+        if (L == 8) TIPK_OCC(8, 2);
+        TIPK_OCC(16, 1);
+    }
+    if (threads == 1024 && lds < SLAB_RED_FLOATS * sizeof(float)) lds = SLAB_RED_FLOATS * sizeof(float);   // (what a launch with riders asks for)
+    if (map == -1) {
+        if (threads != 1024) return TIPK_EUNSUPPORTED;
+        switch (L) {
+            case 1: TIPK_OCC(1, -1);
+            case 2: TIPK_OCC(2, -1);
+            case 4: TIPK_OCC(4, -1);
+            case 8: TIPK_OCC(8, -1);
+            case 16: TIPK_OCC(16, -1);
+            case 32: TIPK_OCC(32, -1);
+            default: TIPK_OCC(64, -1);
+        }
+    }
+    switch (L) {
+        case 1: TIPK_OCC(1, 0);
+        case 2: TIPK_OCC(2, 0);
+        case 4: TIPK_OCC(4, 0);
+        case 8: TIPK_OCC(8, 0);
+        case 16: TIPK_OCC(16, 0);
+        case 32: TIPK_OCC(32, 0);
+        default: TIPK_OCC(64, 0);
+    }
+#undef TIPK_OCC
 }
 
 extern "C" int tipk_gather_sum_finalize(const float* partial, const int32_t* rows, int64_t n_rows, float* out,

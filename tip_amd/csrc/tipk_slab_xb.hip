@@ -22,13 +22,64 @@ struct SxArgs {
     float* xroot;                                                          // [n_rows][d_out]
 };
 
-__global__ __launch_bounds__(1024) void sum_slabs_xb_kernel(SxArgs a) {
+// One half (16 of K = 32) of an output column's weights: w[(16 h + k) d_out], k = 0 .. 15.
+template <int DOUT>
+__device__ __forceinline__ void load_w_half(const float* w, int h, int d_out, float (&wv)[16]) {
+    if constexpr (DOUT == 0) {                         // a run-time stride: ONE offset register walks the rows, not 16 address pairs
+        unsigned off = (unsigned)(16 * h * d_out);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            wv[k] = w[off];
+            off += (unsigned)d_out;
+            asm volatile("" : "+v"(off));
+        }
+    } else {                                           // the column's one address pair + an immediate offset
+#pragma unroll
+        for (int k = 0; k < 16; ++k) wv[k] = w[(16 * h + k) * DOUT];
+    }
+}
+
+// ... and its share of the two rows' fma chains, k ascending.  In quarters an empty asm keeps apart: left to itself the compiler reads
+// all 64 x1 values back from LDS ahead of the first fma, which with the weights does not fit 64 registers.
+__device__ __forceinline__ void fma_w_half(const float* xs, int h, const float (&wv)[16], float& acc0, float& acc1) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        asm volatile("" : "+v"(acc0), "+v"(acc1) : : "memory");
+#pragma unroll
+        for (int k = 4 * q; k < 4 * q + 4; ++k) { acc0 = fmaf(xs[16 * h + k], wv[k], acc0); acc1 = fmaf(xs[32 + 16 * h + k], wv[k], acc1); }
+    }
+}
+
+// DOUT: d_out as a constant (16 | 32), 0: read from the arguments.  At most 64 VGPRs either way, so that two of these 1024-thread
+// workgroups share a CU and all of BioSNAP's 323 are resident at once: holding a column's 32 weights behind 32 address pairs took
+// 107.  The weights come as two halves of 16 -- the same k order and the same two fma chains: the first half of the thread's
+// first column is requested before the slabs (it depends on no sum), the second right behind the barrier, in front of the first
+// half's fmas.
+template <int DOUT>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void sum_slabs_xb_kernel(SxArgs a) {
     __shared__ float red[1024];
     __shared__ float xs[64];
     constexpr int lanes = 16, epb = 64;                                    // slab lanes per element, elements per workgroup
     const int t = threadIdx.x, e = t % epb, j = t / epb;
     const int64_t count = (int64_t)a.n_rows * 32;
     const int64_t i = (int64_t)blockIdx.x * epb + e;
+    // thread = output column n of [XB (n_bases x d_out) | x root (d_out)]
+    const int d_out = DOUT > 0 ? DOUT : a.d_out;
+    const int n_xb = a.n_bases * d_out, n_cols = n_xb + d_out;
+    const auto column = [&](int n, bool& is_root, int& b, int& c) {
+        is_root = n >= n_xb;
+        b = is_root ? 0 : n / d_out;
+        c = is_root ? n - n_xb : n - b * d_out;
+        return is_root ? a.root + c : a.basis + (int64_t)b * 32 * d_out + c;
+    };
+    bool is_root = false;
+    int b = 0, c = 0;
+    const float* w = nullptr;
+    float wa[16], wb[16];
+    if (t < n_cols) {
+        w = column(t, is_root, b, c);
+        load_w_half<DOUT>(w, 0, d_out, wa);
+    }
     float s = 0.f;
     if (i < count) {
         const float* p = a.in + i;                                         // four loads in flight, original order of additions
@@ -55,22 +106,20 @@ __global__ __launch_bounds__(1024) void sum_slabs_xb_kernel(SxArgs a) {
         xs[e] = v;
     }
     __syncthreads();
-    // the two rows' products: thread = output column n of [XB (n_bases x d_out) | x root (d_out)], K = 32 in index order
+    // the two rows' products, K = 32 in index order
     const int row0 = (int)blockIdx.x * 2;
-    const int n_xb = a.n_bases * a.d_out, n_cols = n_xb + a.d_out;
     for (int n = t; n < n_cols; n += 1024) {
-        const bool is_root = n >= n_xb;
-        const int b = is_root ? 0 : n / a.d_out, c = is_root ? n - n_xb : n - b * a.d_out;
-        const float* w = is_root ? a.root + c : a.basis + (int64_t)b * 32 * a.d_out + c;
-        float wv[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) wv[k] = w[k * a.d_out];
+        if (n != t) {
+            w = column(n, is_root, b, c);
+            load_w_half<DOUT>(w, 0, d_out, wa);
+        }
+        load_w_half<DOUT>(w, 1, d_out, wb);
         float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) { acc0 = fmaf(xs[k], wv[k], acc0); acc1 = fmaf(xs[32 + k], wv[k], acc1); }
+        fma_w_half(xs, 0, wa, acc0, acc1);
+        fma_w_half(xs, 1, wb, acc0, acc1);
         if (is_root) {
-            a.xroot[(int64_t)row0 * a.d_out + c] = acc0;
-            if (row0 + 1 < a.n_rows) a.xroot[(int64_t)(row0 + 1) * a.d_out + c] = acc1;
+            a.xroot[(int64_t)row0 * d_out + c] = acc0;
+            if (row0 + 1 < a.n_rows) a.xroot[(int64_t)(row0 + 1) * d_out + c] = acc1;
         } else {
             a.xb[((int64_t)row0 * a.n_bases + b) * 32 + c] = acc0;
             if (row0 + 1 < a.n_rows) a.xb[((int64_t)(row0 + 1) * a.n_bases + b) * 32 + c] = acc1;
@@ -92,6 +141,21 @@ extern "C" int tipk_sum_slabs_xb(const float* slabs, int64_t n_slabs, int64_t sl
     a.in = slabs; a.n_slabs = n_slabs; a.slab_stride = slab_stride; a.n_rows = (int)n_rows;
     a.row_scale = row_scale; a.addend = addend; a.relu = relu; a.x = x;
     a.basis = basis; a.root = root; a.n_bases = n_bases; a.d_out = d_out; a.xb = xb; a.xroot = xroot;
-    hipLaunchKernelGGL(sum_slabs_xb_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, a);
+    if (d_out == 16) hipLaunchKernelGGL(sum_slabs_xb_kernel<16>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, a);
+    else if (d_out == 32) hipLaunchKernelGGL(sum_slabs_xb_kernel<32>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(sum_slabs_xb_kernel<0>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, a);
     TIPK_RETURN_LAUNCH();
+}
+
+extern "C" int tipk_sum_slabs_xb_occupancy(int d_out, int* workgroups_per_cu) {
+    if (!workgroups_per_cu) return TIPK_EINVAL;
+    if (d_out < 1 || d_out > 32) return TIPK_EUNSUPPORTED;
+    const void* f = d_out == 16 ? reinterpret_cast<const void*>(&sum_slabs_xb_kernel<16>)
+                  : d_out == 32 ? reinterpret_cast<const void*>(&sum_slabs_xb_kernel<32>)
+                                : reinterpret_cast<const void*>(&sum_slabs_xb_kernel<0>);
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 1024, 0);
+    if (e != hipSuccess) return tipk_hip_status(e);
+    *workgroups_per_cu = n;
+    return TIPK_OK;
 }

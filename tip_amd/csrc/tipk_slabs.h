@@ -77,10 +77,17 @@ __device__ __forceinline__ void slab_sum_body(const SlabArgs& a, int block, floa
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         int64_t k = 0;
+        // a slab's address = a workgroup-uniform (scalar) base + the thread's 16-byte slot as ONE 32-bit register, re-read every
+        // trip through an empty asm so that it is not folded back into eight 64-bit induction pointers: those 16 VGPRs put every
+        // host of this body over the 64 registers at which two 1024-thread workgroups share a CU
+        const char* p0 = reinterpret_cast<const char*>(in + (int64_t)(block - first) * 4096);
+        const int64_t stb = a.slab_stride * 4;
+        unsigned toff = threadIdx.x * 16u;
         for (; k + 8 <= a.n_slabs; k += 8) {
             float4 v[8];
+            asm volatile("" : "+v"(toff));
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(k + u) * st4];
+            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(p0 + (k + u) * stb + toff);
 #pragma unroll
             for (int u = 0; u < 8; ++u) { s[u & 3].x += v[u].x; s[u & 3].y += v[u].y; s[u & 3].z += v[u].z; s[u & 3].w += v[u].w; }
         }
@@ -97,11 +104,15 @@ __device__ __forceinline__ void slab_sum_body(const SlabArgs& a, int block, floa
         }
         float r[4] = {((s[0].x + s[1].x) + s[2].x) + s[3].x, ((s[0].y + s[1].y) + s[2].y) + s[3].y,
                       ((s[0].z + s[1].z) + s[2].z) + s[3].z, ((s[0].w + s[1].w) + s[2].w) + s[3].w};
-        const float rs = a.row_scale ? a.row_scale[i / a.cols] : 1.f;              // cols % 4 == 0: one row per thread
+        // the epilogue starts from the four finished sums: its element index passes through the same empty asm as they do, so the
+        // 64-bit division and the addend / gate loads below cannot be moved up over the 48 registers of the last slab batch
+        int64_t ie = i;
+        asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(ie));
+        const float rs = a.row_scale ? a.row_scale[ie / a.cols] : 1.f;             // cols % 4 == 0: one row per thread
         float4 ad = make_float4(0.f, 0.f, 0.f, 0.f), ac = ad, gt = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (a.addend) ad = *reinterpret_cast<const float4*>(a.addend + i);
-        if (a.accumulate) ac = *reinterpret_cast<const float4*>(a.out + i);
-        if (a.gate) gt = *reinterpret_cast<const float4*>(a.gate + i);
+        if (a.addend) ad = *reinterpret_cast<const float4*>(a.addend + ie);
+        if (a.accumulate) ac = *reinterpret_cast<const float4*>(a.out + ie);
+        if (a.gate) gt = *reinterpret_cast<const float4*>(a.gate + ie);
         const float adv[4] = {ad.x, ad.y, ad.z, ad.w}, acv[4] = {ac.x, ac.y, ac.z, ac.w}, gtv[4] = {gt.x, gt.y, gt.z, gt.w};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -113,7 +124,7 @@ __device__ __forceinline__ void slab_sum_body(const SlabArgs& a, int block, floa
             if (a.gate && !(gtv[c] > 0.f)) t = 0.f;
             r[c] = t;
         }
-        *reinterpret_cast<float4*>(a.out + i) = make_float4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<float4*>(a.out + ie) = make_float4(r[0], r[1], r[2], r[3]);
         return;
     }
     const int lanes = a.lanes, epb = 1024 / lanes;

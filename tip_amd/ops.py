@@ -127,6 +127,24 @@ def gather_sum_lin_supported(d, d2, group_slots):
     return bool(lib().tipk_gather_sum_lin_supported(int(d), int(d2), int(group_slots)))
 
 
+def gather_sum_occupancy(d, group_slots, weighted=False, map=0):
+    """Workgroups of the grouped gather kernel resident on one CU for rows of width d (`tipk_gather_sum_occupancy`; launches
+    nothing).  map: 0 plain / riders, -1 gate + column sums, d2 > 0 the fused linear map with d2 outputs."""
+    import ctypes as C
+    n = C.c_int(0)
+    check(lib().tipk_gather_sum_occupancy(int(d), int(group_slots), int(bool(weighted)), int(map), C.byref(n)),
+          'tipk_gather_sum_occupancy')
+    return n.value
+
+
+def sum_slabs_xb_occupancy(d_out):
+    """Workgroups of the hand-over kernel (`sum_slabs_xb`) resident on one CU (`tipk_sum_slabs_xb_occupancy`; launches nothing)."""
+    import ctypes as C
+    n = C.c_int(0)
+    check(lib().tipk_sum_slabs_xb_occupancy(int(d_out), C.byref(n)), 'tipk_sum_slabs_xb_occupancy')
+    return n.value
+
+
 def gather_sum_lin(plan, table, weight, bias=None, relu=False, row_scale=None):
     """(agg, out2): agg = the plan's row sums over `table` [n_table, d] (x row_scale), out2 = relu?(agg @ weight^T + bias) for
     weight [d2, d] (any strides), in ONE launch on a grouped plan (include/tipk.h `tipk_gather_sum_lin`)."""

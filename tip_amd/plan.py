@@ -23,7 +23,9 @@ of `items` / `split_rows` is the contract of include/tipk.h section 1.
 import torch
 
 DEFAULT_CHUNK = None          # None = `auto_chunk` (edges per work item chosen from the edge count)
-TARGET_ITEMS = 65536          # ~ 256 CUs x 32 waves x 8 slots: one item per slot fills the chip
+TARGET_ITEMS = 65536          # ~ 256 CUs x 32 waves x 8 slots: one item per slot fills the chip.  32 waves per CU = TWO of the
+                              # grouped gather's 1024-thread workgroups: its d = 16 / 32 instances are held to 64 VGPRs for
+                              # that (`ops.gather_sum_occupancy`; at 72 they ran one workgroup, 16 waves, per CU)
 
 
 def auto_chunk(n_edges):
