@@ -1726,6 +1726,90 @@ int     tipk_distmult_pair_conf_topk(const float* z, int64_t n_nodes, int dim, c
                                      float* dense_logit, float* dense_var /* [n_pairs x n_rel], nullable together */,
                                      tipk_stream_t stream);
 
+/* 4q. Fit of the embedding of NEW drugs to their recorded interactions (serving; no reference call site): the dual of 4m.
+ *     The embeddings z of the training graph's drugs and the DistMult decoder rows rel_w of 4a stay frozen; the unknown is
+ *     the row x of a drug that is not a node of the graph, and a term is a CELL (partner v, side effect r).
+ *
+ *   Objective of new drug a with row x and prior centre c_a, s(v,r) = sum_k x[k] z[v,k] rel_w[r,k]:
+ *     L_a(x) = sum_{distinct recorded cells p} wpos_p softplus(-s_p)
+ *            + dense_w[a] * sum_{(v,r) in [0,n) x [0,R) NOT recorded} softplus(s)  +  l2/2 |x - c_a|^2
+ *   evaluated as  dense_w[a] * sum over ALL n R cells of softplus(s)  -- a mask-free stream --  plus, per distinct recorded
+ *   cell, wpos_p softplus(-s_p) - wneg_p softplus(s_p): wpos = multiplicity / P_a, wneg = dense_w[a] = neg_weight / N_a,
+ *   N_a = n R - the distinct recorded cells (tip_amd.ops.drug_fit_csr builds them).  DistMult is symmetric: a cell has no
+ *   direction.  The drug's pair with itself and pairs among new drugs are not part of the objective (the approximation of
+ *   4k).  s is linear in x, so L_a is convex in dim unknowns; the feature of a cell is f = z[v] * rel_w[r].
+ *
+ *   tipk_distmult_drug_fit_stats.  Input, DEVICE: z [n_nodes x dim] and rel_w [n_rel x dim], dense, 16-byte aligned; the
+ *   trial rows x [n_fit x dim]; dense_w fp32 [n_fit]; the distinct recorded cells as CSR: rec_ptr int64 [n_fit + 1], rec_v
+ *   in [0, n_nodes) / rec_r in [0, n_rel) int32 [n_rec] (the caller's contract; an id outside is clamped, nothing is read
+ *   out of bounds), rec_wpos / rec_wneg fp32 [n_rec]; prior [n_fit x dim], nullable (NULL: zeros); l2 >= 0; active int32
+ *   [n_fit], nullable (NULL: every drug).  Output: loss [n_fit], grad [n_fit x dim], hess [n_fit x dim x dim] (row-major,
+ *   both triangles), the l2 terms included.  Rows of an inactive drug are NOT touched.
+ *   Arithmetic, fp32.  Feature f_k = z[v,k] * rel_w[r,k] rounded once; logit: acc = fmaf(f_k, x[k], acc), k ascending from
+ *   +0.0f; softplus, sigma and sigma' from one expf exactly as in 4m.  Terms: loss c softplus, gradient c sigma f_i,
+ *   Hessian c sigma' f_i f_j with c = dense_w[a].
+ *   Summation order.  RECTANGULAR tiles of 64 partners x 64 side effects are numbered partner-block major; the tiles are
+ *   cut into tipk_distmult_drug_fit_slabs(n_nodes, dim, n_rel, n_fit) SLABS of equal length (the last may be shorter).  In
+ *   a tile wavefront q of 4 owns the partners v = 16 q .. 16 q + 15, in ascending order; within a partner the gradient and
+ *   Hessian entries take the 64 side effects in r order on v_mfma_f32_16x16x4_f32 with the cells as K (an exact fmaf
+ *   chain), the loss lane r adds its own term and the 64 lanes are summed at the end of the slab by the halving tree.  One
+ *   accumulator per (slab, wavefront) runs through the slab: at most 1 024 terms per tile.  Then, per output, the 4 * slabs
+ *   partials are added in ascending (slab, wavefront) order from +0.0f; the recorded cells are summed in chunks of 256 (a
+ *   chain from +0.0f in list order, the chunk totals added in ascending order from +0.0f); result = dense + sparse, then
+ *   + l2 term with d_k = x_k - c_k rounded once (loss: l2/2 times the fmaf chain of d_k^2; gradient: + l2 d_i; Hessian
+ *   diagonal: + l2).
+ *   tipk_distmult_drug_fit_max_chain(n_nodes, dim, n_rel, n_fit) = D, the largest number of fp32 additions a term passes
+ *   through:  max(1 024 * tiles per slab + 6 + 4 * slabs,  256 + ceil(n R / 256)) + 2.
+ *   Slabs and D depend on (n_nodes, dim, n_rel, n_fit) alone.  No floating-point atomics, no workgroup waits for another:
+ *   the results are BITWISE repeatable call to call.
+ *   Every drug streams every cell, whatever its dense_w.  A NaN logit makes every statistic of ITS drug NaN and touches no
+ *   other drug: a NaN in z or rel_w reaches every drug, a NaN in one trial row only that drug.
+ *   An INFINITE z[v,k] (no NaN logit: x[a,k] != 0, column k of rel_w without a zero, nothing else infinite) gives logits
+ *   of +-inf on every cell of partner v: for every drug with dense_w[a] > 0, grad[k] and row k and column k of hess are
+ *   non-finite (+inf or NaN: sigma' = 0 meets an infinite feature) and every other entry of grad and hess stays finite, so
+ *   tipk_newton_step ends that drug with status 3; the loss is non-finite as soon as one unrecorded cell has the logit +inf
+ *   or one recorded cell -inf.  Nothing finite is invented.  (A drug with dense_w[a] == 0 multiplies the infinite terms of
+ *   the stream by zero: its statistics are NaN where those of the others are infinite.)
+ *   Work: a dense launch of slabs x ceil(n_fit / 4) workgroups of 256 threads -- the feature of a cell is computed once
+ *   for the 4 drugs of the block; the tile's z rows and rel_w rows are staged in LDS (rows 16-byte aligned, stride width +
+ *   4 floats) -- then a finishing launch of one workgroup per drug.  A workgroup whose drugs are all inactive returns at
+ *   once.  Nothing of size n R reaches memory.
+ *   workspace: tipk_distmult_drug_fit_workspace_bytes(n_nodes, dim, n_rel, n_fit) bytes (-1: unsupported; n_fit == 0: 0),
+ *   which also holds the state of tipk_distmult_drug_fit; the statistics entry uses its head.
+ *
+ *   tipk_distmult_drug_fit.  Enqueues one initialising launch (start = init [n_fit x dim]; NULL: the prior; both NULL:
+ *   zeros) and max_iter + 1 (statistics, tipk_newton_step of 4m) pairs on `stream`; the active mask makes a finished drug's
+ *   workgroups return at once.  Output: out_x [n_fit x dim], out_loss [n_fit], out_grad [n_fit x dim] = the accepted row
+ *   and its statistics, out_info int32 [n_fit x 4] as in 4m (status 0 after max_iter + 1 evaluations: not converged);
+ *   out_hess [n_fit x dim x dim], nullable: the Hessian of the ACCEPTED row -- one more statistics pair at out_x after the
+ *   last step, so its bits are those of tipk_distmult_drug_fit_stats at out_x.
+ *   Supported: 1 <= n_nodes, 1 <= n_rel, n_nodes * n_rel < 2^31, dim % 4 == 0 in 4..32 (widths below 16 | 32 zero-padded
+ *   on chip), 1 <= n_fit <= 65 536; z and rel_w 16-byte aligned.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes, n_rel or dim < 1, l2 < 0
+ *   or NaN, gtol < 0 or NaN, max_iter < 0, a NULL required pointer (with n_fit > 0: everything but `prior`, `active`,
+ *   `init`, `out_hess` and, with n_rec == 0, the four cell arrays); then TIPK_EUNSUPPORTED outside the supported range;
+ *   n_fit == 0 is TIPK_OK with no launch and nothing written.
+ *   Nothing lives in host memory: the entries do NOT synchronise or allocate and may be captured into a hipGraph
+ *   (sequential launches, no parallel branches).
+ */
+int     tipk_distmult_drug_fit_supported(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_fit);
+int64_t tipk_distmult_drug_fit_slabs(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_fit);            /* -1 unsupported */
+int64_t tipk_distmult_drug_fit_max_chain(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_fit);        /* -1 unsupported */
+int64_t tipk_distmult_drug_fit_workspace_bytes(int64_t n_nodes, int dim, int64_t n_rel, int64_t n_fit);  /* -1 unsupported */
+int     tipk_distmult_drug_fit_stats(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                     const float* x, int64_t n_fit, const float* dense_w,
+                                     const int64_t* rec_ptr /* [n_fit+1] */, const int32_t* rec_v, const int32_t* rec_r,
+                                     const float* rec_wpos, const float* rec_wneg, int64_t n_rec,
+                                     const float* prior /* nullable: zeros */, float l2, const int32_t* active /* nullable */,
+                                     float* loss, float* grad, float* hess, void* workspace, tipk_stream_t stream);
+int     tipk_distmult_drug_fit(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel, int64_t n_fit,
+                               const float* dense_w, const int64_t* rec_ptr /* [n_fit+1] */, const int32_t* rec_v,
+                               const int32_t* rec_r, const float* rec_wpos, const float* rec_wneg, int64_t n_rec,
+                               const float* prior /* nullable: zeros */, float l2,
+                               const float* init /* nullable: the prior */, int max_iter, float gtol,
+                               float* out_x, float* out_loss, float* out_grad, int32_t* out_info,
+                               float* out_hess /* nullable */, void* workspace, tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

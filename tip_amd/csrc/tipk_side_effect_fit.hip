@@ -27,7 +27,7 @@
 //   solves with the vector in registers (one shuffle per column); a pivot that is not > 0 gives the scaled steepest-descent
 //   direction.
 #include "tipk_chol.h"
-#include <math.h>
+#include "tipk_fit_terms.h"
 
 namespace {
 
@@ -45,8 +45,6 @@ constexpr int64_t SF_FITMAX = 65536;
 constexpr int64_t SF_TARGET_WGS = 1024;     // dense workgroups to aim for: four per CU
 constexpr int SF_EPT = (1 + SF_DMAX + SF_DMAX * SF_DMAX + SF_CH - 1) / SF_CH;   // outputs per thread of the finish
 
-typedef float sf_f4 __attribute__((ext_vector_type(4)));
-
 struct FitStatsArgs {
     const float *z, *w, *dense_w;
     const int64_t* pair_ptr;
@@ -59,26 +57,6 @@ struct FitStatsArgs {
     float* part;
     float *loss, *grad, *hess;
 };
-
-__device__ __forceinline__ void sf_wave_sync() {               // LDS written by this wavefront is visible to it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// softplus(s), sigma(s) and sigma'(s) from one exponential; all NaN for a NaN logit.  The terms of a listed pair are the same
-// function at -s: softplus(-s), sigma(-s)
-__device__ __forceinline__ void sf_terms(float s, float& sp, float& sig, float& h) {
-    const float e = expf(-fabsf(s));
-    const float r = 1.0f / (1.0f + e);
-    sp = fmaxf(s, 0.f) + log1pf(e);
-    const float er = e * r;
-    sig = s >= 0.f ? r : er;
-    h = er * r;
-    if (s != s) sig = s;
-}
-
-__host__ __device__ inline int64_t sf_elems(int dim) { return 1 + dim + (int64_t)dim * dim; }
 
 template <int DP>
 __global__ void __launch_bounds__(SF_NT) fit_dense_kernel(FitStatsArgs a) {
@@ -480,8 +458,6 @@ FitShape sf_shape(int64_t n_nodes, int64_t n_fit) {
     s.slabs = (int)tipk_ceil_div(s.n_tiles, s.tps);
     return s;
 }
-
-int64_t sf_a256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // workspace: [dense partials] then the state of tipk_distmult_fit
 struct FitLayout {

@@ -41,6 +41,8 @@ ProteinExplanation = namedtuple('ProteinExplanation', ['logit', 'offset', 'featu
 NewDrugs = namedtuple('NewDrugs',['x0', 'h', 'z', 'degree', 'n_targets'])
 # TIP.fit_side_effects' result: per new side effect its fitted DistMult row and how the fit ended
 NewSideEffects = namedtuple('NewSideEffects', ['weight', 'loss', 'grad_norm', 'evaluations', 'status', 'n_pairs', 'decoder', 'known'])
+# what `TIP.fit_new_drugs` returns; `.z` makes it go wherever the `NewDrugs` of `embed_new_drugs` goes
+FittedDrugs = namedtuple('FittedDrugs', ['z', 'loss', 'grad_norm', 'evaluations', 'status', 'n_interactions', 'hess'])
 RegimenSideEffects = namedtuple('RegimenSideEffects', ['score', 'relation', 'u', 'v'])
 AddOnRisk = namedtuple('AddOnRisk', ['burden', 'candidate', 'ptr', 'best_burden', 'best_drug'])
 # TIP.combination_risk's result: the total burden of every combination of alternatives and each query's k safest ones
@@ -68,7 +70,7 @@ ConfidentSideEffects = namedtuple('ConfidentSideEffects', ['probability', 'mean_
                                                            'dense_logit', 'dense_std'])
 
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
-           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects',
+           'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects', 'FittedDrugs',
            'CombinationRisk', 'DecoderPosterior', 'ConfidentSideEffects']
 
 
@@ -2069,6 +2071,63 @@ class TIP(nn.Module):
             gn = grad.abs().amax(dim=1) if b else grad.new_zeros(0)
             return NewSideEffects(w, loss, gn, info[:, 1], info[:, 0], fp.n_pairs.to(dev), dec,
                                   tuple(t.to(dev) for t in fp.known))
+
+    def fit_new_drugs(self, interactions, prior=None, init=None, l2=1e-4, neg_weight=1.0, max_iter=16, gtol=1e-5):
+        """Fit the embedding of drugs that are NOT nodes of the training graph directly to the (partner drug, side effect)
+        reports recorded for them (extension): the dual of `fit_side_effects`, with the embeddings AND the DistMult decoder
+        frozen (`ops.distmult_drug_fit`: one `tipk_distmult_drug_fit` call enqueues every Newton step for all M drugs; under
+        no_grad on `self.embeddings` and `self.decoder.weight`).
+        interactions: a list of M lists of (partner drug id, side-effect id), or (index [2, P], ptr [M + 1])
+        (`ops.drug_fit_csr`): partners are EXISTING drugs; duplicates count.  Row x of drug a minimises the expectation of the
+        training objective over its negative draw,
+            1/P_a sum_listed softplus(-s) + neg_weight/N_a sum_{(v, r) not recorded} softplus(s) + l2/2 |x - c_a|^2,
+        s(v, r) = sum_k x[k] z[v,k] w[r,k]: a convex problem in dim unknowns.  The drug's pair with itself and pairs among new
+        drugs are not part of it -- the approximation of `embed_new_drugs`.
+        prior: the centres c_a -- None (zeros), a tensor [M, dim] or the `NewDrugs` of `embed_new_drugs`, whose .z is used;
+        init: the start, given the same way; None starts at the prior.  The intended call
+            new = model.embed_new_drugs(targets, interactions)
+            fit = model.fit_new_drugs(interactions, prior=new, l2=...)
+        starts from the fold-in row and moves it as far as the evidence says: l2 weighs the fold-in against the reports.
+        -> FittedDrugs(z [M, dim], loss [M], grad_norm [M] (max |gradient|), evaluations int64 [M], status int64 [M] (1
+        converged, 2 step underflow, 3 non-finite statistic, 0 not converged in max_iter + 1 evaluations), n_interactions int64
+        [M], hess [M, dim, dim]: the Hessian of the objective at z).  Every `new=` argument of the queries reads .z only, so the
+        result goes wherever a `NewDrugs` goes, and torch.cat([model.embeddings, fit.z]) through every decoder query.
+        NotImplementedError for the NN decoder (its logit is not linear in z: the fit is not convex), a relation-sharded model,
+        or widths `tipk_distmult_drug_fit_supported` refuses; ValueError for l2 < 0, neg_weight <= 0, max_iter < 0, gtol < 0,
+        an id out of range, or a `prior` / `init` of the wrong shape."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('fit_new_drugs fits against DistMult rows; this model scores with the NN decoder')
+        _refuse_sharded(self.shard, 'new drugs')
+        if not float(l2) >= 0:
+            raise ValueError('l2 must be >= 0, not %r' % (l2,))
+        if not float(neg_weight) > 0:
+            raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
+        if int(max_iter) < 0:
+            raise ValueError('max_iter must be >= 0, not %r' % (max_iter,))
+        if not float(gtol) >= 0:
+            raise ValueError('gtol must be >= 0, not %r' % (gtol,))
+        n, n_rel, dim = self.data.n_drug, self.data.n_dd_et, self.decoder.in_dim
+        fl = ops.drug_fit_csr(interactions, n, n_rel, neg_weight)
+        m = fl.dense_w.numel()
+        rows = {}
+        for name, given in (('prior', prior), ('init', init)):
+            if given is not None:
+                given = torch.as_tensor(given.z if hasattr(given, 'z') else given)
+                if tuple(given.shape) != (m, dim):
+                    raise ValueError('%s: [%d, %d] expected, got %s' % (name, m, dim, tuple(given.shape)))
+            rows[name] = given
+        if not ops.distmult_drug_fit_supported(n, dim, n_rel, max(m, 1)):
+            raise NotImplementedError('fit_new_drugs: tipk_distmult_drug_fit does not take n = %d, %d side effects, dim = %d, '
+                                      '%d drugs (include/tipk.h 4q)' % (n, n_rel, dim, m))
+        with torch.no_grad():
+            z, w = self.embeddings.detach(), self.decoder.weight.detach()
+            dev = z.device
+            rows = {k: None if v is None else v.detach().to(dev, torch.float32) for k, v in rows.items()}
+            x, loss, grad, info, hess = ops.distmult_drug_fit(z, w, fl, rows['prior'], l2, rows['init'], int(max_iter),
+                                                              float(gtol))
+            info = info.to(torch.int64)
+            gn = grad.abs().amax(dim=1) if m else grad.new_zeros(0)
+            return FittedDrugs(x, loss, gn, info[:, 1], info[:, 0], fl.n_interactions.to(dev), hess)
 
     def decoder_posterior(self, pairs=None, weight=None, relations=None, l2=1e-4, neg_weight=1.0, new=None):
         """How sure the decoder is of its rows (extension): a Gaussian (Laplace) posterior N(w_b, (P_b H_b)^-1) of DistMult

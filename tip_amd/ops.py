@@ -1638,7 +1638,154 @@ def distmult_fit(z, fp, l2=1e-4, init=None, max_iter=16, gtol=1e-5):
     return w, loss, grad, info
 
 
-CONF_MODES = {'moderated': 0, 'bound': 1}                             # TIPK_CONF_MODERATED, TIPK_CONF_BOUND
+# what `drug_fit_csr` returns: the distinct recorded cells of M new drugs and their weights (include/tipk.h 4q)
+DrugFitLists = collections.namedtuple('DrugFitLists', ['ptr', 'v', 'r', 'wpos', 'wneg', 'dense_w', 'n_interactions', 'known'])
+
+
+def drug_fit_csr(interactions, n_nodes, n_rel, neg_weight=1.0):
+    """The recorded interactions of M new drugs in the form the drug-fit entries read (host function, CPU tensors).
+
+    interactions: a list of M lists of (partner, side effect), or (index int [2, P], ptr int [M + 1]): row 0 the partners, row 1
+    the side effects, drug a owns the columns ptr[a]:ptr[a + 1].  A repeat is ONE distinct cell whose multiplicity is the
+    number of times it is listed.
+    -> DrugFitLists(ptr int64 [M + 1], v, r int32 [D], sorted by (v, r) inside a drug, wpos fp32 [D] = multiplicity / P_a,
+    wneg fp32 [D] = dense_w of the cell's drug, dense_w fp32 [M] = neg_weight / N_a, n_interactions int64 [M] = P_a (duplicates
+    count), known = (keys int64 v * n_rel + r, ptr int64 [M + 1]): the distinct cells, sorted inside each drug).
+    N_a = n_nodes * n_rel minus the distinct recorded cells; N_a == 0 gives dense_w = wneg = 0.
+    ValueError for an id outside [0, n_nodes) x [0, n_rel) or a malformed list."""
+    n, nr = int(n_nodes), int(n_rel)
+    if n < 1 or nr < 1:
+        raise ValueError('n_nodes and n_rel must be >= 1, not %d and %d' % (n, nr))
+    if not float(neg_weight) > 0:
+        raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
+    if isinstance(interactions, tuple) and len(interactions) == 2 and torch.is_tensor(interactions[0]):
+        idx, lptr = torch.as_tensor(interactions[0]).to('cpu'), torch.as_tensor(interactions[1]).to('cpu')
+        if idx.dtype.is_floating_point or lptr.dtype.is_floating_point or idx.dim() != 2 or idx.shape[0] != 2 or lptr.dim() != 1 \
+                or lptr.numel() < 1:
+            raise ValueError('interactions: (index int [2, P], ptr int [M + 1]) expected')
+        idx, lptr = idx.to(torch.int64), lptr.to(torch.int64)
+        if int(lptr[0]) != 0 or int(lptr[-1]) != idx.shape[1] or bool((lptr[1:] < lptr[:-1]).any()):
+            raise ValueError('interactions: ptr must rise from 0 to P = %d' % idx.shape[1])
+    else:
+        try:
+            rows = [[(int(v), int(r)) for v, r in lst] for lst in interactions]
+        except (TypeError, ValueError):
+            raise ValueError('interactions: a list of lists of (partner, side effect) expected') from None
+        lptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
+        if rows:
+            lptr[1:] = torch.cumsum(torch.tensor([len(r) for r in rows], dtype=torch.int64), 0)
+        flat = [p for r in rows for p in r]
+        idx = torch.tensor(flat, dtype=torch.int64).reshape(-1, 2).t() if flat else torch.zeros((2, 0), dtype=torch.int64)
+    if idx.numel() and (int(idx[0].min()) < 0 or int(idx[0].max()) >= n):
+        raise ValueError('partner id out of range: [%d, %d] for %d drugs' % (int(idx[0].min()), int(idx[0].max()), n))
+    if idx.numel() and (int(idx[1].min()) < 0 or int(idx[1].max()) >= nr):
+        raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (int(idx[1].min()), int(idx[1].max()), nr))
+    m = lptr.numel() - 1
+    cells = n * nr
+    n_inter = lptr[1:] - lptr[:-1]
+    drug = torch.repeat_interleave(torch.arange(m, dtype=torch.int64), n_inter)
+    key, count = torch.unique(drug * cells + idx[0] * nr + idx[1], return_counts=True)     # sorted by (drug, v, r)
+    ddrug, dkey = torch.div(key, cells, rounding_mode='floor'), key % cells
+    dptr = torch.zeros(m + 1, dtype=torch.int64)
+    dptr[1:] = torch.cumsum(torch.bincount(ddrug, minlength=m), 0)
+    n_neg = (float(cells) - (dptr[1:] - dptr[:-1]).to(torch.float64))
+    dense = torch.where(n_neg > 0, float(neg_weight) / n_neg.clamp(min=1.0), torch.zeros_like(n_neg))
+    wpos = count.to(torch.float64) / n_inter.to(torch.float64)[ddrug]
+    return DrugFitLists(dptr, torch.div(dkey, nr, rounding_mode='floor').to(torch.int32), (dkey % nr).to(torch.int32),
+                        wpos.to(torch.float32), dense[ddrug].to(torch.float32), dense.to(torch.float32), n_inter,
+                        (dkey.contiguous(), dptr.clone()))
+
+
+def _drug_fit_operands(z, rel_w, fl, prior, l2, who):
+    """z and rel_w as the drug-fit entries read them, the lists of `fl` (a `DrugFitLists`) and the prior on their device."""
+    z, rel_w = _f32c(z).contiguous(), _f32c(rel_w).contiguous()
+    require_device(z, rel_w, prior)
+    if z.dim() != 2 or rel_w.dim() != 2 or z.shape[1] != rel_w.shape[1]:
+        raise _lib.TipkError('%s: z [n, dim] and rel_w [n_rel, dim] expected, got %s and %s'
+                             % (who, tuple(z.shape), tuple(rel_w.shape)))
+    if not float(l2) >= 0:
+        raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
+    dev = z.device
+    lists = (fl.ptr.to(dev, torch.int64), fl.v.to(dev, torch.int32), fl.r.to(dev, torch.int32), fl.wpos.to(dev, torch.float32),
+             fl.wneg.to(dev, torch.float32), fl.dense_w.to(dev, torch.float32))
+    n_fit = lists[0].numel() - 1
+    if lists[5].numel() != n_fit or any(t.numel() != lists[1].numel() for t in lists[2:5]):
+        raise _lib.TipkError('%s: the interaction lists do not belong together' % who)
+    if prior is not None:
+        prior = _f32c(prior).contiguous()
+        if tuple(prior.shape) != (n_fit, z.shape[1]):
+            raise _lib.TipkError('%s: prior [%d, %d] expected, got %s' % (who, n_fit, z.shape[1], tuple(prior.shape)))
+    nbytes = lib().tipk_distmult_drug_fit_workspace_bytes(z.shape[0], z.shape[1], rel_w.shape[0], n_fit)
+    if nbytes < 0:
+        raise _lib.TipkError('%s: unsupported shape n = %d, n_rel = %d, dim = %d, n_fit = %d (include/tipk.h section 4q)'
+                             % (who, z.shape[0], rel_w.shape[0], z.shape[1], n_fit))
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    return z, rel_w, tuple(t.contiguous() for t in lists), prior, n_fit, ws
+
+
+def distmult_drug_fit_supported(n_nodes, dim, n_rel, n_fit=1):
+    return bool(lib().tipk_distmult_drug_fit_supported(n_nodes, dim, n_rel, n_fit))
+
+
+def distmult_drug_fit_stats(z, rel_w, x, fl, prior=None, l2=1e-4, active=None, out=None):
+    """Loss, gradient and Hessian of the new drugs' objective at the trial rows x [M, dim] (include/tipk.h section 4q).
+    fl: the `DrugFitLists` of `drug_fit_csr` (moved to z's device); prior: None (zeros) or the centres [M, dim] of the l2 term;
+    active: None or int [M], 0 = leave that drug's rows of `out` untouched; out: None or (loss [M], grad [M, dim], hess
+    [M, dim, dim]) to write into.
+    -> (loss, grad, hess), fp32, the l2 terms included.  Does not synchronise."""
+    z, rel_w, (rptr, rv, rr, wpos, wneg, dense), prior, n_fit, ws = _drug_fit_operands(z, rel_w, fl, prior, l2,
+                                                                                         'distmult_drug_fit_stats')
+    x = _f32c(x).contiguous()
+    require_device(x, active)
+    dim = z.shape[1]
+    if tuple(x.shape) != (n_fit, dim):
+        raise _lib.TipkError('distmult_drug_fit_stats: x [%d, %d] expected, got %s' % (n_fit, dim, tuple(x.shape)))
+    if active is not None:
+        active = active.to(torch.int32).contiguous()
+        if tuple(active.shape) != (n_fit,):
+            raise _lib.TipkError('distmult_drug_fit_stats: active [%d] expected, got %s' % (n_fit, tuple(active.shape)))
+    if out is None:
+        out = (torch.empty(n_fit, dtype=torch.float32, device=z.device),
+               torch.empty((n_fit, dim), dtype=torch.float32, device=z.device),
+               torch.empty((n_fit, dim, dim), dtype=torch.float32, device=z.device))
+    loss, grad, hess = out
+    check(lib().tipk_distmult_drug_fit_stats(ptr(z), z.shape[0], dim, ptr(rel_w), rel_w.shape[0], ptr(x), n_fit, ptr(dense),
+                                             ptr(rptr), ptr(rv), ptr(rr), ptr(wpos), ptr(wneg), rv.numel(), ptr(prior),
+                                             float(l2), ptr(active), ptr(loss), ptr(grad), ptr(hess), ptr(ws),
+                                             stream_ptr(z.device)), 'tipk_distmult_drug_fit_stats')
+    return loss, grad, hess
+
+
+def distmult_drug_fit(z, rel_w, fl, prior=None, l2=1e-4, init=None, max_iter=16, gtol=1e-5):
+    """Fit the embedding rows of M new drugs on the frozen z and rel_w by damped Newton steps: max_iter + 1 (statistics, step)
+    launches enqueued by ONE `tipk_distmult_drug_fit` call (include/tipk.h section 4q).  prior: None (zeros) or the centres
+    [M, dim] of the l2 term; init: None (the prior) or the start [M, dim].
+    -> (x [M, dim], loss [M], grad [M, dim], info int32 [M, 4] = (status, evaluations, accepted, rejected), hess [M, dim, dim]:
+    the Hessian at x); status 1 converged (max |grad| <= gtol), 2 step below 2^-20, 3 non-finite statistic, 0 still running after
+    max_iter + 1 evaluations.  Does not synchronise."""
+    z, rel_w, (rptr, rv, rr, wpos, wneg, dense), prior, n_fit, ws = _drug_fit_operands(z, rel_w, fl, prior, l2,
+                                                                                         'distmult_drug_fit')
+    dim, dev = z.shape[1], z.device
+    if int(max_iter) < 0 or not float(gtol) >= 0:
+        raise _lib.TipkError('distmult_drug_fit: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
+    if init is not None:
+        init = _f32c(init).contiguous()
+        require_device(init)
+        if tuple(init.shape) != (n_fit, dim):
+            raise _lib.TipkError('distmult_drug_fit: init [%d, %d] expected, got %s' % (n_fit, dim, tuple(init.shape)))
+    x = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
+    loss = torch.empty(n_fit, dtype=torch.float32, device=dev)
+    grad = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
+    info = torch.zeros((n_fit, 4), dtype=torch.int32, device=dev)
+    h = torch.empty((n_fit, dim, dim), dtype=torch.float32, device=dev)
+    check(lib().tipk_distmult_drug_fit(ptr(z), z.shape[0], dim, ptr(rel_w), rel_w.shape[0], n_fit, ptr(dense), ptr(rptr), ptr(rv),
+                                       ptr(rr), ptr(wpos), ptr(wneg), rv.numel(), ptr(prior), float(l2), ptr(init),
+                                       int(max_iter), float(gtol), ptr(x), ptr(loss), ptr(grad), ptr(info), ptr(h), ptr(ws),
+                                       stream_ptr(dev)), 'tipk_distmult_drug_fit')
+    return x, loss, grad, info, h
+
+
+CONF_MODES ={'moderated': 0, 'bound': 1}                             # TIPK_CONF_MODERATED, TIPK_CONF_BOUND
 
 
 def distmult_pair_conf_topk_supported(n_nodes, dim, n_rel, k=10):
