@@ -1810,6 +1810,95 @@ int     tipk_distmult_drug_fit(const float* z, int64_t n_nodes, int dim, const f
                                float* out_x, float* out_loss, float* out_grad, int32_t* out_info,
                                float* out_hess /* nullable */, void* workspace, tipk_stream_t stream);
 
+/* 4r. Calibration of the DistMult probabilities: a Platt map per side effect (serving; no reference call site).  The model
+ *     is trained on one uniform negative per positive, so sigma(logit) sits at a 1:1 class balance; the map
+ *     logit' = a_r logit + b_r is fitted on held-out positives against ALL unrecorded pairs at their true prevalence.  It
+ *     keeps every ranking inside a side effect (a_r > 0) and moves the level.
+ *
+ *   A QUERY q names a relation q_rel[q].  Its CELLS are the unordered pairs u < v of [0, n); three sets partition them:
+ *     TRAIN  the cells recorded for the relation in training, in either direction;
+ *     POS    the distinct given calibration pairs with u != v that are not in TRAIN;
+ *     NEG    every other cell.                                       M = |POS| + |NEG|.
+ *   Logit s(u,v), u < v, with exactly the arithmetic of wg_score_tile (4c, 4h): x = z[u,k] * w[k] rounded once, acc =
+ *   fmaf(x, z[v,k], acc), k ascending from +0.0f -- the screen's logit, bit for bit.  With t = fmaf(a, s, b):
+ *     L_q(a, b) = 1/M [ sum_POS softplus(-t) + sum_NEG softplus(t) ] + l2/2 (a - 1)^2
+ *   softplus exact (no epsilon), the intercept not penalised; l2 only bounds a on a separable list.  Convex in (a, b).
+ *   Evaluated as  dense_w[q] * sum over ALL cells of softplus(t)  -- a mask-free stream --  plus, per LISTED cell (the merged,
+ *   sorted list of the distinct TRAIN and POS cells, u < v: the caller's contract), wpos_p softplus(-t_p) + wneg_p
+ *   softplus(t_p):  dense_w = 1/M; a TRAIN cell has wpos = 0, wneg = -1/M; a POS cell wpos = 1/M, wneg = -1/M
+ *   (tip_amd.ops.calibration_lists builds them; M == 0: all three 0).  The logit of a listed cell is recomputed with the
+ *   same chain, so what the stream added is taken out at the same bits of s.
+ *
+ *   tipk_distmult_calibrate_stats.  Input, DEVICE: z [n_nodes x dim] dense, 16-byte aligned; rel_w [n_rel x dim]; q_rel
+ *   int32 [n_q] in [0, n_rel); the trial maps ab [n_q x 2] = (a, b); dense_w fp32 [n_q]; the listed cells as CSR: pair_ptr
+ *   int64 [n_q + 1], pair_u / pair_v int32 [n_pairs] in [0, n_nodes) (an id outside, also of q_rel, is clamped: nothing is
+ *   read out of bounds), pair_wpos / pair_wneg fp32 [n_pairs]; l2 >= 0; active int32 [n_q], nullable (NULL: every query).
+ *   Output: loss [n_q], grad [n_q x 2] = (dL/da, dL/db), hess [n_q x 2 x 2] (row-major, both triangles), the l2 terms
+ *   included: the layout tipk_newton_step(dim = 2, ...) reads.  Rows of an inactive query are NOT touched.
+ *   Arithmetic.  Per cell, fp32, from one expf as in 4m: e = expf(-|t|), r = 1.0f / (1.0f + e), softplus(t) = fmaxf(t, 0) +
+ *   log1pf(e), sigma = r (t >= 0) | e r, sigma' = e r r; the six terms softplus, sigma s, sigma, (sigma' s) s, sigma' s,
+ *   sigma', each product rounded once.
+ *   Summation order.  The tiles of 64 x 64 cells (u-block, v-block >= u-block; u-block major) are dealt to
+ *   tipk_distmult_calibrate_splits(n_nodes, dim, n_q) PARTS per query: part x of S owns the tiles [T x / S, T (x + 1) / S).
+ *   In a tile thread (ty, tx) of 16 x 16 owns the cells (4 ty + i, 4 tx + j) and adds their terms in fp32 in (i, j) order,
+ *   i major, from +0.0f; a cell with u >= v or v >= n adds +0.0f.  The tile's sum goes onto an fp64 accumulator of the
+ *   thread that runs through the part; at its end the 64 lanes of a wavefront are added by the halving tree (lane l +=
+ *   lane l + 32, 16, .., 1), the 4 wavefronts in ascending order from 0.0.  The finishing launch adds the parts in ascending
+ *   order from 0.0 (fp64); a listed cell's terms are scaled by wpos | wneg in fp64, thread x of 256 adds the cells x, x +
+ *   256, ... of the list in that order, threads and wavefronts are added as above;  result = dense_w * dense + sparse
+ *   + the l2 term (loss: l2/2 (a - 1)^2; grad[0]: l2 (a - 1); hess[0][0]: l2), all in fp64, rounded to fp32 ONCE.
+ *   tipk_distmult_calibrate_max_chain(n_nodes, dim, n_q) = D = 18, the most fp32 additions a term passes through: the 16
+ *   cells of a thread in a tile and the final rounding, + 1 for all the fp64 additions together.
+ *   Parts and D depend on (n_nodes, dim, n_q) alone.  No floating-point atomics, no workgroup waits for another, no trip
+ *   count depends on data: the results are BITWISE repeatable call to call.
+ *   A weight of exactly 0 (dense_w, wpos, wneg, wpos + wneg for the Hessian) makes its term ABSENT: it adds 0 whatever the
+ *   term is.  So a query with M == 0 has the l2 term alone, whatever its logits are.
+ *   A NaN logit makes every statistic of ITS query NaN (M > 0) and touches no other query (a NaN row of z reaches every
+ *   query with n >= 2, a NaN in a row of rel_w or in one (a, b) only the queries of that relation or that map).
+ *   An INFINITE z[u,k] (no NaN logit; w[k] != 0, the other entries of column k != 0, a != 0) gives t = +-inf on the cells of
+ *   row u: for a query with M > 0, grad[0], hess[0][0], hess[0][1] and hess[1][0] are non-finite (+-inf or NaN: sigma' = 0
+ *   meets an infinite s), so tipk_newton_step ends that query with status 3; grad[1] and hess[1][1] stay finite; the loss is
+ *   non-finite as soon as one cell has t = +inf or one POS cell t = -inf (a listed cell streamed at +inf is taken out
+ *   again: NaN).  Nothing finite is invented.
+ *   Work: a dense launch of n_q x parts workgroups of 256 threads -- the logits on the vector unit (the fp32 matrix cores
+ *   offer the same rate and do not overlap with it; the per-cell transform is the cost) --, then a finishing launch of one
+ *   workgroup per query.  A workgroup of an inactive query returns at once.  Nothing of size n^2 reaches memory.
+ *   workspace: tipk_distmult_calibrate_workspace_bytes(n_nodes, dim, n_q) bytes, 8-byte aligned (-1: unsupported; n_q ==
+ *   0: 0), which also holds the state of tipk_distmult_calibrate; the statistics entry uses its head.
+ *
+ *   tipk_distmult_calibrate.  Enqueues one initialising launch (start = init [n_q x 2]; NULL: the identity (1, 0)) and
+ *   max_iter + 1 (statistics, tipk_newton_step of 4m with dim = 2, through its C entry, as it is) pairs on `stream`; the
+ *   active mask makes a finished query's workgroups return at once.  Output: out_ab [n_q x 2], out_loss [n_q], out_grad
+ *   [n_q x 2] = the accepted map and its statistics, out_info int32 [n_q x 4] as in 4m (status 0 after max_iter + 1
+ *   evaluations: not converged).
+ *   Supported: 1 <= n_nodes <= 46 340, dim % 4 == 0 in 4..256, 1 <= n_q <= 65 536, n_rel < 2^31; z 16-byte aligned.
+ *   Status: TIPK_EINVAL -- before anything is launched or written -- for a negative size, n_nodes, dim or n_rel < 1, l2 < 0
+ *   or NaN, gtol < 0 or NaN, max_iter < 0, a NULL required pointer (with n_q > 0: everything but `active`, `init` and, with
+ *   n_pairs == 0, the four cell arrays); then TIPK_EUNSUPPORTED outside the supported range; n_q == 0 is TIPK_OK with no
+ *   launch and nothing written.
+ *   Nothing lives in host memory: the entries do NOT synchronise or allocate and may be captured into a hipGraph
+ *   (sequential launches, no parallel branches).
+ *   Applying the map needs no kernel: with z' = [z | 1 0 0 0] and w'_r = [a_r w_r | b_r 0 0 0] every DistMult entry of
+ *   section 4 computes a_r s + b_r up to rounding -- the constant column is the last term of the ascending fma chain.
+ */
+int     tipk_distmult_calibrate_supported(int64_t n_nodes, int dim, int64_t n_q);
+int64_t tipk_distmult_calibrate_splits(int64_t n_nodes, int dim, int64_t n_q);           /* -1 unsupported */
+int64_t tipk_distmult_calibrate_max_chain(int64_t n_nodes, int dim, int64_t n_q);        /* -1 unsupported */
+int64_t tipk_distmult_calibrate_workspace_bytes(int64_t n_nodes, int dim, int64_t n_q);  /* -1 unsupported */
+int     tipk_distmult_calibrate_stats(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                      const int32_t* q_rel, const float* ab /* [n_q x 2] */, int64_t n_q,
+                                      const float* dense_w, const int64_t* pair_ptr /* [n_q+1] */, const int32_t* pair_u,
+                                      const int32_t* pair_v, const float* pair_wpos, const float* pair_wneg, int64_t n_pairs,
+                                      float l2, const int32_t* active /* nullable */, float* loss, float* grad, float* hess,
+                                      void* workspace, tipk_stream_t stream);
+int     tipk_distmult_calibrate(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel,
+                                const int32_t* q_rel, int64_t n_q, const float* dense_w,
+                                const int64_t* pair_ptr /* [n_q+1] */, const int32_t* pair_u, const int32_t* pair_v,
+                                const float* pair_wpos, const float* pair_wneg, int64_t n_pairs, float l2,
+                                const float* init /* nullable: (1, 0) */, int max_iter, float gtol,
+                                float* out_ab, float* out_loss, float* out_grad, int32_t* out_info, void* workspace,
+                                tipk_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * 5. Typed negative sampling on device -- replaces typed_negative_sampling / negative_sampling,
  *    src/neg_sampling.py:5-26 (K11: host numpy + one D2H copy per relation).

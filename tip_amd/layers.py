@@ -69,9 +69,47 @@ class DecoderPosterior(namedtuple('DecoderPosterior', ['weight', 'factor', 'n_pa
 ConfidentSideEffects = namedtuple('ConfidentSideEffects', ['probability', 'mean_probability', 'logit', 'std', 'relation',
                                                            'dense_logit', 'dense_std'])
 
+
+class Calibration(namedtuple('Calibration', ['scale', 'offset', 'loss', 'loss_raw', 'expected_raw', 'n_pos', 'n_neg', 'n_dropped',
+                                             'evaluations', 'status', 'z', 'decoder'])):
+    """TIP.calibrate's result: the Platt map logit' = scale[r] * logit + offset[r] of every side effect r (include/tipk.h
+    section 4r) and the operands that apply it.  scale, offset, loss [R]: the fitted map and its objective; loss_raw,
+    expected_raw [R]: the objective and the sum of sigma(logit) over the POS and NEG cells at the identity map -- how many
+    positives the raw model expects where n_pos are held out; n_pos, n_neg, n_dropped int64 [R]; evaluations, status int64
+    [R] (1 converged, 2 step underflow, 3 non-finite statistic, 0 not converged, 4 not fitted: the identity is kept).
+    z [n_drug, dim + 4]: a detached SNAPSHOT of the embeddings widened by the columns (1, 0, 0, 0); decoder: a frozen
+    `MultiInnerProductDecoder(dim + 4, R)`, not registered in the model, with the rows [scale w_r | offset 0 0 0], so every
+    DistMult query on (z, decoder) computes scale * logit + offset."""
+    __slots__ = ()
+
+    def embed(self, x):
+        """Rows [M, dim] of further drugs (e.g. `NewDrugs.z`) widened to [M, dim + 4] as `z` is."""
+        x = torch.as_tensor(x).detach().to(self.z.device, self.z.dtype)
+        if x.dim() != 2 or x.shape[1] != self.z.shape[1] - 4:
+            raise ValueError('embed: rows [M, %d] expected, got %s' % (self.z.shape[1] - 4, tuple(x.shape)))
+        pad = x.new_zeros((x.shape[0], 4))
+        pad[:, 0] = 1.0
+        return torch.cat([x, pad], 1)
+
+
+def calibrated_operands(z, w, ab):
+    """The operands that apply the maps ab [R, 2] = (scale, offset) to the DistMult logit of z [n, dim] and w [R, dim]: z' =
+    [z | 1 0 0 0] and a frozen, unregistered `MultiInnerProductDecoder(dim + 4, R)` with the rows [scale w_r | offset 0 0 0].
+    The constant column is the last term of the ascending fma chain of every entry."""
+    n, dim = z.shape
+    wide = z.new_zeros((n, dim + 4))
+    wide[:, :dim], wide[:, dim] = z.detach(), 1.0
+    dec = MultiInnerProductDecoder(dim + 4, w.shape[0]).to(z.device)
+    dec.weight.data.zero_()
+    dec.weight.data[:, :dim] = ab[:, :1].to(w.dtype) * w.detach()
+    dec.weight.data[:, dim] = ab[:, 1].to(w.dtype)
+    dec.weight.requires_grad_(False)
+    return wide, dec
+
+
 __all__ = ['GCNConv', 'MyRGCNConv', 'MyRGCNConv2', 'MyHierarchyConv', 'PPEncoder', 'FMEncoder',
            'FMEncoderCat', 'MultiInnerProductDecoder', 'NNDecoder', 'Setting', 'TIP', 'NewSideEffects', 'FittedDrugs',
-           'CombinationRisk', 'DecoderPosterior', 'ConfidentSideEffects']
+           'CombinationRisk', 'DecoderPosterior', 'ConfidentSideEffects', 'Calibration']
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1410,6 +1448,28 @@ def _ids_at(pos, lookup, first=None):
     return torch.where(pos >= 0, lookup[at.clamp(min=0, max=lookup.numel() - 1)], torch.full_like(at, -1))
 
 
+def _scoring_operands(model, calibration):
+    """(z, decoder) a decoder query runs on: the model's own for None, else the widened snapshot and decoder of the
+    `Calibration`, refused unless they fit this model: NotImplementedError for the NN decoder or a relation-sharded
+    model, ValueError for another number of side effects, drugs or columns."""
+    if calibration is None:
+        return model.embeddings, model.decoder
+    if model.decoder_kind == 'nn':
+        raise NotImplementedError('a calibration widens DistMult operands; this model scores with the NN decoder '
+                                  '(include/tipk.h 4r)')
+    _refuse_sharded(model.shard, 'calibrated side effects')
+    if not isinstance(calibration, Calibration):
+        raise ValueError('calibration: the Calibration of TIP.calibrate expected, got %s' % type(calibration).__name__)
+    z, dec = calibration.z, calibration.decoder
+    if z.device != model.embeddings.device or dec.weight.device != z.device:
+        raise ValueError('calibration: its operands are on %s, the model is on %s' % (z.device, model.embeddings.device))
+    want = (model.data.n_drug, model.decoder.in_dim + 4)
+    if tuple(z.shape) != want or dec.num_et != model.decoder.num_et or dec.in_dim != want[1]:
+        raise ValueError('calibration: made for %d drugs, %d columns and %d side effects; this model has %d, %d + 4 and %d'
+                         % (z.shape[0], z.shape[1], dec.num_et, want[0], want[1] - 4, model.decoder.num_et))
+    return z, dec
+
+
 # ---------------------------------------------------------------------------------------------
 # A9  training framework   (src/layers.py:260-375)
 # ---------------------------------------------------------------------------------------------
@@ -1570,7 +1630,7 @@ class TIP(nn.Module):
             return (torch.zeros((0, k), device=pairs.device), torch.zeros((0, k), dtype=torch.int64, device=pairs.device))
         return torch.cat(vals), torch.cat(ids)
 
-    def side_effects(self, pairs, k=10, exclude=None, relations=None, sigmoid=True):
+    def side_effects(self, pairs, k=10, exclude=None, relations=None, sigmoid=True, calibration=None):
         """Serving (extension): the k side effects the model scores highest for every drug pair of `pairs` [2, P], among
         those not already recorded for the pair (`decoder.top_relations`: one `tipk_distmult_pair_topk` /
         `tipk_pair_table_pair_topk` launch on `self.embeddings`, under no_grad; both decoder kinds).
@@ -1578,6 +1638,9 @@ class TIP(nn.Module):
         test ones, None drops nothing; a recorded side effect is dropped in either pair direction.  relations: candidate
         side-effect ids (None = all); the returned ids are global.  Ranking is on the logit, ties by ascending position in
         `relations`; sigmoid = True applies sigma afterwards (padding: score sigma(-inf) = 0, relation -1).
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> SideEffects(score [P, k], relation int64 [P, k]) on the model's device."""
         _refuse_sharded(self.shard, 'side effects')
         _check_known_mode('exclude', exclude)
@@ -1593,12 +1656,14 @@ class TIP(nn.Module):
         rel = _relation_ids(relations, dev)
         known = _pair_known(d, exclude, rel)
         with torch.no_grad():
-            logit, idx = self.decoder.top_relations(self.embeddings, pairs, k, known, rel)
+            z, decoder = _scoring_operands(self, calibration)
+            logit, idx = decoder.top_relations(z, pairs, k, known, rel)
             score = torch.sigmoid(logit) if sigmoid else logit
             idx = idx.to(torch.int64) if rel is None else _ids_at(idx, rel)
         return SideEffects(score, idx)
 
-    def regimen_side_effects(self, regimens, k=10, aggregate='noisy_or', exclude=None, relations=None, probability=True):
+    def regimen_side_effects(self, regimens, k=10, aggregate='noisy_or', exclude=None, relations=None, probability=True,
+                             calibration=None):
         """Serving (extension): the k side effects the model expects most from every drug REGIMEN (a medication list), and the
         two drugs of the list that drive each (`decoder.top_regimen_relations`: one `tipk_distmult_regimen_topk` /
         `tipk_pair_table_regimen_topk` launch on `self.embeddings`, under no_grad; both decoder kinds).
@@ -1608,6 +1673,9 @@ class TIP(nn.Module):
         probability that at least one pair causes it; 'max' by its largest pair logit.  exclude / relations: as
         `side_effects` -- a recorded (pair, side effect) does not contribute.  probability = True maps the score after the
         kernel: sigmoid(A) for 'max', -expm1(-A) for 'noisy_or' (padding: score 0, relation -1, u = v = -1).
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> RegimenSideEffects(score [G, k], relation int64 [G, k], u int64 [G, k], v int64 [G, k]) on the model's device."""
         _refuse_sharded(self.shard, 'side effects')
         _check_known_mode('exclude', exclude)
@@ -1621,7 +1689,8 @@ class TIP(nn.Module):
         rel = _relation_ids(relations, dev)
         known = _pair_known(d, exclude, rel)
         with torch.no_grad():
-            score, idx, pi, pj = self.decoder.top_regimen_relations(self.embeddings, drugs_d, ptr_d, k, aggregate, known, rel)
+            z, decoder = _scoring_operands(self, calibration)
+            score, idx, pi, pj = decoder.top_regimen_relations(z, drugs_d, ptr_d, k, aggregate, known, rel)
             if probability:
                 score = torch.sigmoid(score) if aggregate == 'max' \
                     else torch.where(idx >= 0, -torch.expm1(-score), torch.zeros_like(score))   # (padding: -expm1(inf))
@@ -1630,7 +1699,7 @@ class TIP(nn.Module):
         return RegimenSideEffects(score, idx, u, v)
 
     def add_on_risk(self, regimens, candidates=None, k=10, replace=None, aggregate='noisy_or', weights=None, relations=None,
-                    exclude=None):
+                    exclude=None, calibration=None):
         """Serving (extension): which CANDIDATE drug adds the least expected side-effect burden to every drug regimen
         (`decoder.addon_burden`: one `tipk_distmult_addon_burden` / `tipk_pair_table_addon_burden` call on
         `self.embeddings`, under no_grad; both decoder kinds).  The burden of candidate c for a patient on drugs S is
@@ -1643,6 +1712,9 @@ class TIP(nn.Module):
         lists = one list per regimen (`normalize_add_on_queries`).  weights: None (every side effect counts 1) or one
         finite weight >= 0 per side effect -- per entry of `relations` when that is given --, e.g. a severity.
         exclude / relations: as `regimen_side_effects` -- a recorded (pair, side effect) does not contribute.
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> AddOnRisk(burden float32 [T], candidate int64 [T], ptr int64 [G + 1], best_burden float32 [G, k], best_drug
         int64 [G, k]) on the model's device: regimen g owns the tasks ptr[g]:ptr[g + 1] (flat CSR; for the two shared
         candidate forms `burden.view(G, C)`), burden NaN where a candidate is not applicable (a member of the context, an
@@ -1684,9 +1756,10 @@ class TIP(nn.Module):
         known = _pair_known(d, exclude, rel)
         with torch.no_grad():
             w_d = None if weights is None else weights.to(dev)
-            burden, best_b, best_p = self.decoder.addon_burden(self.embeddings, drugs_d, ptr_d, cand_d,
-                                                               None if cand_ptr is None else task_ptr_d, k, aggregate, w_d,
-                                                               known, rel)
+            z, decoder = _scoring_operands(self, calibration)
+            burden, best_b, best_p = decoder.addon_burden(z, drugs_d, ptr_d, cand_d,
+                                                          None if cand_ptr is None else task_ptr_d, k, aggregate, w_d,
+                                                          known, rel)
             if k == 0:
                 best_b = torch.empty((G, 0), dtype=torch.float32, device=dev)
                 best_drug = torch.empty((G, 0), dtype=torch.int64, device=dev)
@@ -1694,7 +1767,8 @@ class TIP(nn.Module):
                 best_drug = _ids_at(best_p, cand_flat_d, task_ptr_d[:-1, None])
         return AddOnRisk(burden.reshape(-1), cand_flat_d, task_ptr_d, best_b, best_drug)
 
-    def combination_risk(self, slots, fixed=None, k=10, aggregate='noisy_or', weights=None, relations=None, exclude=None):
+    def combination_risk(self, slots, fixed=None, k=10, aggregate='noisy_or', weights=None, relations=None, exclude=None,
+                         calibration=None):
         """Serving (extension): the TOTAL expected side-effect burden of every regimen that takes one alternative per open
         slot on top of the fixed drugs, and the k safest combinations (`decoder.combination_burden`:
         `tipk_distmult_combo_burden` / `tipk_pair_table_combo_burden` on `self.embeddings`, under no_grad; both decoder
@@ -1703,6 +1777,9 @@ class TIP(nn.Module):
         slots / fixed: as `normalize_combination_queries` -- one query (a list of slots) or a list of queries; an
         alternative of -1 leaves its slot empty, so `[[d, -1] for d in drugs]` asks which drugs of a list to stop.
         weights / relations / exclude: exactly as `add_on_risk`.
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> CombinationRisk(burden float32 [T], ptr int64 [G + 1], best_burden float32 [G, k], best_combination int64 [G, k],
         best_drugs int64 [G, k, S_max]) on the model's device: query g owns burden[ptr[g]:ptr[g + 1]], a combination's index
         is its position there, the last slot running fastest (itertools.product); NaN where a combination takes a drug
@@ -1737,7 +1814,8 @@ class TIP(nn.Module):
         known = _pair_known(d, exclude, rel)
         with torch.no_grad():
             w_d = None if weights is None else weights.to(dev)
-            burden, ptr_d, best_b, best_c = self.decoder.combination_burden(self.embeddings, plan, k, aggregate, w_d, known, rel)
+            z, decoder = _scoring_operands(self, calibration)
+            burden, ptr_d, best_b, best_c = decoder.combination_burden(z, plan, k, aggregate, w_d, known, rel)
             size = sptr[1:] - sptr[:-1]
             s_max = int(size.max()) if G else 0
             if k == 0:
@@ -2016,6 +2094,84 @@ class TIP(nn.Module):
                                            (r2.basis.detach(), r2.att.detach(), r2.root.detach()), xd.contiguous(), tgt, inter, cat)
             return NewDrugs(x0n, hn, zn, inter[0][1:] - inter[0][:-1], tgt[0][1:] - tgt[0][:-1])
 
+    def calibrate(self, pairs=None, relations=None, l2=1e-6, init=None, max_iter=32, gtol=1e-6):
+        """Calibrate the side-effect probabilities (extension): per side effect r a Platt map logit' = a_r logit + b_r, fitted
+        on held-out positives against ALL unrecorded pairs at their true prevalence (`ops.distmult_calibrate`: one
+        `tipk_distmult_calibrate` call enqueues every Newton step for all side effects; under no_grad on `self.embeddings`;
+        include/tipk.h section 4r).  The model is trained on one uniform negative per positive, so sigma(logit) sits at a
+        1:1 class balance: rankings are sound, expected counts are inflated.  The map keeps every ranking inside a side
+        effect (a_r > 0) and fixes the level.
+        pairs: None = the held-out set (data.dd_test_idx, data.dd_test_et), else (edge_index [2, T], edge_type [T]); both
+        directions and repeats are one pair, self pairs are dropped, a pair that is a training pair of its side effect is
+        dropped and counted.  relations: the side effects to fit (None = all); the others keep (1, 0) and status 4, and so
+        does one without a positive or without a negative.  For side effect r with POS its given cells, NEG every other
+        unordered pair that is not a training pair of r, M = |POS| + |NEG| and t = a s + b:
+            1/M [ sum_POS softplus(-t) + sum_NEG softplus(t) ] + l2/2 (a - 1)^2,
+        convex in (a, b).  l2 only bounds a on a separable list; 1e-6 is a modelling default.  init: None = (1, log((n_pos +
+        .5) / (n_neg + .5))), the prevalence start, or [R, 2].  gtol: the fit ends when max |gradient| <= gtol; the default
+        sits above the noise floor of the fp32 gradient.
+        -> `Calibration`; pass it as `calibration=` to `side_effects`, `regimen_side_effects`, `add_on_risk`,
+        `combination_risk`, `drug_profile` and `screen`.  It is a snapshot: calibrate again after further training.
+        NotImplementedError for the NN decoder, a relation-sharded model, or sizes `tipk_distmult_calibrate_supported`
+        refuses (include/tipk.h 4r); ValueError for l2 < 0, gtol < 0, max_iter < 0, an id out of range or an `init` of the
+        wrong shape."""
+        if self.decoder_kind == 'nn':
+            raise NotImplementedError('calibrate fits a map of the DistMult logit; this model scores with the NN decoder '
+                                      '(include/tipk.h 4r)')
+        _refuse_sharded(self.shard, 'calibrated side effects')
+        if not float(l2) >= 0:
+            raise ValueError('l2 must be >= 0, not %r' % (l2,))
+        if not float(gtol) >= 0:
+            raise ValueError('gtol must be >= 0, not %r' % (gtol,))
+        if int(max_iter) < 0:
+            raise ValueError('max_iter must be >= 0, not %r' % (max_iter,))
+        d = self.data
+        n, n_rel, dim = d.n_drug, d.n_dd_et, self.decoder.in_dim
+        if init is not None:
+            init = torch.as_tensor(init)
+            if tuple(init.shape) != (n_rel, 2):
+                raise ValueError('init: [%d, 2] expected, got %s' % (n_rel, tuple(init.shape)))
+        idx, et = _checked_triples(pairs, d, 'cpu')
+        rel = torch.arange(n_rel, dtype=torch.int64) if relations is None else _relation_ids(relations, 'cpu')
+        if rel.numel() and (int(rel.min()) < 0 or int(rel.max()) >= n_rel):
+            raise ValueError('side-effect id out of range: [%d, %d] for %d side effects' % (int(rel.min()), int(rel.max()), n_rel))
+        rel = torch.unique(rel)
+        if not ops.distmult_calibrate_supported(n, dim, n_rel) or not ops.distmult_calibrate_supported(n, dim + 4, n_rel):
+            raise NotImplementedError('calibrate: tipk_distmult_calibrate does not take n = %d, dim = %d, %d side effects '
+                                      '(include/tipk.h 4r)' % (n, dim, n_rel))
+        with torch.no_grad():
+            z, w = self.embeddings.detach(), self.decoder.weight.detach()
+            dev = z.device
+            train = (d.dd_train_idx, d.dd_train_et)
+            every = ops.calibration_lists(train, (idx, et), n, n_rel)                  # ONE pass over the triples: all side effects
+            ident = torch.zeros((n_rel, 2), dtype=torch.float32, device=dev)
+            ident[:, 0] = 1.0
+            loss_raw, grad_raw, _ = ops.distmult_calibrate_stats(z, w, ident, every, 0.0)
+            m_all = (every.n_pos + every.n_neg).to(dev)
+            n_pos_d = every.n_pos.to(dev)
+            # dL/db = (sum of sigma over POS and NEG - n_pos) / M
+            expected_raw = grad_raw[:, 1].double() * m_all.double() + n_pos_d.double()
+            fit_rel = rel[(every.n_pos[rel] > 0) & (every.n_neg[rel] > 0)]
+            ab = ident.clone()
+            loss = loss_raw.clone()
+            evals = torch.zeros(n_rel, dtype=torch.int64, device=dev)
+            status = torch.full((n_rel,), 4, dtype=torch.int64, device=dev)
+            if fit_rel.numel():
+                cl = ops.calibration_queries(every, fit_rel)                         # query r of `every` is side effect r
+                if init is None:
+                    start = torch.stack([torch.ones(fit_rel.numel(), dtype=torch.float64),
+                                         torch.log((cl.n_pos.double() + .5) / (cl.n_neg.double() + .5))], 1)
+                else:
+                    start = init.detach().to('cpu')[fit_rel]
+                got, l_fit, _, info = ops.distmult_calibrate(z, w, cl, l2, start.to(dev, torch.float32), int(max_iter),
+                                                             float(gtol))
+                at = fit_rel.to(dev)
+                ab[at], loss[at] = got, l_fit
+                evals[at], status[at] = info[:, 1].to(torch.int64), info[:, 0].to(torch.int64)
+            wide, dec = calibrated_operands(z, w, ab)
+            return Calibration(ab[:, 0].clone(), ab[:, 1].clone(), loss, loss_raw, expected_raw.to(torch.float32),
+                               n_pos_d, every.n_neg.to(dev), every.n_dropped.to(dev), evals, status, wide, dec)
+
     def fit_side_effects(self, pairs, l2=1e-4, neg_weight=1.0, init=None, max_iter=16, gtol=1e-5, new=None):
         """Learn side effects the model was NOT trained on (extension): one row of the DistMult decoder per new side effect
         from its recorded drug pairs, with the embeddings frozen (`ops.distmult_fit`: one `tipk_distmult_fit` call enqueues
@@ -2272,7 +2428,7 @@ class TIP(nn.Module):
             return ConfidentSideEffects(prob, mean, logit, torch.sqrt(var), _ids_at(idx, posterior.relation.to(dev)), d_logit,
                                         None if d_var is None else torch.sqrt(d_var))
 
-    def drug_profile(self, drugs=None, k=10, exclude='all', relations=None, partner_weights=None, new=None):
+    def drug_profile(self, drugs=None, k=10, exclude='all', relations=None, partner_weights=None, new=None, calibration=None):
         """Serving (extension): the liability profile of single drugs -- for every side effect, with how many OTHER drugs the
         model expects the drug to cause it, beyond the pairs already recorded (`decoder.partner_sums`: one
         `tipk_distmult_partner_sum` / `tipk_pair_table_partner_sum` call on `self.embeddings`, under no_grad; no N x N x R
@@ -2287,6 +2443,9 @@ class TIP(nn.Module):
         new: the `NewDrugs` of `embed_new_drugs`; an id n_drug + i in `drugs` then queries new drug i, on
         torch.cat([self.embeddings, new.z]).  The partners are the EXISTING drugs only (new drugs weigh 0, so they are never
         partners, of each other or of a training drug), and a new drug has no recorded list: nothing is dropped from its row.
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> DrugProfile(expected float32 [Q, R'], candidates int64 [Q, R']: the number of partners summed over, top_expected
         float32 [Q, k], top_relation int64 [Q, k]: the k side effects of each drug with the largest expectation, descending,
         ties by position in `relations`, padded with (-inf, -1)) on the model's device."""
@@ -2325,25 +2484,28 @@ class TIP(nn.Module):
         dev = self.embeddings.device
         known = _screen_known(d, exclude)
         with torch.no_grad():
-            z = self.embeddings
+            z, decoder = _scoring_operands(self, calibration)
             pw = None if partner_weights is None else partner_weights.to(dev)
             if new is not None:
-                z = torch.cat([z.detach(), new.z.detach().to(dev)])
+                z = torch.cat([z.detach(), new.z.detach().to(dev) if calibration is None else calibration.embed(new.z)])
                 ones = torch.ones(d.n_drug, dtype=torch.float32, device=dev) if pw is None else pw
                 pw = torch.cat([ones, torch.zeros(n_new, dtype=torch.float32, device=dev)])
                 known = _rekeyed_known(known, d.n_drug, n_all)
             rel = None if rel_host is None else rel_host.to(dev)
-            total, count, top_v, top_p = self.decoder.partner_sums(z, q_host.to(dev), k, rel, pw, known)
+            total, count, top_v, top_p = decoder.partner_sums(z, q_host.to(dev), k, rel, pw, known)
             top_rel = top_p.to(torch.int64) if rel is None else _ids_at(top_p, rel)
         return DrugProfile(total, count.to(torch.int64), top_v, top_rel)
 
-    def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True):
+    def screen(self, k=10, relations=None, drugs=None, exclude='train', sigmoid=True, calibration=None):
         """Serving (extension): the k drug pairs the model scores highest per side effect, among pairs not known to cause it
         (`MultiInnerProductDecoder.screen`, one `tipk_distmult_screen` call on `self.embeddings`, under no_grad).
         relations: side-effect ids (None = all); drugs: None = relation screen (pairs u < v), else the best partners v of
         each drug, drug-major.  exclude: 'train' drops the training positives (held-out test pairs can and do appear),
         'all' drops train and test positives (truly novel pairs), None drops nothing.  Ranking is on the logit; sigmoid
         = True applies sigma afterwards (padding: score sigma(-inf) = 0, u = v = -1).
+        calibration: None, or the `Calibration` of `calibrate`: the query then runs on its widened operands, so every logit
+        is scale[r] * logit + offset[r].  It is a SNAPSHOT of the embeddings -- calibrate again after further training --
+        and rankings within one side effect do not change for scale > 0.
         -> ScreenResult(score [Q, k], u [Q, k], v [Q, k], relation [Q, k]) on the model's device."""
         if self.decoder_kind == 'nn':
             raise NotImplementedError('screen ranks DistMult logits over all pairs; the NN decoder has no screen kernel')
@@ -2352,7 +2514,8 @@ class TIP(nn.Module):
         known = _screen_known(self.data, exclude)
         q = screen_queries(self.decoder.num_et, relations, drugs)
         with torch.no_grad():
-            logit, u, v = self.decoder.screen(self.embeddings, k, relations, drugs, known)
+            z, decoder = _scoring_operands(self, calibration)
+            logit, u, v = decoder.screen(z, k, relations, drugs, known)
             score = torch.sigmoid(logit) if sigmoid else logit
         relation = q[:, 0].to(device=logit.device, dtype=torch.int64)[:, None].expand(-1, logit.shape[1])
         return ScreenResult(score, u, v, relation)

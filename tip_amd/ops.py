@@ -1785,6 +1785,167 @@ def distmult_drug_fit(z, rel_w, fl, prior=None, l2=1e-4, init=None, max_iter=16,
     return x, loss, grad, info, h
 
 
+# what `calibration_lists` returns: per query the merged, sorted list of its distinct TRAIN and POS cells and their weights
+# (include/tipk.h 4r)
+CalibrationLists = collections.namedtuple('CalibrationLists', ['ptr', 'u', 'v', 'wpos', 'wneg', 'dense_w', 'q_rel', 'n_pos',
+                                                               'n_neg', 'n_dropped'])
+
+
+def _distinct_cells(edge_index, edge_type, n, n_rel, what):
+    """The distinct (relation, unordered pair u < v) of the triples, self pairs dropped, as sorted int64 keys
+    relation * n^2 + u * n + v (host)."""
+    idx, et = torch.as_tensor(edge_index).to('cpu'), torch.as_tensor(edge_type).to('cpu')
+    if idx.dim() != 2 or idx.shape[0] != 2 or et.dim() != 1 or et.numel() != idx.shape[1] or idx.dtype.is_floating_point \
+            or et.dtype.is_floating_point:
+        raise ValueError('%s: int tensors (edge_index [2, T], edge_type [T]) expected' % what)
+    idx, et = idx.to(torch.int64), et.to(torch.int64)
+    if et.numel():
+        if int(idx.min()) < 0 or int(idx.max()) >= n:
+            raise ValueError('%s: drug id out of range: [%d, %d] for %d drugs' % (what, int(idx.min()), int(idx.max()), n))
+        if int(et.min()) < 0 or int(et.max()) >= n_rel:
+            raise ValueError('%s: side-effect id out of range: [%d, %d] for %d side effects'
+                             % (what, int(et.min()), int(et.max()), n_rel))
+    lo, hi = torch.minimum(idx[0], idx[1]), torch.maximum(idx[0], idx[1])
+    return torch.unique((et * (n * n) + lo * n + hi)[lo != hi])
+
+
+def calibration_lists(train, given, n_nodes, n_rel, relations=None):
+    """The cells of a per-relation calibration in the form the entries of include/tipk.h section 4r read (host function, CPU
+    tensors).  train, given: (edge_index int [2, T], edge_type int [T]) -- the training triples and the calibration
+    (held-out) triples.  A pair is unordered: (u, v), (v, u) and repeats are ONE cell; self pairs are dropped; a given pair
+    that is also a training pair of its relation is dropped and counted.  relations: the ids that become the queries, in
+    that order (None: all n_rel).
+    -> CalibrationLists(ptr int64 [Q + 1], u, v int32 [D] with u < v, sorted by (u, v) inside a query, wpos fp32 [D] (1/M for
+    a POS cell, 0 for a TRAIN cell), wneg fp32 [D] = -1/M, dense_w fp32 [Q] = 1/M, q_rel int32 [Q], n_pos, n_neg, n_dropped
+    int64 [Q]); M = n (n - 1) / 2 - |TRAIN| = n_pos + n_neg; M == 0 gives dense_w = wpos = wneg = 0.
+    ValueError for an id outside its range or a malformed argument."""
+    n, n_rel = int(n_nodes), int(n_rel)
+    if n < 1 or n_rel < 1:
+        raise ValueError('n_nodes and n_rel must be >= 1, not %d and %d' % (n, n_rel))
+    tr = _distinct_cells(train[0], train[1], n, n_rel, 'train')
+    gv = _distinct_cells(given[0], given[1], n, n_rel, 'given')
+    if relations is None:
+        rel = torch.arange(n_rel, dtype=torch.int64)
+    else:
+        rel = torch.as_tensor(relations).to('cpu')
+        if rel.numel() and (rel.dtype.is_floating_point or rel.dtype == torch.bool):
+            raise ValueError('relations: int ids expected, got %s' % rel.dtype)
+        rel = rel.to(torch.int64).reshape(-1)
+        if rel.numel() and (int(rel.min()) < 0 or int(rel.max()) >= n_rel):
+            raise ValueError('relations: side-effect id out of range: [%d, %d] for %d side effects'
+                             % (int(rel.min()), int(rel.max()), n_rel))
+    in_train = torch.isin(gv, tr)
+    pos = gv[~in_train]
+    cells = n * n
+    per = lambda keys: torch.bincount(torch.div(keys, cells, rounding_mode='floor'), minlength=n_rel)   # noqa: E731
+    n_train, n_pos, n_drop = per(tr), per(pos), per(gv[in_train])
+    big_m = n * (n - 1) // 2 - n_train
+    merged, order = torch.sort(torch.cat([tr, pos]))                     # (TRAIN and POS are disjoint: no key twice)
+    is_pos = torch.cat([torch.zeros(tr.numel(), dtype=torch.bool), torch.ones(pos.numel(), dtype=torch.bool)])[order]
+    first = torch.searchsorted(merged, rel * cells)
+    last = torch.searchsorted(merged, (rel + 1) * cells)
+    count = last - first
+    ptr = torch.zeros(rel.numel() + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(count, 0)
+    q_of = torch.repeat_interleave(torch.arange(rel.numel(), dtype=torch.int64), count)
+    take = first[q_of] + torch.arange(int(ptr[-1]), dtype=torch.int64) - ptr[:-1][q_of]
+    key, posf = merged[take] % cells, is_pos[take]
+    m_q = big_m[rel].to(torch.float64)
+    dense = torch.where(m_q > 0, 1.0 / m_q.clamp(min=1.0), torch.zeros_like(m_q))
+    return CalibrationLists(ptr, torch.div(key, n, rounding_mode='floor').to(torch.int32), (key % n).to(torch.int32),
+                            torch.where(posf, dense[q_of], torch.zeros_like(dense[q_of])).to(torch.float32),
+                            (-dense[q_of]).to(torch.float32), dense.to(torch.float32), rel.to(torch.int32), n_pos[rel],
+                            big_m[rel] - n_pos[rel], n_drop[rel])
+
+
+def calibration_queries(cl, index):
+    """The queries `index` (int64 positions, in that order) of a `CalibrationLists` as a `CalibrationLists` of their own: a row
+    subset, no second pass over the triples (host)."""
+    index = torch.as_tensor(index, dtype=torch.int64).reshape(-1)
+    count = (cl.ptr[1:] - cl.ptr[:-1])[index]
+    ptr = torch.zeros(index.numel() + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(count, 0)
+    q_of = torch.repeat_interleave(torch.arange(index.numel(), dtype=torch.int64), count)
+    take = cl.ptr[:-1][index][q_of] + torch.arange(int(ptr[-1]), dtype=torch.int64) - ptr[:-1][q_of]
+    return CalibrationLists(ptr, cl.u[take], cl.v[take], cl.wpos[take], cl.wneg[take], cl.dense_w[index], cl.q_rel[index],
+                            cl.n_pos[index], cl.n_neg[index], cl.n_dropped[index])
+
+
+def _calibrate_operands(z, rel_w, cl, l2, who):
+    """z and rel_w as the calibration entries read them and the lists of `cl` (a `CalibrationLists`) on their device."""
+    z, rel_w = _distmult_operands(z, rel_w, who)
+    if not float(l2) >= 0:
+        raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
+    dev = z.device
+    lists = (cl.ptr.to(dev, torch.int64), cl.u.to(dev, torch.int32), cl.v.to(dev, torch.int32), cl.wpos.to(dev, torch.float32),
+             cl.wneg.to(dev, torch.float32), cl.dense_w.to(dev, torch.float32), cl.q_rel.to(dev, torch.int32))
+    n_q = lists[0].numel() - 1
+    if lists[5].numel() != n_q or lists[6].numel() != n_q or any(t.numel() != lists[1].numel() for t in lists[2:5]):
+        raise _lib.TipkError('%s: the cell lists do not belong together' % who)
+    nbytes = lib().tipk_distmult_calibrate_workspace_bytes(z.shape[0], z.shape[1], n_q)
+    if nbytes < 0:
+        raise _lib.TipkError('%s: unsupported shape n = %d, dim = %d, n_q = %d (include/tipk.h section 4r)'
+                             % (who, z.shape[0], z.shape[1], n_q))
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    return z, rel_w, tuple(t.contiguous() for t in lists), n_q, ws
+
+
+def distmult_calibrate_supported(n_nodes, dim, n_q=1):
+    return bool(lib().tipk_distmult_calibrate_supported(n_nodes, dim, n_q))
+
+
+def distmult_calibrate_stats(z, rel_w, ab, cl, l2=1e-6, active=None, out=None):
+    """Loss, gradient and Hessian of the calibration objective at the trial maps ab [Q, 2] = (scale, offset) (include/tipk.h
+    section 4r).  cl: the `CalibrationLists` of `calibration_lists` (moved to z's device); active: None or int [Q], 0 = leave
+    that query's rows of `out` untouched; out: None or (loss [Q], grad [Q, 2], hess [Q, 2, 2]) to write into.
+    -> (loss, grad, hess), fp32, the l2 term included.  Does not synchronise."""
+    z, rel_w, (pptr, pu, pv, wpos, wneg, dense, qrel), n_q, ws = _calibrate_operands(z, rel_w, cl, l2, 'distmult_calibrate_stats')
+    ab = _f32c(ab).contiguous()
+    require_device(ab, active)
+    if tuple(ab.shape) != (n_q, 2):
+        raise _lib.TipkError('distmult_calibrate_stats: ab [%d, 2] expected, got %s' % (n_q, tuple(ab.shape)))
+    if active is not None:
+        active = active.to(torch.int32).contiguous()
+        if tuple(active.shape) != (n_q,):
+            raise _lib.TipkError('distmult_calibrate_stats: active [%d] expected, got %s' % (n_q, tuple(active.shape)))
+    if out is None:
+        out = (torch.empty(n_q, dtype=torch.float32, device=z.device),
+               torch.empty((n_q, 2), dtype=torch.float32, device=z.device),
+               torch.empty((n_q, 2, 2), dtype=torch.float32, device=z.device))
+    loss, grad, hess = out
+    check(lib().tipk_distmult_calibrate_stats(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(qrel), ptr(ab),
+                                              n_q, ptr(dense), ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg), pu.numel(),
+                                              float(l2), ptr(active), ptr(loss), ptr(grad), ptr(hess), ptr(ws),
+                                              stream_ptr(z.device)), 'tipk_distmult_calibrate_stats')
+    return loss, grad, hess
+
+
+def distmult_calibrate(z, rel_w, cl, l2=1e-6, init=None, max_iter=32, gtol=1e-6):
+    """Fit the Platt map (scale, offset) of every query of `cl` by damped Newton steps on two unknowns: max_iter + 1
+    (statistics, step) launches enqueued by ONE `tipk_distmult_calibrate` call (include/tipk.h section 4r).  init: None (the
+    identity (1, 0)) or [Q, 2].
+    -> (ab [Q, 2], loss [Q], grad [Q, 2], info int32 [Q, 4] = (status, evaluations, accepted, rejected)); status as
+    `distmult_fit`.  Does not synchronise."""
+    z, rel_w, (pptr, pu, pv, wpos, wneg, dense, qrel), n_q, ws = _calibrate_operands(z, rel_w, cl, l2, 'distmult_calibrate')
+    dev = z.device
+    if int(max_iter) < 0 or not float(gtol) >= 0:
+        raise _lib.TipkError('distmult_calibrate: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
+    if init is not None:
+        init = _f32c(init).contiguous()
+        require_device(init)
+        if tuple(init.shape) != (n_q, 2):
+            raise _lib.TipkError('distmult_calibrate: init [%d, 2] expected, got %s' % (n_q, tuple(init.shape)))
+    ab = torch.empty((n_q, 2), dtype=torch.float32, device=dev)
+    loss = torch.empty(n_q, dtype=torch.float32, device=dev)
+    grad = torch.empty((n_q, 2), dtype=torch.float32, device=dev)
+    info = torch.zeros((n_q, 4), dtype=torch.int32, device=dev)
+    check(lib().tipk_distmult_calibrate(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(qrel), n_q, ptr(dense),
+                                        ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg), pu.numel(), float(l2), ptr(init),
+                                        int(max_iter), float(gtol), ptr(ab), ptr(loss), ptr(grad), ptr(info), ptr(ws),
+                                        stream_ptr(dev)), 'tipk_distmult_calibrate')
+    return ab, loss, grad, info
+
+
 CONF_MODES ={'moderated': 0, 'bound': 1}                             # TIPK_CONF_MODERATED, TIPK_CONF_BOUND
 
 
