@@ -93,6 +93,33 @@ def test_stats_relation_blocks(b):
         assert torch.equal(x, y[b - 1:]), name
 
 
+@pytest.mark.parametrize('n, tiles, slabs', [(129, 6, 3), (193, 10, 4)])
+def test_stats_slabs(n, tiles, slabs):
+    """More tiles than slabs (1 024 relations: 256 blocks; slabs of 2 of the 6 tiles at n = 129, of 3, 3, 3, 1 of the 10 tiles
+    at n = 193, so a slab starts in the middle of a tile row and runs into the next one) and fewer tiles than the slab target
+    (one relation: a slab per tile, 24 and 40 partials for the finish to add: whole batches and a tail); _max_chain bounds
+    what the partial layout implies."""
+    L = _lib.lib()
+    dim, b = 16, 1024
+    assert L.tipk_distmult_fit_slabs(n, dim, b) == slabs and L.tipk_distmult_fit_slabs(n, dim, 1) == tiles
+    for bb in (1, b):
+        s = L.tipk_distmult_fit_slabs(n, dim, bb)
+        tps = -(-tiles // s)
+        assert _chain(n, dim, bb) >= 16 * 64 * tps + 6 + 4 * s + 2
+    z = cases.embeddings(n, dim, 305, 2.0).to(DEV)
+    w = cases.trial_rows(b, dim, 'random', 405).to(DEV)
+    pick = [0, 1, 514, b - 1]
+    lists = [[] for _ in range(b)]
+    for i in pick:
+        lists[i] = cases.random_pairs(n, 40 + i % 7, 60 + i, selfs=True)
+    got = _raw_stats(z, w, ops.fit_pairs_csr(lists, n), 1e-4)
+    sub = tuple(v[pick] for v in got)
+    check_stats(z, w[pick], [lists[i] for i in pick], 1e-4, 1.0, sub, _chain(n, dim, b), what='%d slabs' % slabs)
+    assert all(bool(torch.isfinite(v).all()) for v in got)
+    one = _raw_stats(z, w[:1].contiguous(), ops.fit_pairs_csr(lists[:1], n), 1e-4)
+    check_stats(z, w[:1], lists[:1], 1e-4, 1.0, one, _chain(n, dim, 1), what='%d slabs' % tiles)
+
+
 def test_stats_n_fit_zero_launches_nothing():
     L = _lib.lib()
     z = cases.embeddings(5, 16, 1).to(DEV)

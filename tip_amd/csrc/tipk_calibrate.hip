@@ -1,6 +1,7 @@
 // Per-relation Platt calibration of the DistMult logit (include/tipk.h section 4r): the statistics (loss, gradient, Hessian)
 // of the calibration objective at trial maps t = a s + b, and an entry that enqueues max_iter + 1 (statistics,
-// tipk_newton_step with dim = 2) pairs.
+// tipk_newton_step with dim = 2) pairs: the step, the state layout, the init launch and the loop are tipk_newton.h /
+// tipk_newton.hip, shared with the two fits (4m, 4q).
 //
 // Statistics, launch 1, calib_dense_kernel: the sum over ALL cells u < v of a query's relation as a mask-free stream over
 //   the 64 x 64 tiles of the upper triangle.  Workgroup (query, part) takes the part's tiles as WgDeal deals them and scores
@@ -16,6 +17,7 @@
 // A workgroup of an inactive query returns at once; its rows of the outputs are not touched.
 // No atomics, no workgroup waits for another, every trip count depends on sizes and list lengths only: BITWISE repeatable.
 #include "tipk_fit_terms.h"
+#include "tipk_newton.h"
 #include "tipk_wg_topk.h"
 
 namespace {
@@ -180,41 +182,9 @@ __global__ void __launch_bounds__(WG_NT) calib_finish_kernel(CalArgs a) {
     }
 }
 
-struct CalInitArgs {
-    const float* init;
-    float *ab, *ab_trial, *loss, *grad, *p, *t;
-    int32_t *info, *active;
-    int64_t n_q;
-};
-
-__global__ void __launch_bounds__(256) calib_init_kernel(CalInitArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n_q) return;
-    const float ca = a.init ? a.init[2 * i] : 1.f, cb = a.init ? a.init[2 * i + 1] : 0.f;
-    a.ab[2 * i] = ca; a.ab[2 * i + 1] = cb; a.ab_trial[2 * i] = ca; a.ab_trial[2 * i + 1] = cb;
-    a.grad[2 * i] = 0.f; a.grad[2 * i + 1] = 0.f; a.p[2 * i] = 0.f; a.p[2 * i + 1] = 0.f;
-    a.loss[i] = 0.f; a.t[i] = 1.0f; a.active[i] = 1;
-    a.info[4 * i] = 0; a.info[4 * i + 1] = 0; a.info[4 * i + 2] = 0; a.info[4 * i + 3] = 0;
-}
-
 // workspace: [dense partials, fp64] then the state of tipk_distmult_calibrate
-struct CalLayout {
-    int64_t part, p, t, ab_trial, active, s_loss, s_grad, s_hess, total;
-};
-
-CalLayout cal_layout(int64_t n_nodes, int64_t n_q) {
-    CalLayout l;
-    int64_t o = 0;
-    l.part = o; o += sf_a256(n_q * wg_splits(n_nodes, n_q) * CAL_NS * 8);
-    l.p = o; o += sf_a256(n_q * 2 * 4);
-    l.t = o; o += sf_a256(n_q * 4);
-    l.ab_trial = o; o += sf_a256(n_q * 2 * 4);
-    l.active = o; o += sf_a256(n_q * 4);
-    l.s_loss = o; o += sf_a256(n_q * 4);
-    l.s_grad = o; o += sf_a256(n_q * 2 * 4);
-    l.s_hess = o; o += sf_a256(n_q * 4 * 4);
-    l.total = o;
-    return l;
+NewtonLayout cal_layout(int64_t n_nodes, int64_t n_q) {
+    return newton_layout(n_q * wg_splits(n_nodes, n_q) * CAL_NS * 8, n_q, 2);
 }
 
 int cal_stats_check(const float* z, int64_t n_nodes, int dim, const float* rel_w, int64_t n_rel, const int32_t* q_rel,
@@ -293,30 +263,13 @@ extern "C" int tipk_distmult_calibrate(const float* z, int64_t n_nodes, int dim,
                                     pair_wpos, pair_wneg, n_pairs, l2, out_loss, out_grad, out_loss, workspace);
     if (bad != TIPK_OK) return bad;
     if (n_q == 0) return TIPK_OK;
-    const CalLayout l = cal_layout(n_nodes, n_q);
-    char* ws = reinterpret_cast<char*>(workspace);
+    const NewtonState s = newton_state(workspace, cal_layout(n_nodes, n_q), n_q, 2, out_ab, out_loss, out_grad, out_info);
     hipStream_t st = (hipStream_t)stream;
 
-    CalInitArgs ia;
-    ia.init = init; ia.ab = out_ab; ia.ab_trial = reinterpret_cast<float*>(ws + l.ab_trial); ia.loss = out_loss;
-    ia.grad = out_grad; ia.p = reinterpret_cast<float*>(ws + l.p); ia.t = reinterpret_cast<float*>(ws + l.t);
-    ia.info = out_info; ia.active = reinterpret_cast<int32_t*>(ws + l.active); ia.n_q = n_q;
-    hipLaunchKernelGGL(calib_init_kernel, dim3((unsigned)tipk_ceil_div(n_q, 256)), dim3(256), 0, st, ia);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return tipk_hip_status(e);
-
     CalArgs a;
-    a.z = z; a.w = rel_w; a.ab = ia.ab_trial; a.dense_w = dense_w; a.qrel = q_rel; a.pair_ptr = pair_ptr; a.pair_u = pair_u;
-    a.pair_v = pair_v; a.pair_wpos = pair_wpos; a.pair_wneg = pair_wneg; a.active = ia.active; a.l2 = l2; a.n = (int)n_nodes;
-    a.dim = dim; a.n_rel = (int)n_rel; a.n_q = n_q; a.part = reinterpret_cast<double*>(ws + l.part);
-    a.loss = reinterpret_cast<float*>(ws + l.s_loss); a.grad = reinterpret_cast<float*>(ws + l.s_grad);
-    a.hess = reinterpret_cast<float*>(ws + l.s_hess);
-    for (int it = 0; it <= max_iter; ++it) {
-        int status = cal_stats_launch(a, st);
-        if (status != TIPK_OK) return status;
-        status = tipk_newton_step(2, n_q, a.loss, a.grad, a.hess, gtol, out_ab, out_loss, out_grad, ia.p, ia.t, out_info,
-                                  ia.ab_trial, ia.active, stream);
-        if (status != TIPK_OK) return status;
-    }
-    return TIPK_OK;
+    a.z = z; a.w = rel_w; a.ab = s.trial; a.dense_w = dense_w; a.qrel = q_rel; a.pair_ptr = pair_ptr; a.pair_u = pair_u;
+    a.pair_v = pair_v; a.pair_wpos = pair_wpos; a.pair_wneg = pair_wneg; a.active = s.active; a.l2 = l2; a.n = (int)n_nodes;
+    a.dim = dim; a.n_rel = (int)n_rel; a.n_q = n_q; a.part = reinterpret_cast<double*>(workspace);
+    a.loss = s.s_loss; a.grad = s.s_grad; a.hess = s.s_hess;
+    return newton_run(s, init, nullptr, 1.f, max_iter, gtol, st, [&] { return cal_stats_launch(a, st); });   // start: (1, 0)
 }

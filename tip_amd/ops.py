@@ -1502,6 +1502,31 @@ def pair_table_partner_sum(s1t, s2t, q_drug, k, rel_ids=None, partner_w=None, kn
 FitPairs = collections.namedtuple('FitPairs', ['ptr', 'u', 'v', 'wpos', 'wneg', 'dense_w', 'n_pairs', 'known'])
 
 
+def _ragged_lists(arg, what, item_names, tensor_form):
+    """A ragged argument of the fits' list builders -- a list of lists of 2-tuples, or (index int [2, P], ptr int [rows + 1])
+    -- as (index int64 [2, P], ptr int64 [rows + 1]) on the host.  ValueError names the argument `what`, the tuple's items
+    and the tensor form."""
+    if isinstance(arg, tuple) and len(arg) == 2 and torch.is_tensor(arg[0]):
+        idx, lptr = torch.as_tensor(arg[0]).to('cpu'), torch.as_tensor(arg[1]).to('cpu')
+        if idx.dtype.is_floating_point or lptr.dtype.is_floating_point or idx.dim() != 2 or idx.shape[0] != 2 or lptr.dim() != 1 \
+                or lptr.numel() < 1:
+            raise ValueError('%s: %s expected' % (what, tensor_form))
+        idx, lptr = idx.to(torch.int64), lptr.to(torch.int64)
+        if int(lptr[0]) != 0 or int(lptr[-1]) != idx.shape[1] or bool((lptr[1:] < lptr[:-1]).any()):
+            raise ValueError('%s: ptr must rise from 0 to P = %d' % (what, idx.shape[1]))
+        return idx, lptr
+    try:
+        rows = [[(int(a), int(b)) for a, b in lst] for lst in arg]
+    except (TypeError, ValueError):
+        raise ValueError('%s: a list of lists of %s expected' % (what, item_names)) from None
+    lptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
+    if rows:
+        lptr[1:] = torch.cumsum(torch.tensor([len(r) for r in rows], dtype=torch.int64), 0)
+    flat = [p for r in rows for p in r]
+    idx = torch.tensor(flat, dtype=torch.int64).reshape(-1, 2).t() if flat else torch.zeros((2, 0), dtype=torch.int64)
+    return idx, lptr
+
+
 def fit_pairs_csr(pairs, n_nodes, neg_weight=1.0):
     """The recorded pairs of B new side effects in the form the fit entries read (host function, CPU tensors).
 
@@ -1519,24 +1544,7 @@ def fit_pairs_csr(pairs, n_nodes, neg_weight=1.0):
         raise ValueError('n_nodes must be >= 1, not %d' % n)
     if not float(neg_weight) > 0:
         raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
-    if isinstance(pairs, tuple) and len(pairs) == 2 and torch.is_tensor(pairs[0]):
-        idx, lptr = torch.as_tensor(pairs[0]).to('cpu'), torch.as_tensor(pairs[1]).to('cpu')
-        if idx.dtype.is_floating_point or lptr.dtype.is_floating_point or idx.dim() != 2 or idx.shape[0] != 2 or lptr.dim() != 1 \
-                or lptr.numel() < 1:
-            raise ValueError('pairs: (edge_index int [2, P], ptr int [B + 1]) expected')
-        idx, lptr = idx.to(torch.int64), lptr.to(torch.int64)
-        if int(lptr[0]) != 0 or int(lptr[-1]) != idx.shape[1] or bool((lptr[1:] < lptr[:-1]).any()):
-            raise ValueError('pairs: ptr must rise from 0 to P = %d' % idx.shape[1])
-    else:
-        try:
-            rows = [[(int(u), int(v)) for u, v in lst] for lst in pairs]
-        except (TypeError, ValueError):
-            raise ValueError('pairs: a list of lists of (u, v) expected') from None
-        lptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
-        if rows:
-            lptr[1:] = torch.cumsum(torch.tensor([len(r) for r in rows], dtype=torch.int64), 0)
-        flat = [p for r in rows for p in r]
-        idx = torch.tensor(flat, dtype=torch.int64).reshape(-1, 2).t() if flat else torch.zeros((2, 0), dtype=torch.int64)
+    idx, lptr = _ragged_lists(pairs, 'pairs', '(u, v)', '(edge_index int [2, P], ptr int [B + 1])')
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
         raise ValueError('drug id out of range: [%d, %d] for %d drugs' % (int(idx.min()), int(idx.max()), n))
     b = lptr.numel() - 1
@@ -1561,6 +1569,60 @@ def fit_pairs_csr(pairs, n_nodes, neg_weight=1.0):
                     ((both % (n * n)).contiguous(), kptr))
 
 
+def _lists_on(dev, nt, term_ints, row_ints, who, what):
+    """The lists of a fit's named tuple `nt` on dev as the entries read them -> ((ptr int64, the per-term lists: `term_ints`
+    int32, wpos, wneg fp32, the per-row lists: dense_w fp32, `row_ints` int32), number of rows)."""
+    terms = [getattr(nt, f).to(dev, torch.int32) for f in term_ints] + [nt.wpos.to(dev, torch.float32),
+                                                                        nt.wneg.to(dev, torch.float32)]
+    rows = [nt.dense_w.to(dev, torch.float32)] + [getattr(nt, f).to(dev, torch.int32) for f in row_ints]
+    lptr = nt.ptr.to(dev, torch.int64)
+    n_rows = lptr.numel() - 1
+    if any(t.numel() != n_rows for t in rows) or any(t.numel() != terms[0].numel() for t in terms[1:]):
+        raise _lib.TipkError('%s: the %s lists do not belong together' % (who, what))
+    return tuple(t.contiguous() for t in [lptr] + terms + rows), n_rows
+
+
+def _fit_workspace(nbytes, dev, who, shape_text, section):
+    """The workspace of a fit entry from its *_workspace_bytes answer; a negative answer is an unsupported shape."""
+    if nbytes < 0:
+        raise _lib.TipkError('%s: unsupported shape %s (include/tipk.h section %s)' % (who, shape_text, section))
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+def _trial_active_out(x, active, out, n_rows, width, dev, who, name):
+    """What a *_stats wrapper takes besides the lists: the trial rows `name` [n_rows, width], the active mask and the
+    (loss, grad, hess) triple, made where `out` is None."""
+    x = _f32c(x).contiguous()
+    require_device(x, active)
+    if tuple(x.shape) != (n_rows, width):
+        raise _lib.TipkError('%s: %s [%d, %d] expected, got %s' % (who, name, n_rows, width, tuple(x.shape)))
+    if active is not None:
+        active = active.to(torch.int32).contiguous()
+        if tuple(active.shape) != (n_rows,):
+            raise _lib.TipkError('%s: active [%d] expected, got %s' % (who, n_rows, tuple(active.shape)))
+    if out is None:
+        out = (torch.empty(n_rows, dtype=torch.float32, device=dev),
+               torch.empty((n_rows, width), dtype=torch.float32, device=dev),
+               torch.empty((n_rows, width, width), dtype=torch.float32, device=dev))
+    return x, active, out
+
+
+def _newton_outputs(init, n_rows, width, max_iter, gtol, dev, who):
+    """What a fit wrapper takes besides the lists: max_iter and gtol checked, init [n_rows, width] or None as the entry reads
+    it, and the outputs -> (init, x [n_rows, width], loss [n_rows], grad [n_rows, width], info int32 [n_rows, 4])."""
+    if int(max_iter) < 0 or not float(gtol) >= 0:
+        raise _lib.TipkError('%s: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (who, max_iter, gtol))
+    if init is not None:
+        init = _f32c(init).contiguous()
+        require_device(init)
+        if tuple(init.shape) != (n_rows, width):
+            raise _lib.TipkError('%s: init [%d, %d] expected, got %s' % (who, n_rows, width, tuple(init.shape)))
+    return (init, torch.empty((n_rows, width), dtype=torch.float32, device=dev),
+            torch.empty(n_rows, dtype=torch.float32, device=dev),
+            torch.empty((n_rows, width), dtype=torch.float32, device=dev),
+            torch.zeros((n_rows, 4), dtype=torch.int32, device=dev))
+
+
 def _fit_operands(z, fp, l2, who):
     """z as the fit entries read it and the lists of `fp` (a `FitPairs`) on its device."""
     z = _f32c(z).contiguous()
@@ -1569,18 +1631,10 @@ def _fit_operands(z, fp, l2, who):
         raise _lib.TipkError('%s: z [n, dim] expected, got %s' % (who, tuple(z.shape)))
     if not float(l2) >= 0:
         raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
-    dev = z.device
-    lists = (fp.ptr.to(dev, torch.int64), fp.u.to(dev, torch.int32), fp.v.to(dev, torch.int32), fp.wpos.to(dev, torch.float32),
-             fp.wneg.to(dev, torch.float32), fp.dense_w.to(dev, torch.float32))
-    n_fit = lists[0].numel() - 1
-    if lists[5].numel() != n_fit or any(t.numel() != lists[1].numel() for t in lists[2:5]):
-        raise _lib.TipkError('%s: the pair lists do not belong together' % who)
-    nbytes = lib().tipk_distmult_fit_workspace_bytes(z.shape[0], z.shape[1], n_fit)
-    if nbytes < 0:
-        raise _lib.TipkError('%s: unsupported shape n = %d, dim = %d, n_fit = %d (include/tipk.h section 4m)'
-                             % (who, z.shape[0], z.shape[1], n_fit))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    return z, tuple(t.contiguous() for t in lists), n_fit, ws
+    lists, n_fit = _lists_on(z.device, fp, ('u', 'v'), (), who, 'pair')
+    ws = _fit_workspace(lib().tipk_distmult_fit_workspace_bytes(z.shape[0], z.shape[1], n_fit), z.device, who,
+                        'n = %d, dim = %d, n_fit = %d' % (z.shape[0], z.shape[1], n_fit), '4m')
+    return z, lists, n_fit, ws
 
 
 def distmult_fit_supported(n_nodes, dim, n_fit=1):
@@ -1593,20 +1647,8 @@ def distmult_fit_stats(z, w, fp, l2=1e-4, active=None, out=None):
     `out` untouched; out: None or (loss [B], grad [B, dim], hess [B, dim, dim]) to write into.
     -> (loss, grad, hess), fp32, the l2 terms included.  Does not synchronise."""
     z, (pptr, pu, pv, wpos, wneg, dense), n_fit, ws = _fit_operands(z, fp, l2, 'distmult_fit_stats')
-    w = _f32c(w).contiguous()
-    require_device(w, active)
     dim = z.shape[1]
-    if tuple(w.shape) != (n_fit, dim):
-        raise _lib.TipkError('distmult_fit_stats: w [%d, %d] expected, got %s' % (n_fit, dim, tuple(w.shape)))
-    if active is not None:
-        active = active.to(torch.int32).contiguous()
-        if tuple(active.shape) != (n_fit,):
-            raise _lib.TipkError('distmult_fit_stats: active [%d] expected, got %s' % (n_fit, tuple(active.shape)))
-    if out is None:
-        out = (torch.empty(n_fit, dtype=torch.float32, device=z.device),
-               torch.empty((n_fit, dim), dtype=torch.float32, device=z.device),
-               torch.empty((n_fit, dim, dim), dtype=torch.float32, device=z.device))
-    loss, grad, hess = out
+    w, active, (loss, grad, hess) = _trial_active_out(w, active, out, n_fit, dim, z.device, 'distmult_fit_stats', 'w')
     check(lib().tipk_distmult_fit_stats(ptr(z), z.shape[0], dim, ptr(w), n_fit, ptr(dense), ptr(pptr), ptr(pu), ptr(pv),
                                         ptr(wpos), ptr(wneg), pu.numel(), float(l2), ptr(active), ptr(loss), ptr(grad),
                                         ptr(hess), ptr(ws), stream_ptr(z.device)), 'tipk_distmult_fit_stats')
@@ -1621,17 +1663,7 @@ def distmult_fit(z, fp, l2=1e-4, init=None, max_iter=16, gtol=1e-5):
     evaluations.  Does not synchronise."""
     z, (pptr, pu, pv, wpos, wneg, dense), n_fit, ws = _fit_operands(z, fp, l2, 'distmult_fit')
     dim, dev = z.shape[1], z.device
-    if int(max_iter) < 0 or not float(gtol) >= 0:
-        raise _lib.TipkError('distmult_fit: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
-    if init is not None:
-        init = _f32c(init).contiguous()
-        require_device(init)
-        if tuple(init.shape) != (n_fit, dim):
-            raise _lib.TipkError('distmult_fit: init [%d, %d] expected, got %s' % (n_fit, dim, tuple(init.shape)))
-    w = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
-    loss = torch.empty(n_fit, dtype=torch.float32, device=dev)
-    grad = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
-    info = torch.zeros((n_fit, 4), dtype=torch.int32, device=dev)
+    init, w, loss, grad, info = _newton_outputs(init, n_fit, dim, max_iter, gtol, dev, 'distmult_fit')
     check(lib().tipk_distmult_fit(ptr(z), z.shape[0], dim, n_fit, ptr(dense), ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg),
                                   pu.numel(), float(l2), ptr(init), int(max_iter), float(gtol), ptr(w), ptr(loss), ptr(grad),
                                   ptr(info), ptr(ws), stream_ptr(dev)), 'tipk_distmult_fit')
@@ -1658,24 +1690,7 @@ def drug_fit_csr(interactions, n_nodes, n_rel, neg_weight=1.0):
         raise ValueError('n_nodes and n_rel must be >= 1, not %d and %d' % (n, nr))
     if not float(neg_weight) > 0:
         raise ValueError('neg_weight must be > 0, not %r' % (neg_weight,))
-    if isinstance(interactions, tuple) and len(interactions) == 2 and torch.is_tensor(interactions[0]):
-        idx, lptr = torch.as_tensor(interactions[0]).to('cpu'), torch.as_tensor(interactions[1]).to('cpu')
-        if idx.dtype.is_floating_point or lptr.dtype.is_floating_point or idx.dim() != 2 or idx.shape[0] != 2 or lptr.dim() != 1 \
-                or lptr.numel() < 1:
-            raise ValueError('interactions: (index int [2, P], ptr int [M + 1]) expected')
-        idx, lptr = idx.to(torch.int64), lptr.to(torch.int64)
-        if int(lptr[0]) != 0 or int(lptr[-1]) != idx.shape[1] or bool((lptr[1:] < lptr[:-1]).any()):
-            raise ValueError('interactions: ptr must rise from 0 to P = %d' % idx.shape[1])
-    else:
-        try:
-            rows = [[(int(v), int(r)) for v, r in lst] for lst in interactions]
-        except (TypeError, ValueError):
-            raise ValueError('interactions: a list of lists of (partner, side effect) expected') from None
-        lptr = torch.zeros(len(rows) + 1, dtype=torch.int64)
-        if rows:
-            lptr[1:] = torch.cumsum(torch.tensor([len(r) for r in rows], dtype=torch.int64), 0)
-        flat = [p for r in rows for p in r]
-        idx = torch.tensor(flat, dtype=torch.int64).reshape(-1, 2).t() if flat else torch.zeros((2, 0), dtype=torch.int64)
+    idx, lptr = _ragged_lists(interactions, 'interactions', '(partner, side effect)', '(index int [2, P], ptr int [M + 1])')
     if idx.numel() and (int(idx[0].min()) < 0 or int(idx[0].max()) >= n):
         raise ValueError('partner id out of range: [%d, %d] for %d drugs' % (int(idx[0].min()), int(idx[0].max()), n))
     if idx.numel() and (int(idx[1].min()) < 0 or int(idx[1].max()) >= nr):
@@ -1705,22 +1720,14 @@ def _drug_fit_operands(z, rel_w, fl, prior, l2, who):
                              % (who, tuple(z.shape), tuple(rel_w.shape)))
     if not float(l2) >= 0:
         raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
-    dev = z.device
-    lists = (fl.ptr.to(dev, torch.int64), fl.v.to(dev, torch.int32), fl.r.to(dev, torch.int32), fl.wpos.to(dev, torch.float32),
-             fl.wneg.to(dev, torch.float32), fl.dense_w.to(dev, torch.float32))
-    n_fit = lists[0].numel() - 1
-    if lists[5].numel() != n_fit or any(t.numel() != lists[1].numel() for t in lists[2:5]):
-        raise _lib.TipkError('%s: the interaction lists do not belong together' % who)
+    lists, n_fit = _lists_on(z.device, fl, ('v', 'r'), (), who, 'interaction')
     if prior is not None:
         prior = _f32c(prior).contiguous()
         if tuple(prior.shape) != (n_fit, z.shape[1]):
             raise _lib.TipkError('%s: prior [%d, %d] expected, got %s' % (who, n_fit, z.shape[1], tuple(prior.shape)))
-    nbytes = lib().tipk_distmult_drug_fit_workspace_bytes(z.shape[0], z.shape[1], rel_w.shape[0], n_fit)
-    if nbytes < 0:
-        raise _lib.TipkError('%s: unsupported shape n = %d, n_rel = %d, dim = %d, n_fit = %d (include/tipk.h section 4q)'
-                             % (who, z.shape[0], rel_w.shape[0], z.shape[1], n_fit))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    return z, rel_w, tuple(t.contiguous() for t in lists), prior, n_fit, ws
+    ws = _fit_workspace(lib().tipk_distmult_drug_fit_workspace_bytes(z.shape[0], z.shape[1], rel_w.shape[0], n_fit), z.device,
+                        who, 'n = %d, n_rel = %d, dim = %d, n_fit = %d' % (z.shape[0], rel_w.shape[0], z.shape[1], n_fit), '4q')
+    return z, rel_w, lists, prior, n_fit, ws
 
 
 def distmult_drug_fit_supported(n_nodes, dim, n_rel, n_fit=1):
@@ -1735,20 +1742,8 @@ def distmult_drug_fit_stats(z, rel_w, x, fl, prior=None, l2=1e-4, active=None, o
     -> (loss, grad, hess), fp32, the l2 terms included.  Does not synchronise."""
     z, rel_w, (rptr, rv, rr, wpos, wneg, dense), prior, n_fit, ws = _drug_fit_operands(z, rel_w, fl, prior, l2,
                                                                                          'distmult_drug_fit_stats')
-    x = _f32c(x).contiguous()
-    require_device(x, active)
     dim = z.shape[1]
-    if tuple(x.shape) != (n_fit, dim):
-        raise _lib.TipkError('distmult_drug_fit_stats: x [%d, %d] expected, got %s' % (n_fit, dim, tuple(x.shape)))
-    if active is not None:
-        active = active.to(torch.int32).contiguous()
-        if tuple(active.shape) != (n_fit,):
-            raise _lib.TipkError('distmult_drug_fit_stats: active [%d] expected, got %s' % (n_fit, tuple(active.shape)))
-    if out is None:
-        out = (torch.empty(n_fit, dtype=torch.float32, device=z.device),
-               torch.empty((n_fit, dim), dtype=torch.float32, device=z.device),
-               torch.empty((n_fit, dim, dim), dtype=torch.float32, device=z.device))
-    loss, grad, hess = out
+    x, active, (loss, grad, hess) = _trial_active_out(x, active, out, n_fit, dim, z.device, 'distmult_drug_fit_stats', 'x')
     check(lib().tipk_distmult_drug_fit_stats(ptr(z), z.shape[0], dim, ptr(rel_w), rel_w.shape[0], ptr(x), n_fit, ptr(dense),
                                              ptr(rptr), ptr(rv), ptr(rr), ptr(wpos), ptr(wneg), rv.numel(), ptr(prior),
                                              float(l2), ptr(active), ptr(loss), ptr(grad), ptr(hess), ptr(ws),
@@ -1766,17 +1761,7 @@ def distmult_drug_fit(z, rel_w, fl, prior=None, l2=1e-4, init=None, max_iter=16,
     z, rel_w, (rptr, rv, rr, wpos, wneg, dense), prior, n_fit, ws = _drug_fit_operands(z, rel_w, fl, prior, l2,
                                                                                          'distmult_drug_fit')
     dim, dev = z.shape[1], z.device
-    if int(max_iter) < 0 or not float(gtol) >= 0:
-        raise _lib.TipkError('distmult_drug_fit: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
-    if init is not None:
-        init = _f32c(init).contiguous()
-        require_device(init)
-        if tuple(init.shape) != (n_fit, dim):
-            raise _lib.TipkError('distmult_drug_fit: init [%d, %d] expected, got %s' % (n_fit, dim, tuple(init.shape)))
-    x = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
-    loss = torch.empty(n_fit, dtype=torch.float32, device=dev)
-    grad = torch.empty((n_fit, dim), dtype=torch.float32, device=dev)
-    info = torch.zeros((n_fit, 4), dtype=torch.int32, device=dev)
+    init, x, loss, grad, info = _newton_outputs(init, n_fit, dim, max_iter, gtol, dev, 'distmult_drug_fit')
     h = torch.empty((n_fit, dim, dim), dtype=torch.float32, device=dev)
     check(lib().tipk_distmult_drug_fit(ptr(z), z.shape[0], dim, ptr(rel_w), rel_w.shape[0], n_fit, ptr(dense), ptr(rptr), ptr(rv),
                                        ptr(rr), ptr(wpos), ptr(wneg), rv.numel(), ptr(prior), float(l2), ptr(init),
@@ -1876,18 +1861,10 @@ def _calibrate_operands(z, rel_w, cl, l2, who):
     z, rel_w = _distmult_operands(z, rel_w, who)
     if not float(l2) >= 0:
         raise _lib.TipkError('%s: l2 must be >= 0, not %r' % (who, l2))
-    dev = z.device
-    lists = (cl.ptr.to(dev, torch.int64), cl.u.to(dev, torch.int32), cl.v.to(dev, torch.int32), cl.wpos.to(dev, torch.float32),
-             cl.wneg.to(dev, torch.float32), cl.dense_w.to(dev, torch.float32), cl.q_rel.to(dev, torch.int32))
-    n_q = lists[0].numel() - 1
-    if lists[5].numel() != n_q or lists[6].numel() != n_q or any(t.numel() != lists[1].numel() for t in lists[2:5]):
-        raise _lib.TipkError('%s: the cell lists do not belong together' % who)
-    nbytes = lib().tipk_distmult_calibrate_workspace_bytes(z.shape[0], z.shape[1], n_q)
-    if nbytes < 0:
-        raise _lib.TipkError('%s: unsupported shape n = %d, dim = %d, n_q = %d (include/tipk.h section 4r)'
-                             % (who, z.shape[0], z.shape[1], n_q))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    return z, rel_w, tuple(t.contiguous() for t in lists), n_q, ws
+    lists, n_q = _lists_on(z.device, cl, ('u', 'v'), ('q_rel',), who, 'cell')
+    ws = _fit_workspace(lib().tipk_distmult_calibrate_workspace_bytes(z.shape[0], z.shape[1], n_q), z.device, who,
+                        'n = %d, dim = %d, n_q = %d' % (z.shape[0], z.shape[1], n_q), '4r')
+    return z, rel_w, lists, n_q, ws
 
 
 def distmult_calibrate_supported(n_nodes, dim, n_q=1):
@@ -1900,19 +1877,7 @@ def distmult_calibrate_stats(z, rel_w, ab, cl, l2=1e-6, active=None, out=None):
     that query's rows of `out` untouched; out: None or (loss [Q], grad [Q, 2], hess [Q, 2, 2]) to write into.
     -> (loss, grad, hess), fp32, the l2 term included.  Does not synchronise."""
     z, rel_w, (pptr, pu, pv, wpos, wneg, dense, qrel), n_q, ws = _calibrate_operands(z, rel_w, cl, l2, 'distmult_calibrate_stats')
-    ab = _f32c(ab).contiguous()
-    require_device(ab, active)
-    if tuple(ab.shape) != (n_q, 2):
-        raise _lib.TipkError('distmult_calibrate_stats: ab [%d, 2] expected, got %s' % (n_q, tuple(ab.shape)))
-    if active is not None:
-        active = active.to(torch.int32).contiguous()
-        if tuple(active.shape) != (n_q,):
-            raise _lib.TipkError('distmult_calibrate_stats: active [%d] expected, got %s' % (n_q, tuple(active.shape)))
-    if out is None:
-        out = (torch.empty(n_q, dtype=torch.float32, device=z.device),
-               torch.empty((n_q, 2), dtype=torch.float32, device=z.device),
-               torch.empty((n_q, 2, 2), dtype=torch.float32, device=z.device))
-    loss, grad, hess = out
+    ab, active, (loss, grad, hess) = _trial_active_out(ab, active, out, n_q, 2, z.device, 'distmult_calibrate_stats', 'ab')
     check(lib().tipk_distmult_calibrate_stats(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(qrel), ptr(ab),
                                               n_q, ptr(dense), ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg), pu.numel(),
                                               float(l2), ptr(active), ptr(loss), ptr(grad), ptr(hess), ptr(ws),
@@ -1928,17 +1893,7 @@ def distmult_calibrate(z, rel_w, cl, l2=1e-6, init=None, max_iter=32, gtol=1e-6)
     `distmult_fit`.  Does not synchronise."""
     z, rel_w, (pptr, pu, pv, wpos, wneg, dense, qrel), n_q, ws = _calibrate_operands(z, rel_w, cl, l2, 'distmult_calibrate')
     dev = z.device
-    if int(max_iter) < 0 or not float(gtol) >= 0:
-        raise _lib.TipkError('distmult_calibrate: max_iter >= 0 and gtol >= 0 expected, got %r and %r' % (max_iter, gtol))
-    if init is not None:
-        init = _f32c(init).contiguous()
-        require_device(init)
-        if tuple(init.shape) != (n_q, 2):
-            raise _lib.TipkError('distmult_calibrate: init [%d, 2] expected, got %s' % (n_q, tuple(init.shape)))
-    ab = torch.empty((n_q, 2), dtype=torch.float32, device=dev)
-    loss = torch.empty(n_q, dtype=torch.float32, device=dev)
-    grad = torch.empty((n_q, 2), dtype=torch.float32, device=dev)
-    info = torch.zeros((n_q, 4), dtype=torch.int32, device=dev)
+    init, ab, loss, grad, info = _newton_outputs(init, n_q, 2, max_iter, gtol, dev, 'distmult_calibrate')
     check(lib().tipk_distmult_calibrate(ptr(z), z.shape[0], z.shape[1], ptr(rel_w), rel_w.shape[0], ptr(qrel), n_q, ptr(dense),
                                         ptr(pptr), ptr(pu), ptr(pv), ptr(wpos), ptr(wneg), pu.numel(), float(l2), ptr(init),
                                         int(max_iter), float(gtol), ptr(ab), ptr(loss), ptr(grad), ptr(info), ptr(ws),
